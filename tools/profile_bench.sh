@@ -15,7 +15,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT $R/profiles
 touch $OUT/.start          # (the manifest lists what this call writes after this moment)
 STAGES=${STAGES:-"a b"}
-ARGS="--steps 3 --warmup 3 --no-cpu-baseline --no-configs"   # 3 warm-up steps: the first two run 5-10 % slower under the profiler
+ARGS="--full --steps 3 --warmup 3 --no-cpu-baseline --no-configs"   # --full: the event-timed last step and the unfused pass; 3 warm-up steps: the first two run 5-10 % slower under the profiler
 if [[ " $STAGES " == *" a "* ]]; then
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py $ARGS > $OUT/bench_trace.json 2> $OUT/bench_trace.err
@@ -45,7 +45,7 @@ bash tools/probe/pmc_kernel.sh $TAG fused rq_fused_linear_kernel3 > $OUT/pmc_fus
 bash tools/probe/pmc_kernel.sh $TAG hidden resnet_hidden_kernel > $OUT/pmc_hidden.log 2>&1 && cp gpurun_out/pmc_hidden_$TAG/summary.txt profiles/${TAG}_hidden_sq_counters.txt
 # the line of the profiled library, un-profiled, refusing any profile of another build: every profiles/${TAG}_* file must carry
 # the sha256 that this line reports as `library.sha256`
-python3 bench.py --steps 20 --warmup 5 --strict-profiles > profiles/${TAG}_bench_n1.json 2> $OUT/bench_final.err
+python3 bench.py --full --steps 20 --warmup 5 --strict-profiles > profiles/${TAG}_bench_n1.json 2> $OUT/bench_final.err
 echo "final strict bench exit $?"
 fi
 # the raw rocprofv3 tables cannot carry a field of their own: one manifest names every file of this tag with the library it
