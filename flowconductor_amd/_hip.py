@@ -14,11 +14,16 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # build of the same ABI call ``use_library(path)`` explicitly before the first kernel call (tools/ only).
 LIB_PATH = os.path.join(_HERE, "csrc", "libflowcon_hip.so")
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 ERR_OUTSIDE_DOMAIN = 1
 ERR_DISCRIMINANT = 2
 ERR_NONFINITE = 4
+ERR_NOT_LOWER_TRIANGULAR = 8
+ERR_DIAGONAL_NONPOSITIVE = 16
+ERR_NOT_SYMMETRIC = 32
+ERR_NOT_POSITIVE_DEFINITE = 64
+ERR_CHOLESKY_FAILED = 128
 
 
 class HipLibraryMissing(RuntimeError):
@@ -133,6 +138,11 @@ SIGNATURES = {
     "fc_comm_destroy": [_P],
     "fc_comm_abort": [_P],
     "fc_allreduce_loglik": [_P, _P, _P],
+    "fc_tril_pack": [_P, _P, _I64, _I32, _I32, _P],
+    "fc_matrix_diag": [_P, _P, _P, _I64, _I32, _I32, _P],
+    "fc_cholesky_outer": [_P, _P, _P, _P, _I64, _I32, _I32, _P],
+    "fc_cholesky_outer_backward": [_P, _P, _P, _P, _I64, _I32, _P],
+    "fc_cholesky": [_P, _P, _P, _P, _I64, _I32, _F, _I32, _P],
 }
 
 _lib = None

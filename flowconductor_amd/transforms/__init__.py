@@ -68,6 +68,7 @@ from flowconductor_amd.transforms.nonlinearities import (  # noqa: F401
 from flowconductor_amd.transforms.normalization import ActNorm, BatchNorm  # noqa: F401
 from flowconductor_amd.transforms.orthogonal import HouseholderSequence, ParametrizedHouseHolder  # noqa: F401
 from flowconductor_amd.transforms.permutations import (  # noqa: F401
+    FillTriangular,
     Permutation,
     RandomPermutation,
     ReversePermutation,
@@ -77,4 +78,10 @@ from flowconductor_amd.transforms.standard import (  # noqa: F401
     AffineTransform,
     IdentityTransform,
     PointwiseAffineTransform,
+)
+from flowconductor_amd.transforms.matrix import (  # noqa: F401
+    CholeskyOuterProduct,
+    TransformDiagonal,
+    TransformDiagonalExponential,
+    TransformDiagonalSoftplus,
 )

@@ -1,6 +1,7 @@
 """Feature permutations (same classes, constructor arguments and ``_permutation`` buffer as
 flowcon/transforms/permutations.py:10-64).  The gather itself is the ``fc_permute`` HIP kernel: bit-exact, zero
 log-determinant."""
+import numpy as np
 import torch
 
 from flowconductor_amd import ops
@@ -79,3 +80,45 @@ class ReversePermutation(Permutation):
     def __init__(self, features, dim=1):
         count = _need_feature_count(features)
         super().__init__(torch.arange(count - 1, -1, -1), dim)
+
+
+class FillTriangular(Transform):
+    """``[B, d] -> [B, m, m]`` with d = m (m + 1) / 2: the entries fill the lower triangle in ``np.tril_indices(m)``
+    order, zeros above (flowcon/transforms/permutations.py:67-113).  Zero logabsdet; the inverse gathers back.  Both
+    directions are the bit-exact ``fc_tril_pack`` HIP kernel, each the other's backward."""
+
+    _HIP_AUTOGRAD = True
+
+    def __init__(self, features: int = None, matrix_dimension: int = None):
+        super().__init__()
+        if (features is not None) and (matrix_dimension is None):
+            self.features = features
+            self.matrix_dim = self.calc_matrix_dimension(features)
+        elif (features is None) and (matrix_dimension is not None):
+            self.features = self.calc_n_ltri(matrix_dimension)
+            self.matrix_dim = matrix_dimension
+        else:
+            raise ValueError("Provide either 'features' or 'full_matrix_dimension', but not both.")
+        self.lower_indices = np.tril_indices(self.matrix_dim, k=0)
+
+    @staticmethod
+    def calc_matrix_dimension(n_ltri_entries):
+        assert n_ltri_entries > 0, f"Dimension must be positive, but is {n_ltri_entries}"
+        temp = 1 + 8 * n_ltri_entries
+        assert np.square(
+            np.floor(np.sqrt(temp))) == temp, "invalid dimension: can't be mapped to lower triangular matrix"
+        return int((-1 + np.floor(np.sqrt(temp))) // 2)
+
+    @staticmethod
+    def calc_n_ltri(matrix_dim):
+        return int((matrix_dim * (matrix_dim + 1)) / 2)
+
+    def forward(self, inputs, context=None):
+        assert inputs.shape[-1] == self.features
+        outputs = ops.fill_triangular(inputs, self.matrix_dim)
+        return outputs, inputs.new_zeros(inputs.shape[0])
+
+    def inverse(self, inputs, context=None):
+        assert inputs.shape[-2:] == (self.matrix_dim, self.matrix_dim)
+        outputs = ops.tril_gather(inputs)
+        return outputs, inputs.new_zeros(inputs.shape[0])

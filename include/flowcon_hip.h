@@ -32,11 +32,18 @@ extern "C" {
 #define FC_ERR_OUTSIDE_DOMAIN 1u /* InputOutsideDomain, splines/rational_quadratic.py:81-82 */
 #define FC_ERR_DISCRIMINANT 2u   /* assert (discriminant >= 0).all(), rational_quadratic.py:142 */
 #define FC_ERR_NONFINITE 4u
+/* flows on SPD matrices (transforms/matrix/cholesky.py:37-49; the checks run only under checkargs except the last) */
+#define FC_ERR_NOT_LOWER_TRIANGULAR 8u   /* a strictly-upper entry of CholeskyOuterProduct's input is not 0 */
+#define FC_ERR_DIAGONAL_NONPOSITIVE 16u  /* a diagonal entry of CholeskyOuterProduct's input is <= 0 */
+#define FC_ERR_NOT_SYMMETRIC 32u         /* inverse input != its transpose */
+#define FC_ERR_NOT_POSITIVE_DEFINITE 64u /* a Cholesky pivot <= 0 (stands in for the torch.linalg.eig test) */
+#define FC_ERR_CHOLESKY_FAILED 128u      /* a Cholesky pivot <= 0 without checkargs (torch.linalg.LinAlgError) */
 
 /* ABI version of this header; fc_abi_version() must return it.  Bumped whenever an exported entry, an accepted enum value
  * or a documented behaviour changes (2: round 4 -- fc_rq_fused_linear_backward is one launch, fc_comm_* entries of round 3,
- * FC_AFFINE_MAF_SOFTPLUS / FC_RQ_STREAMED_WEIGHTS). */
-#define FC_ABI_VERSION 2
+ * FC_AFFINE_MAF_SOFTPLUS / FC_RQ_STREAMED_WEIGHTS; 3: the SPD-matrix entries fc_tril_pack, fc_matrix_diag,
+ * fc_cholesky_outer(_backward), fc_cholesky and their FC_ERR_* bits). */
+#define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
 
@@ -341,6 +348,36 @@ int fc_standard_normal_log_prob(const float* z, const float* add, float* out, in
  * Replaces Permutation._permute (transforms/permutations.py:27-46, torch.index_select). */
 int fc_permute(const float* x, float* y, const int32_t* perm, int64_t outer, int32_t d,
                int64_t inner, void* stream);
+
+/* ---- flows on symmetric positive definite matrices ---------------------------------------- */
+/* All matrices are [batch, m, m] row-major float32, d = m (m + 1) / 2; x != y everywhere.
+ * fc_tril_pack     mode 0: y[b] = the m x m matrix with x[b, :] on and below the diagonal in np.tril_indices(m)
+ *                  order, zeros above (FillTriangular.forward, permutations.py:97-106); mode 1: the gather back,
+ *                  y[b, :] = x[b][tril_indices] (FillTriangular.inverse, :108-113).  Bit-exact; each mode is the
+ *                  other's backward.
+ * fc_matrix_diag   mode 0: diag[b, i] = x[b, i, i] (torch.diagonal); mode 1: y = x with its diagonal replaced by
+ *                  diag (torch.diagonal_scatter, matrix/diagonal.py:37-45); x == NULL reads as zeros (the
+ *                  backward of mode 0).  Bit-exact.
+ * fc_cholesky_outer  y = 0.5 (L L^T + (L L^T)^T) over the FULL input (upper part included),
+ *                  logabsdet[b] = m log 2 + sum_i (m - i) log L_ii (CholeskyOuterProduct.forward,
+ *                  matrix/cholesky.py:18-25).  checkargs != 0 ORs FC_ERR_NOT_LOWER_TRIANGULAR /
+ *                  FC_ERR_DIAGONAL_NONPOSITIVE into err_flag (:37-43).  logabsdet may be NULL.
+ * fc_cholesky_outer_backward  grad_inputs = (G + G^T) L + diag((m - i) grad_logabsdet[b] / L_ii), the autograd of
+ *                  the forward over the full m x m input; grad_outputs or grad_logabsdet may be NULL (zero).
+ * fc_cholesky      L = chol(A + eps I) with exact zeros above the diagonal, the jitter added in float32 first;
+ *                  logabsdet[b] = -(m log 2 + sum_i (m - i) log L_ii) (CholeskyOuterProduct.inverse, :27-35).
+ *                  checkargs != 0: FC_ERR_NOT_SYMMETRIC when A != A^T, FC_ERR_NOT_POSITIVE_DEFINITE on a pivot
+ *                  <= 0; checkargs == 0: FC_ERR_CHOLESKY_FAILED on a pivot <= 0.  err_flag is required.
+ * 1 <= m <= FC_SPD_MAX_DIM for the three matrix entries (hipErrorInvalidValue otherwise). */
+#define FC_SPD_MAX_DIM 128
+int fc_tril_pack(const float* x, float* y, int64_t batch, int32_t m, int32_t mode, void* stream);
+int fc_matrix_diag(const float* x, float* diag, float* y, int64_t batch, int32_t m, int32_t mode, void* stream);
+int fc_cholesky_outer(const float* L, float* y, float* logabsdet, uint32_t* err_flag, int64_t batch, int32_t m,
+                      int32_t checkargs, void* stream);
+int fc_cholesky_outer_backward(const float* L, const float* grad_outputs, const float* grad_logabsdet,
+                               float* grad_inputs, int64_t batch, int32_t m, void* stream);
+int fc_cholesky(const float* A, float* L, float* logabsdet, uint32_t* err_flag, int64_t batch, int32_t m, float eps,
+                int32_t checkargs, void* stream);
 
 /* ---- batch-shared point-wise affine maps ---------------------------------------------------- */
 /* x, y viewed as [n, m] (m = elements of one batch item); scale/shift have 1 or m entries.
