@@ -143,6 +143,8 @@ SIGNATURES = {
     "fc_cholesky_outer": [_P, _P, _P, _P, _I64, _I32, _I32, _P],
     "fc_cholesky_outer_backward": [_P, _P, _P, _P, _I64, _I32, _P],
     "fc_cholesky": [_P, _P, _P, _P, _I64, _I32, _F, _I32, _P],
+    "fc_squeeze": [_P, _P, _I64, _I32, _I32, _I32, _I32, _P],
+    "fc_conv1x1": [_P, _P, _P, _P, _P, _I64, _I32, _I64, _P],
 }
 
 _lib = None

@@ -269,3 +269,65 @@ class ResidualNet(ops.RuntimeCaches, nn.Module):
         if getattr(self, "_hip_packed", None) is None or self._hip_packed[0] != key:
             self._hip_packed = (key, ops.pack_resnet_hidden(self))
         return ops.resnet_hidden(rows, id_cols, self._hip_packed[1], in_features, len(self.blocks), context, act)
+
+
+class ConvResidualBlock(nn.Module):
+    """Pre-activation block of two 3x3 convolutions: x + conv1(drop(act(bn(conv0(act(bn(x))))))) with an optional
+    GLU gate on a 1x1 convolution of the context (flowcon/nn/nets/resnet.py:103-152).  A conditioner: plain torch
+    (MIOpen) convolutions."""
+
+    def __init__(self, channels, context_channels=None, activation=F.relu, dropout_probability=0.0,
+                 use_batch_norm=False, zero_initialization=True):
+        super().__init__()
+        self.activation = activation
+        if context_channels is not None:
+            self.context_layer = nn.Conv2d(in_channels=context_channels, out_channels=channels, kernel_size=1,
+                                           padding=0)
+        self.use_batch_norm = use_batch_norm
+        if use_batch_norm:
+            self.batch_norm_layers = nn.ModuleList(nn.BatchNorm2d(channels, eps=1e-3) for _ in range(2))
+        self.conv_layers = nn.ModuleList(nn.Conv2d(channels, channels, kernel_size=3, padding=1) for _ in range(2))
+        self.dropout = nn.Dropout(p=dropout_probability)
+        if zero_initialization:
+            nn.init.uniform_(self.conv_layers[-1].weight, -1e-3, 1e-3)
+            nn.init.uniform_(self.conv_layers[-1].bias, -1e-3, 1e-3)
+
+    def forward(self, inputs, context=None):
+        h = inputs
+        for i in range(2):
+            if self.use_batch_norm:
+                h = self.batch_norm_layers[i](h)
+            h = self.activation(h)
+            if i == 1:
+                h = self.dropout(h)
+            h = self.conv_layers[i](h)
+        if context is not None:
+            h = F.glu(torch.cat((h, self.context_layer(context)), dim=1), dim=1)
+        return inputs + h
+
+
+class ConvResidualNet(nn.Module):
+    """1x1 conv -> num_blocks x ConvResidualBlock -> 1x1 conv, for [N, C, H, W] inputs (resnet.py:155-209); the
+    context, if any, is concatenated to the input channels and gates every block."""
+
+    def __init__(self, in_channels, out_channels, hidden_channels, context_channels=None, num_blocks=2,
+                 activation=F.relu, dropout_probability=0.0, use_batch_norm=False):
+        super().__init__()
+        self.context_channels = context_channels
+        self.hidden_channels = hidden_channels
+        first_in = in_channels if context_channels is None else in_channels + context_channels
+        self.initial_layer = nn.Conv2d(in_channels=first_in, out_channels=hidden_channels, kernel_size=1, padding=0)
+        self.blocks = nn.ModuleList(
+            ConvResidualBlock(channels=hidden_channels, context_channels=context_channels, activation=activation,
+                              dropout_probability=dropout_probability, use_batch_norm=use_batch_norm)
+            for _ in range(num_blocks))
+        self.final_layer = nn.Conv2d(hidden_channels, out_channels, kernel_size=1, padding=0)
+
+    def forward(self, inputs, context=None):
+        if context is None:
+            temps = self.initial_layer(inputs)
+        else:
+            temps = self.initial_layer(torch.cat((inputs, context), dim=1))
+        for block in self.blocks:
+            temps = block(temps, context)
+        return self.final_layer(temps)

@@ -13,6 +13,7 @@ from flowconductor_amd.transforms.base import (  # noqa: F401
     InputOutsideDomain,
     InverseNotAvailable,
     InverseTransform,
+    MultiscaleCompositeTransform,
     Transform,
 )
 from flowconductor_amd.transforms.conditional import (  # noqa: F401
@@ -85,3 +86,5 @@ from flowconductor_amd.transforms.matrix import (  # noqa: F401
     TransformDiagonalExponential,
     TransformDiagonalSoftplus,
 )
+from flowconductor_amd.transforms.conv import OneByOneConvolution  # noqa: F401
+from flowconductor_amd.transforms.reshape import SqueezeTransform  # noqa: F401

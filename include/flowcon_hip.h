@@ -42,7 +42,8 @@ extern "C" {
 /* ABI version of this header; fc_abi_version() must return it.  Bumped whenever an exported entry, an accepted enum value
  * or a documented behaviour changes (2: round 4 -- fc_rq_fused_linear_backward is one launch, fc_comm_* entries of round 3,
  * FC_AFFINE_MAF_SOFTPLUS / FC_RQ_STREAMED_WEIGHTS; 3: the SPD-matrix entries fc_tril_pack, fc_matrix_diag,
- * fc_cholesky_outer(_backward), fc_cholesky and their FC_ERR_* bits). */
+ * fc_cholesky_outer(_backward), fc_cholesky and their FC_ERR_* bits).  The image-flow entries fc_squeeze / fc_conv1x1
+ * were added under version 3: they change no existing entry, and a library without them fails to bind by name). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -378,6 +379,23 @@ int fc_cholesky_outer_backward(const float* L, const float* grad_outputs, const 
                                float* grad_inputs, int64_t batch, int32_t m, void* stream);
 int fc_cholesky(const float* A, float* L, float* logabsdet, uint32_t* err_flag, int64_t batch, int32_t m, float eps,
                 int32_t checkargs, void* stream);
+
+/* ---- flows on images ------------------------------------------------------------------------ */
+/* Contiguous NCHW float32 tensors; x != y.
+ * fc_squeeze   planes = B C of the un-squeezed tensor, h / w its spatial size (both divisible by factor >= 2).
+ *              mode 0: x [planes, h, w] -> y [planes, f^2, h/f, w/f] in the order of
+ *              view(B, C, h/f, f, w/f, f).permute(0, 1, 3, 5, 2, 4) (SqueezeTransform.forward, reshape.py:28-48);
+ *              mode 1: the inverse (reshape.py:50-66).  Bit-exact; each mode is the other's backward.
+ * fc_conv1x1   per image b and pixel p: y[b, :, p] = weight (x[b, :, p] - pre) + post, weight [c, c] row-major,
+ *              pre / post [c] or NULL (zero); hw = H W.  The forward of OneByOneConvolution (conv.py) is the
+ *              permutation folded into the columns of weight and post = bias; its inverse is the permutation folded
+ *              into the rows of weight^-1 and pre = bias (the bias is subtracted BEFORE the product).
+ *              1 <= c <= FC_CONV1X1_MAX_CHANNELS (hipErrorInvalidValue otherwise). */
+#define FC_CONV1X1_MAX_CHANNELS 128
+int fc_squeeze(const float* x, float* y, int64_t planes, int32_t h, int32_t w, int32_t factor, int32_t mode,
+               void* stream);
+int fc_conv1x1(const float* x, const float* weight, const float* pre, const float* post, float* y, int64_t batch,
+               int32_t c, int64_t hw, void* stream);
 
 /* ---- batch-shared point-wise affine maps ---------------------------------------------------- */
 /* x, y viewed as [n, m] (m = elements of one batch item); scale/shift have 1 or m entries.
