@@ -128,6 +128,7 @@ SIGNATURES = {
                                  _I32, ctypes.c_float, _P],
     "fc_affine": [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "fc_dense_mm": [_P, _P, _P, _P, _I64, _I32, _P],
+    "fc_dense_mm_shifted": [_P, _P, _P, _P, _P, _I64, _I32, _P],
     "fc_sylvester_mm": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P],
     "fc_affine_backward": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P],
     "fc_pack_fragments": [_P, _I32, _P],

@@ -287,6 +287,8 @@ __global__ __launch_bounds__(256) void planar_rows4_kernel(const float* __restri
 // mode 0: y = W x + bias (Wt given)               -- linear.py:45-52 cached path, lu.py:56-68
 // mode 1: y = L (U x) + bias (Ut, Lt given)        -- lu.py:56-68 (two F.linear)
 // mode 2: y = U^-1 L^-1 (x - bias), L unit-lower   -- lu.py:70-91 (two solve_triangular)
+// mode 3: y = W (x - bias) (Wt given)              -- linear.py:62-76 cached inverse with W = W^-1: the shift comes off
+//                                                     first (W^-1 x - W^-1 b cancels when |b| dominates the result)
 template <int E>
 __global__ __launch_bounds__(256) void linear_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                      const float* __restrict__ at, const float* __restrict__ bt,
@@ -306,6 +308,10 @@ __global__ __launch_bounds__(256) void linear_kernel(const float* __restrict__ x
       matvec<E>(t, r, at, d, lane, 0);
 #pragma unroll
       for (int e = 0; e < E; ++e) r.v[e] = t.v[e] + bv.v[e];
+    } else if (mode == 3) {
+#pragma unroll
+      for (int e = 0; e < E; ++e) t.v[e] = r.v[e] - bv.v[e];
+      matvec<E>(r, t, at, d, lane, 0);
     } else if (mode == 1) {
       matvec<E>(t, r, at, d, lane, 1);   // U x
       matvec<E>(r, t, bt, d, lane, 0);   // L (U x)
@@ -670,9 +676,9 @@ extern "C" int fc_planar(const float* x, float* y, float* logabsdet, const float
 
 extern "C" int fc_linear(const float* x, float* y, const float* a_t, const float* b_t, const float* bias,
                          int64_t n, int32_t d, int32_t mode, void* stream) {
-  if (n < 0 || d <= 0 || d > 512 || mode < 0 || mode > 2) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > 512 || mode < 0 || mode > 3) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
-  if (!x || !y || !a_t || (mode != 0 && !b_t)) return hipErrorInvalidValue;
+  if (!x || !y || !a_t || ((mode == 1 || mode == 2) && !b_t)) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
   FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::linear_kernel<E>, dim3(fc::row_grid(n)), dim3(256), 0, s, x, y, a_t,
                                         b_t, bias, n, d, mode));

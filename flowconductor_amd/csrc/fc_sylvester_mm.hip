@@ -33,13 +33,14 @@ struct SylArgs {
   const float* bias;   // [F]
   const float* rdiag;  // [F] diag(R1) * diag(R2)
   int64_t blocks16;
+  const float* pre;    // [F] or NULL, kDense only: y = W1 (z - pre) + b
 };
 
 __host__ __device__ constexpr int syl_feat(int t, int g, int r) { return 32 * (t >> 1) + 8 * g + 4 * (t & 1) + r; }
 
 // F = 32 KS features: NT = 2 KS accumulator tiles per lane group, KS k-steps
-// kDense: only the first product, y = W1 z + b (a dense linear layer with batch-independent weights: LU / Linear
-// forward, a Householder sequence folded into its orthogonal matrix)
+// kDense: only the first product, y = W1 (z - pre) + b (a dense linear layer with batch-independent weights: LU / Linear
+// forward, a Householder sequence folded into its orthogonal matrix; with pre, the LU inverse W^-1 (x - b))
 // BPW: 16-row blocks a wave carries together (each weight fragment read from LDS serves all of them)
 template <int KS, bool kDense, int BPW>
 __global__ __launch_bounds__(kSylThreads) void sylvester_mm_kernel(SylArgs a) {
@@ -114,7 +115,8 @@ __global__ __launch_bounds__(kSylThreads) void sylvester_mm_kernel(SylArgs a) {
   for (int i = tid; i < 4 * NT * 4; i += kSylThreads) {   // accumulator order: [g][t * 4 + r]
     const int gg = i / (NT * 4), t = (i / 4) % NT, r = i & 3;
     bias[i] = a.bias ? a.bias[syl_feat(t, gg, r)] : 0.f;
-    rdg[i] = kDense ? 0.f : a.rdiag[syl_feat(t, gg, r)];
+    // (the dense form has no rdiag: its slot holds the shift subtracted before the product)
+    rdg[i] = kDense ? (a.pre ? a.pre[syl_feat(t, gg, r)] : 0.f) : a.rdiag[syl_feat(t, gg, r)];
   }
   __syncthreads();
 
@@ -217,14 +219,26 @@ __global__ __launch_bounds__(kSylThreads) void sylvester_mm_kernel(SylArgs a) {
 #pragma unroll
       for (int b = 0; b < BPW; ++b) load_rows(blk_of(grp, b), z[b]);
     }
+    const f32x4* bsrc = reinterpret_cast<const f32x4*>(bias + g * NT * 4);
+    const f32x4* rsrc = reinterpret_cast<const f32x4*>(rdg + g * NT * 4);
+    if constexpr (kDense) {
+      if (a.pre) {   // z - pre in f32 before the split, as the reference's x - b: W^-1 x - W^-1 b would cancel
+#pragma unroll
+        for (int b = 0; b < BPW; ++b)
+#pragma unroll
+          for (int t = 0; t < NT; ++t) {
+            const f32x4 p = rsrc[t];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) z[b][t][r] = z[b][t][r] - p[r];
+          }
+      }
+    }
     f16x8 bh[BPW][KS], bl[BPW][KS];
     f32x4 acc[BPW][NT];
     float un[BPW];
 #pragma unroll
     for (int b = 0; b < BPW; ++b) un[b] = make_operand(z[b], bh[b], bl[b]);
     product(0, bh, bl, acc);
-    const f32x4* bsrc = reinterpret_cast<const f32x4*>(bias + g * NT * 4);
-    const f32x4* rsrc = reinterpret_cast<const f32x4*>(rdg + g * NT * 4);
     if constexpr (kDense) {
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
@@ -317,7 +331,7 @@ extern "C" int fc_sylvester_mm(const float* x, float* y, float* logabsdet, const
   if (n == 0) return hipSuccess;
   if (!x || !y || !logabsdet || !w1 || !w2 || !bias || !r_diag_prod) return hipErrorInvalidValue;
   if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)w1 | (uintptr_t)w2) & 15u) != 0) return hipErrorInvalidValue;
-  fc::SylArgs a{x, y, logabsdet, w1, w2, bias, r_diag_prod, n / 16};
+  fc::SylArgs a{x, y, logabsdet, w1, w2, bias, r_diag_prod, n / 16, nullptr};
   const int cus = fc::device_cu_count();
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (d / 32) {
@@ -330,11 +344,16 @@ extern "C" int fc_sylvester_mm(const float* x, float* y, float* logabsdet, const
 
 extern "C" int fc_dense_mm(const float* x, float* y, const float* w, const float* bias, int64_t n, int32_t d,
                            void* stream) {
+  return fc_dense_mm_shifted(x, y, w, nullptr, bias, n, d, stream);
+}
+
+extern "C" int fc_dense_mm_shifted(const float* x, float* y, const float* w, const float* pre, const float* post,
+                                   int64_t n, int32_t d, void* stream) {
   if (n < 0 || d <= 0 || d % 32 != 0 || d > 128 || n % 16 != 0) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x || !y || !w) return hipErrorInvalidValue;
   if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)w) & 15u) != 0) return hipErrorInvalidValue;
-  fc::SylArgs a{x, y, nullptr, w, nullptr, bias, nullptr, n / 16};
+  fc::SylArgs a{x, y, nullptr, w, nullptr, post, nullptr, n / 16, pre};
   const int cus = fc::device_cu_count();
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (d / 32) {

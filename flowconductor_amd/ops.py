@@ -1762,11 +1762,11 @@ def linear_per_sample(inputs, matrices, mode=PER_SAMPLE_DENSE, offdiag_scale=1.0
     return (y, lad) if want_logabsdet else y
 
 
-LINEAR_DENSE, LINEAR_LU_FORWARD, LINEAR_LU_INVERSE = 0, 1, 2
+LINEAR_DENSE, LINEAR_LU_FORWARD, LINEAR_LU_INVERSE, LINEAR_DENSE_SHIFTED = 0, 1, 2, 3
 
 
 def linear(inputs, a, b=None, bias=None, mode=LINEAR_DENSE):
-    """Dense [D, D] maps on rows: ``A x + bias``; ``B (A x) + bias``; ``A^-1 B^-1 (x - bias)``
+    """Dense [D, D] maps on rows: ``A x + bias``; ``B (A x) + bias``; ``A^-1 B^-1 (x - bias)``; ``A (x - bias)``
     (reference linear.py:45-76, lu.py:56-91).  ``a``/``b`` are given untransposed."""
     lib = _hip.load()
     x = _rows(inputs)
@@ -1979,9 +1979,10 @@ def pack_sylvester(q_vectors, r1, r2):
     return w1, w2, rdiag
 
 
-def dense_mm(inputs, weight, bias=None):
-    """``inputs @ weight.T + bias`` for a batch-independent [D, D] ``weight`` on the matrix cores (rows a multiple
-    of 16, D % 32 == 0, D <= 128): f32-GEMM accuracy by split-f16 products."""
+def dense_mm(inputs, weight, bias=None, pre=None):
+    """``inputs @ weight.T + bias`` -- or ``(inputs - pre) @ weight.T + bias`` -- for a batch-independent [D, D]
+    ``weight`` on the matrix cores (rows a multiple of 16, D % 32 == 0, D <= 128): f32-GEMM accuracy by split-f16
+    products.  The shift is subtracted in f32 inside the kernel, before the product."""
     lib = _hip.load()
     x = _rows(inputs, align16=True)
     _hip.require_no_grad(inputs)
@@ -1993,8 +1994,15 @@ def dense_mm(inputs, weight, bias=None):
         raise ValueError("weight must be [%d, %d]" % (d, d))
     bv = _param(bias, x.device, "bias").reshape(-1) if bias is not None else None
     y = torch.empty_like(x)
-    _call("fc_dense_mm", lib.fc_dense_mm, x.device, _hip.ptr(x), _hip.ptr(y), _hip.ptr(w), _hip.ptr(bv), n, d,
-          _hip.stream_ptr(x.device))
+    if pre is None:
+        _call("fc_dense_mm", lib.fc_dense_mm, x.device, _hip.ptr(x), _hip.ptr(y), _hip.ptr(w), _hip.ptr(bv), n, d,
+              _hip.stream_ptr(x.device))
+        return y
+    pv = _param(pre, x.device, "pre").reshape(-1)
+    if pv.numel() != d or (bv is not None and bv.numel() != d):
+        raise ValueError("pre / bias must have %d entries" % d)
+    _call("fc_dense_mm_shifted", lib.fc_dense_mm_shifted, x.device, _hip.ptr(x), _hip.ptr(y), _hip.ptr(w),
+          _hip.ptr(pv), _hip.ptr(bv), n, d, _hip.stream_ptr(x.device))
     return y
 
 

@@ -7,10 +7,13 @@ and reused -- any ``train(True)`` drops them -- and the map itself is one ``fc_l
 
     forward:  y = W x + b,            logabsdet =  log|det W|   (the same value for every row)
     inverse:  y = W^-1 (x - b),       logabsdet = -log|det W|
+
+Above ``ops.MAX_ROW_FEATURES`` features the map is the reference's ``F.linear`` on the device.
 """
 import numpy as np
 import torch
 from torch import nn
+from torch.nn import functional as F
 
 from flowconductor_amd import ops
 from flowconductor_amd.transforms.base import Transform
@@ -73,16 +76,21 @@ class Linear(Transform):
         if not self._cache_active(inputs):
             return self.forward_no_cache(inputs)
         self._check_forward_cache()
-        outputs = ops.linear(inputs, self.cache.weight, bias=self.bias, mode=ops.LINEAR_DENSE)
+        if self.features > ops.MAX_ROW_FEATURES:    # wider than the row kernels: the reference's F.linear
+            outputs = F.linear(inputs, self.cache.weight, self.bias)
+        else:
+            outputs = ops.linear(inputs, self.cache.weight, bias=self.bias, mode=ops.LINEAR_DENSE)
         return outputs, self.cache.logabsdet.expand(outputs.shape[0]).clone()
 
     def inverse(self, inputs, context=None):
         if not self._cache_active(inputs):
             return self.inverse_no_cache(inputs)
         self._check_inverse_cache()
-        w_inv = self.cache.inverse
-        # W^-1 (x - b) = W^-1 x - W^-1 b: the [D] constant is formed on the host side of the launch
-        outputs = ops.linear(inputs, w_inv, bias=-(w_inv.detach() @ self.bias.detach()), mode=ops.LINEAR_DENSE)
+        # W^-1 (x - b) with the bias subtracted first, as the reference does: W^-1 x - W^-1 b cancels when |b| dominates
+        if self.features > ops.MAX_ROW_FEATURES:
+            outputs = F.linear(inputs - self.bias, self.cache.inverse)
+        else:
+            outputs = ops.linear(inputs, self.cache.inverse, bias=self.bias, mode=ops.LINEAR_DENSE_SHIFTED)
         return outputs, (-self.cache.logabsdet).expand(outputs.shape[0]).clone()
 
     # -- what a subclass provides -----------------------------------------------------------------------------------

@@ -63,8 +63,20 @@ class LULinear(Linear):
     def _needs_grad(self, inputs):
         return torch.is_grad_enabled() and (inputs.requires_grad or any(p.requires_grad for p in self.parameters()))
 
+    def _composition(self, inputs, inverse):
+        """The reference's own torch composition (lu.py:56-91) on the device, differentiable as it stands: the widths
+        above ``ops.MAX_ROW_FEATURES``, where no row kernel runs (as fc_spd hands over above its largest size)."""
+        lower, upper = self._create_lower_upper()
+        if not inverse:
+            return F.linear(F.linear(inputs, upper), lower, self.bias)
+        outputs = torch.linalg.solve_triangular(lower, (inputs - self.bias).t(), upper=False, unitriangular=True)
+        return torch.linalg.solve_triangular(upper, outputs, upper=True).t()
+
     def forward_no_cache(self, inputs):
         """``L (U x) + bias`` in one kernel; logabsdet = sum log diag(U) for every row."""
+        if self.features > ops.MAX_ROW_FEATURES:
+            outputs = self._composition(inputs, inverse=False)
+            return outputs, self._per_row(self.logabsdet(), outputs.shape[0])
         if self._needs_grad(inputs):    # training: the same kernel behind an autograd node, L / U built differentiably
             lower, upper = self._create_lower_upper()
             outputs = ops.lu_linear_autograd(inputs, lower, upper, self.bias)
@@ -82,6 +94,9 @@ class LULinear(Linear):
 
     def inverse_no_cache(self, inputs):
         """``U^-1 L^-1 (x - bias)`` by forward / back substitution in one kernel."""
+        if self.features > ops.MAX_ROW_FEATURES:
+            outputs = self._composition(inputs, inverse=True)
+            return outputs, self._per_row(-self.logabsdet(), outputs.shape[0])
         if self._needs_grad(inputs):
             lower, upper = self._create_lower_upper()
             outputs = ops.lu_linear_autograd(inputs, lower, upper, self.bias, inverse=True)
@@ -94,12 +109,13 @@ class LULinear(Linear):
             if wide:
                 # batch-independent parameters: W^-1 = U^-1 L^-1 formed once by two float64 triangular solves against the
                 # identity (what lu.py:70-91 does per batch, in float32), the batch goes through the matrix cores as in the
-                # forward direction:  W^-1 (x - b) = W^-1 x - W^-1 b.  (The per-row substitution kernel: two dependent sweeps
-                # over D per row, 4.3 ms per 2^20 x 64 against 0.11 ms.)
+                # forward direction, the bias subtracted in the kernel BEFORE the product as the reference does (the
+                # folded W^-1 x - W^-1 b cancels two large terms when |b| dominates the result).  (The per-row
+                # substitution kernel: two dependent sweeps over D per row, 4.3 ms per 2^20 x 64 against 0.11 ms.)
                 eye = torch.eye(self.features, dtype=torch.float64, device=lower.device)
                 l_inv = torch.linalg.solve_triangular(lower.double(), eye, upper=False, unitriangular=True)
                 w_inv = torch.linalg.solve_triangular(upper.double(), l_inv, upper=True)
-                outputs = ops.dense_mm(inputs, w_inv.float(), -(w_inv @ self.bias.double()).float())
+                outputs = ops.dense_mm(inputs, w_inv.float(), pre=self.bias)
             else:
                 outputs = ops.linear(inputs, upper, lower, self.bias, mode=ops.LINEAR_LU_INVERSE)
             return outputs, self._per_row(-self.logabsdet(), rows)

@@ -495,7 +495,9 @@ int fc_sylvester_mid_backward(const float* pre, float* grad_act_inout, const flo
 /* Dense linear maps with batch-shared [d, d] matrices given TRANSPOSED (a_t[j*d + i] = A[i][j]).
  * mode 0: y = A x + bias                        (linear.py:45-52 cached weight; bias may be NULL)
  * mode 1: y = B (A x) + bias, A = U, B = L      (lu.py:56-68, two F.linear)
- * mode 2: y = A^-1 B^-1 (x - bias), A = U upper, B = L unit-lower (lu.py:70-91, solve_triangular) */
+ * mode 2: y = A^-1 B^-1 (x - bias), A = U upper, B = L unit-lower (lu.py:70-91, solve_triangular)
+ * mode 3: y = A (x - bias)                      (linear.py:62-76 cached inverse, A = W^-1: the bias comes off first;
+ *                                                b_t unused, bias may be NULL) */
 int fc_linear(const float* x, float* y, const float* a_t, const float* b_t, const float* bias,
               int64_t n, int32_t d, int32_t mode, void* stream);
 
@@ -529,6 +531,12 @@ int fc_sylvester_mm(const float* x, float* y, float* logabsdet, const float* w1,
  * LULinear / Linear forward with W = L U (lu.py:56-68, linear.py:45-60), a HouseholderSequence folded into its
  * orthogonal matrix (orthogonal.py:63-85).  bias may be NULL.  d % 32 == 0, d <= 128, n % 16 == 0; x / y / w 16-byte aligned. */
 int fc_dense_mm(const float* x, float* y, const float* w, const float* bias, int64_t n, int32_t d, void* stream);
+
+/* y = W (x - pre) + post: fc_dense_mm with a shift subtracted from every row in f32 before the product (LULinear's
+ * inverse U^-1 L^-1 (x - bias) with W = W^-1 formed once, lu.py:70-91; W^-1 x - W^-1 bias would cancel when the bias
+ * dominates).  pre / post may be NULL; the same shape and alignment rules as fc_dense_mm. */
+int fc_dense_mm_shifted(const float* x, float* y, const float* w, const float* pre, const float* post, int64_t n,
+                        int32_t d, void* stream);
 
 /* ---- weight packing on the device ------------------------------------------------------------------------- */
 /* f32 nn.Linear tensors -> the scaled two-piece f16 matrix-core fragments the kernels above take (w_frag / wt_frag),

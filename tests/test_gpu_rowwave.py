@@ -214,14 +214,17 @@ def test_householder_and_lu_dense_matrix_core_path(d, k, n, device):
     h = T.HouseholderSequence(features=d, num_transforms=k).eval()
     with torch.no_grad():
         h.q_vectors.copy_(torch.randn(k, d))
-    lu = T.LULinear(d).eval()
+    lu = T.LULinear(d, identity_init=False).eval()
+    with torch.no_grad():
+        lu.bias.copy_(torch.randn(d) * 0.5)
     x = torch.randn(n, d)
-    for t, inverse in ((h, False), (h, True), (lu, False)):
+    for t, inverse in ((h, False), (h, True), (lu, False), (lu, True)):
         with torch.no_grad():
             ref_y, ref_lad = O.transform_apply(copy.deepcopy(t).double(), x.double(), inverse=inverse)
             f32_y, _ = O.transform_apply(t, x, inverse=inverse)
         td = copy.deepcopy(t).to(device)
-        with torch.no_grad(), ops.KernelTimer("fc_dense_mm") as timer:
+        entry = "fc_dense_mm_shifted" if t is lu and inverse else "fc_dense_mm"   # LU inverse: W^-1 (x - b)
+        with torch.no_grad(), ops.KernelTimer(entry) as timer:
             y, lad = (td.inverse if inverse else td)(x.to(device))
         assert len(timer.pairs) == 1, "the matrix-core kernel did not run"
         scale = max(1.0, float(ref_y.abs().max()))

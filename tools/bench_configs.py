@@ -628,7 +628,7 @@ def kernels(device):
         lu.bias.normal_(0, 0.1)
     add("lu_linear_forward", "fc_dense_mm", "fc::sylvester_mm_kernel<2> (fc_dense_mm: L U folded, split-f16 MFMA)", lambda: lu(x20), (8 * d + 4) * n20,
         module_parity(lu, x20), "8 D B per sample; 2 D^2 flop per sample run on the matrix cores")
-    add("lu_linear_inverse", "fc_dense_mm", "fc::sylvester_mm_kernel<2> (fc_dense_mm: U^-1 L^-1 folded in float64, split-f16 MFMA)", lambda: lu.inverse(x20),
+    add("lu_linear_inverse", "fc_dense_mm_shifted", "fc::sylvester_mm_kernel<2> (fc_dense_mm_shifted: U^-1 L^-1 folded in float64 applied to x - b, split-f16 MFMA)", lambda: lu.inverse(x20),
         (8 * d + 4) * n20, module_parity(lu, x20, inverse=True))
     # shared Householder sequence D = 128, K = 32 (folded into one orthogonal matrix on the matrix cores)
     x128 = torch.randn(n18, 128, device=device, generator=gen)
