@@ -146,6 +146,8 @@ SIGNATURES = {
     "fc_cholesky": [_P, _P, _P, _P, _I64, _I32, _F, _I32, _P],
     "fc_squeeze": [_P, _P, _I64, _I32, _I32, _I32, _I32, _P],
     "fc_conv1x1": [_P, _P, _P, _P, _P, _I64, _I32, _I64, _P],
+    "fc_iresnet_forward": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P],
+    "fc_iresnet_inverse": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _P],
 }
 
 _lib = None

@@ -88,3 +88,4 @@ from flowconductor_amd.transforms.matrix import (  # noqa: F401
 )
 from flowconductor_amd.transforms.conv import OneByOneConvolution  # noqa: F401
 from flowconductor_amd.transforms.reshape import SqueezeTransform  # noqa: F401
+from flowconductor_amd.transforms.lipschitz import iResBlock  # noqa: F401

@@ -43,7 +43,8 @@ extern "C" {
  * or a documented behaviour changes (2: round 4 -- fc_rq_fused_linear_backward is one launch, fc_comm_* entries of round 3,
  * FC_AFFINE_MAF_SOFTPLUS / FC_RQ_STREAMED_WEIGHTS; 3: the SPD-matrix entries fc_tril_pack, fc_matrix_diag,
  * fc_cholesky_outer(_backward), fc_cholesky and their FC_ERR_* bits).  The image-flow entries fc_squeeze / fc_conv1x1
- * were added under version 3: they change no existing entry, and a library without them fails to bind by name). */
+ * were added under version 3: they change no existing entry, and a library without them fails to bind by name; the same
+ * holds for the invertible-residual-block entries fc_iresnet_forward / fc_iresnet_inverse). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -396,6 +397,48 @@ int fc_squeeze(const float* x, float* y, int64_t planes, int32_t h, int32_t w, i
                void* stream);
 int fc_conv1x1(const float* x, const float* weight, const float* pre, const float* post, float* y, int64_t batch,
                int32_t c, int64_t hw, void* stream);
+
+/* ---- invertible residual blocks over Lipschitz DenseNets (eval mode) -------------------------- */
+/* iResBlock (transforms/lipschitz/iresblock.py:96-153) over a _DenseNet (nn/nets/invertible_densenet.py:68-95,
+ * lipschitz_dense.py:53-56) in eval mode: g(x) = final(h_depth), h_0 = [x | extra],
+ * h_{l+1} = cat(eta1_l h_l, eta2_l act(W_l h_l + b_l)), growth channels per layer.
+ *   image   float32 [image_floats], the net with the spectral normalisation applied (the eval-mode weights):
+ *           [p0, p1, 0, 0]; per dense layer [eta1, eta2, 0, 0] bias[op] wt[w_in][op] with op = out_ch rounded up to 4,
+ *           wt[k][o] = W[o][k], w_in = d + e + l growth, out_ch = growth (growth / 2 for the concatenating
+ *           activations); final layer bias[dp] wt[wtot][dp], dp = d rounded up to 4, wtot = d + e + depth growth.
+ *           Padding entries are zero.  p0 / p1: softplus(beta) of the Swish family, w0 of the sine family, alpha of
+ *           ELU; p1 = sigmoid(alpha) of LeakyLSwish.  image_floats must equal the length this layout gives.
+ *   extra   [n, e] or NULL (e == 0): per-row constant input channels appended to x (tangent zero) -- the context
+ *           embedding of InputConditionalDenseNet (invertible_densenet.py:211-216)
+ *   scale   [n] or NULL: per-row factor on g and its Jacobian -- tanh(factor_net) of the Multiplicative* nets (:263-269)
+ * fc_iresnet_forward  y [n, d] = x + scale g(x), logabsdet [n] = log|det(I + scale dg/dx)| (what the brute-force
+ *           estimator yields, iresblock.py:290-295): exact forward-mode Jacobian, LU with partial pivoting; a singular
+ *           matrix gives -inf.  x != y.
+ * fc_iresnet_inverse  x [n, d] with x + scale g(x) = y by x <- y - scale g(x) from x_0 = y - scale g(y)
+ *           (iresblock.py:111-134); a row stops when |x - x_prev| <= atol + rtol |y| for all its elements or after
+ *           max_iterations.  max_iters: device word or NULL; the launch max-reduces its largest iteration count into
+ *           it (zero it first).  x != y.
+ * 1 <= d <= FC_IRES_MAX_DIM, 1 <= depth <= FC_IRES_MAX_DEPTH, wtot <= FC_IRES_MAX_WIDTH (hipErrorInvalidValue
+ * otherwise). */
+#define FC_IRES_MAX_DIM 16
+#define FC_IRES_MAX_DEPTH 4
+#define FC_IRES_MAX_WIDTH 128
+#define FC_IRES_ACT_RELU 0
+#define FC_IRES_ACT_TANH 1
+#define FC_IRES_ACT_ELU 2
+#define FC_IRES_ACT_SWISH 3        /* t sigmoid(p0 t) / 1.1 (activations.py:84-91) */
+#define FC_IRES_ACT_LIPSWISH 4     /* swish / 1.004 (:143-150) */
+#define FC_IRES_ACT_CLIPSWISH 5    /* lipswish(cat(t, -t)) (:131-140) */
+#define FC_IRES_ACT_SIN 6          /* sin(p0 t) / p0 (:94-100) */
+#define FC_IRES_ACT_CSIN 7         /* sin(p0 cat(t, -t)) / (p0 sqrt 2) (:105-113) */
+#define FC_IRES_ACT_LEAKY_LSWISH 8 /* p1 t + (1 - p1) swish(t) (:119-128) */
+int fc_iresnet_forward(const float* x, const float* extra, const float* scale, const float* image, float* y,
+                       float* logabsdet, int64_t n, int32_t d, int32_t e, int32_t depth, int32_t growth,
+                       int32_t activation, int32_t image_floats, void* stream);
+int fc_iresnet_inverse(const float* y, const float* extra, const float* scale, const float* image, float* x,
+                       uint32_t* max_iters, int64_t n, int32_t d, int32_t e, int32_t depth, int32_t growth,
+                       int32_t activation, int32_t image_floats, int32_t max_iterations, float atol, float rtol,
+                       void* stream);
 
 /* ---- batch-shared point-wise affine maps ---------------------------------------------------- */
 /* x, y viewed as [n, m] (m = elements of one batch item); scale/shift have 1 or m entries.
