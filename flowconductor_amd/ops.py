@@ -212,7 +212,8 @@ RUNTIME_CACHE_ATTRS = frozenset((
     "_hip_packed", "_hip_packed_wide", "_hip_packed_bwd", "_hip_image", "_final_padded", "_tail_image", "_train_pack",
     "_packed", "_masked_final", "_mm_cache", "_dense_cache", "_sp_cache", "_all_cols", "_ctx_cols", "_cols_cache",
     "_id_cols_cache", "_fc_param_list", "_fc_module_list", "_fc_static_ok", "_conv1x1_cache", "_ires_image",
-    "_ires_iters"))
+    "_ires_iters", "_fc_made_inverse_pack", "_fc_made_inverse_context_pack", "_fc_device_loop_ok",
+    "_fc_device_loop_context_ok"))
 
 
 class RuntimeCaches:
@@ -926,16 +927,67 @@ def pack_made_inverse(made, features, per_dim):
             final_frag, un.float().contiguous(), final_bias, need.to(dev).contiguous())
 
 
-def made_inverse(inputs, packed, num_blocks, per_dim, kind, rq=None, logabsdet_accum=None):
+def pack_made_inverse_context(made, features, per_dim):
+    """The context layers of a conditional residual-block MADE (``made.context_layer`` and every block's, made.py:153-162,
+    108-118) as ``fc_made_inverse_context`` reads them: per layer the [hidden, C <= 32] weight with its rows in the unit
+    order of ``pack_made_inverse`` (``_made_pass_prefix``'s ``order``: rank r is row r of the image, the row the
+    accumulator layout ``_hb_perm`` keeps in slot r), zero-padded to [64, 32], one power-of-two scale per layer, two f16
+    pieces in fragment order [t][piece][lane][8]; the biases in the accumulator order of ``hidden_bias``.  Returns
+    ``(context_frag, context_unscale [1 + blocks], context_bias [1 + blocks, 64])``."""
+    hw = 64
+    layers = [made.context_layer] + [block.context_layer for block in made.blocks]
+    dev = layers[0].weight.device
+    wf, uns, biases = [], [], []
+    with torch.no_grad():
+        order, _ = _made_pass_prefix(made, features, per_dim, hw)
+        order = order.to(dev)
+        for lin in layers:
+            if lin.in_features > 32 or lin.out_features > hw:
+                raise ValueError("fc_made_inverse_context: at most 32 context features and 64 hidden units")
+            w = _pad_to(lin.weight.detach().float(), (hw, 32))[order]              # row r = the unit of rank r
+            sc, un = _pow2_scale(w.abs().amax().reshape(1))
+            uns.append(un)
+            wf.append(_a_fragments(w * sc).permute(1, 0, 2, 3, 4).reshape(-1))     # [ks = 1][t][piece][lane][8]
+            b = _pad_to(lin.bias.detach().float(), (hw,))[order]
+            biases.append(b.reshape(4, 4, 4).permute(1, 0, 2).reshape(-1))
+    return torch.cat(wf).contiguous(), torch.cat(uns).float().contiguous(), torch.stack(biases).contiguous()
+
+
+def made_inverse_context_fits(features, num_blocks, per_dim):
+    """LDS budget of ``fc_made_inverse_context`` (fc_made_inverse.h ``mi_lds_bytes`` + ``mi_ctx_lds_bytes``, one 16-row
+    block per wave): the hidden stack's image, the context layers' images and the waves' parameter strips in 160 KB."""
+    k0s = 1 if features <= 32 else 2
+    pt = -(-per_dim // 16)
+    image = (k0s * 8 + 2 * num_blocks * 16) * 1024 + (1 + 2 * num_blocks) * 256 + 64 + 8 * 16 * (16 * pt + 4) * 4
+    context = (1 + num_blocks) * (8 * 1024 + 256) + 64
+    return num_blocks <= 3 and features <= 64 and per_dim <= 48 and image + context <= 160 * 1024
+
+
+def made_inverse(inputs, packed, num_blocks, per_dim, kind, rq=None, logabsdet_accum=None, context=None,
+                 context_pack=None):
     """The D passes of an autoregressive inverse in ONE kernel (``fc_made_inverse``): ``inputs`` [N, D <= 64] (rows a
     multiple of 16), ``packed`` from ``pack_made_inverse``; ``kind`` ``MADE_AFFINE`` or ``MADE_RQ`` (``rq``: keyword
-    arguments of the spline as for ``rq_spline``).  Returns ``(outputs, logabsdet)``."""
+    arguments of the spline as for ``rq_spline``).  With ``context`` [N, C <= 32] and ``context_pack`` from
+    ``pack_made_inverse_context`` the conditional form (``fc_made_inverse_context``).  Returns ``(outputs, logabsdet)``."""
     lib = _hip.load()
     z = _prep_2d(inputs)
     _hip.require_no_grad(inputs)
     n, d = z.shape
     if n % HIDDEN_ROWS != 0 or d > 64:
         raise ValueError("fc_made_inverse: rows must be a multiple of %d, D <= 64" % HIDDEN_ROWS)
+    if (context is None) != (context_pack is None):
+        raise ValueError("made_inverse: context and context_pack go together")
+    if context is not None:
+        _hip.require_no_grad(context)
+        if (not torch.is_tensor(context) or context.dtype != torch.float32 or context.dim() != 2 or context.shape[0] != n
+                or not 1 <= context.shape[1] <= 32 or not context.is_contiguous() or context.device != z.device):
+            raise ValueError("made_inverse: context must be a contiguous float32 [N, C <= 32] tensor on the inputs' device")
+        if not made_inverse_context_fits(d, num_blocks, per_dim):
+            raise ValueError("fc_made_inverse_context has no instantiation for D = %d, %d blocks, %d parameters per dim"
+                             % (d, num_blocks, per_dim))
+        cf, cu, cb = context_pack
+        if cf.numel() != (1 + num_blocks) * 4096 or cu.numel() != 1 + num_blocks or cb.numel() != (1 + num_blocks) * 64:
+            raise ValueError("made_inverse: context_pack does not match num_blocks = %d" % num_blocks)
     cfg = None
     if kind == MADE_RQ:
         rq = dict(rq)
@@ -960,6 +1012,13 @@ def made_inverse(inputs, packed, num_blocks, per_dim, kind, rq=None, logabsdet_a
     hf, hu, hb, ff, fu, fb, need = packed
     if need.dtype != torch.int32 or need.numel() != d:
         raise ValueError("made_inverse: units_needed must hold one int32 per dim")
+    if context is not None:
+        _call("fc_made_inverse_context", lib.fc_made_inverse_context, z.device, _hip.ptr(z), _hip.ptr(context), _hip.ptr(y),
+              _hip.ptr(lad), _hip.ptr(hf), _hip.ptr(hu), _hip.ptr(hb), _hip.ptr(cf), _hip.ptr(cu), _hip.ptr(cb), _hip.ptr(ff),
+              _hip.ptr(fu), _hip.ptr(fb), _hip.ptr(need), _hip.ptr(err), n, d, context.shape[1], num_blocks, per_dim, kind, cfg,
+              _hip.stream_ptr(z.device))
+        _finish(True)
+        return y, lad
     _call("fc_made_inverse", lib.fc_made_inverse, z.device, _hip.ptr(z), _hip.ptr(y), _hip.ptr(lad), _hip.ptr(hf),
           _hip.ptr(hu), _hip.ptr(hb), _hip.ptr(ff), _hip.ptr(fu), _hip.ptr(fb), _hip.ptr(need), _hip.ptr(err), n, d, num_blocks, per_dim,
           kind, cfg, _hip.stream_ptr(z.device))

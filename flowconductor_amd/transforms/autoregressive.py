@@ -79,7 +79,7 @@ class AutoregressiveTransform(Transform):
 
     def inverse(self, inputs, context=None):
         if self._device_loop_ok(inputs, context):
-            return self._inverse_device_loop(inputs)
+            return self._inverse_device_loop(inputs, context)
         if self._incremental_ok(inputs):
             return self._inverse_incremental(inputs, context)
         num_inputs = int(np.prod(inputs.shape[1:]))
@@ -107,8 +107,11 @@ class AutoregressiveTransform(Transform):
 
     def _device_loop_ok(self, inputs, context):
         """One kernel for the whole inverse (``fc_made_inverse``): a residual-block MADE with hidden <= 64, <= 3 ReLU
-        blocks, no context / batch norm / active dropout / hooks, D <= 64, float32 rows on the device, inference only."""
+        blocks, no batch norm / active dropout / hooks, D <= 64, float32 rows on the device, inference only.  A net with
+        context layers called with a context takes ``fc_made_inverse_context`` where that kernel has the shape."""
         net = self.autoregressive_net
+        if context is not None:
+            return self._device_loop_context_ok(inputs, context)
         if not (context is None and inputs.dim() == 2 and inputs.is_cuda and inputs.dtype == torch.float32
                 and 1 < inputs.shape[1] <= 64 and inputs.shape[0] >= 1 and options.get("ar_device_loop")
                 and options.get("fused_hidden") and not self._needs_grad(inputs)):
@@ -125,7 +128,33 @@ class AutoregressiveTransform(Transform):
         return (ops.static_memo(self, "_fc_device_loop_ok", (inputs.shape[1],) + ops.structure_key(net), structure_ok)
                 and not ops.has_hooks(net))
 
-    def _inverse_device_loop(self, inputs):
+    def _device_loop_context_ok(self, inputs, context):
+        """The conditional form (``fc_made_inverse_context``): everything ``_device_loop_ok`` asks without a context, a
+        ``context_layer`` beside the initial layer and in every block, a [N, C <= 32] float32 device context without
+        gradients whose rows match the inputs, and a shape the kernel is instantiated for (its LDS budget)."""
+        net = self.autoregressive_net
+        if not (torch.is_tensor(context) and inputs.dim() == 2 and inputs.is_cuda and inputs.dtype == torch.float32
+                and 1 < inputs.shape[1] <= 64 and inputs.shape[0] >= 1 and options.get("ar_device_loop")
+                and options.get("fused_hidden") and not self._needs_grad(inputs)
+                and context.dim() == 2 and context.shape[0] == inputs.shape[0] and 1 <= context.shape[1] <= 32
+                and context.dtype == torch.float32 and context.device == inputs.device
+                and not (context.requires_grad and torch.is_grad_enabled())):
+            return False
+
+        def structure_ok():
+            form = self._device_loop_form()
+            code = ops.activation_code(net.activation) if isinstance(net, made_module.MADE) else None
+            return (form is not None and isinstance(net, made_module.MADE) and inputs.shape[1] == net.initial_layer.in_features
+                    and hasattr(net, "context_layer") and all(hasattr(b, "context_layer") for b in net.blocks)
+                    and len(net.blocks) <= 3 and net.hip_hidden_supported(context)
+                    and code is not None and code[0] == ops.ACT_RELU and form[1] <= 48
+                    and net.final_layer.out_features == form[1] * inputs.shape[1]
+                    and ops.made_inverse_context_fits(inputs.shape[1], len(net.blocks), form[1]))
+
+        key = (inputs.shape[1], context.shape[1]) + ops.structure_key(net)
+        return ops.static_memo(self, "_fc_device_loop_context_ok", key, structure_ok) and not ops.has_hooks(net)
+
+    def _inverse_device_loop(self, inputs, context=None):
         net = self.autoregressive_net
         kind, per_dim, rq = self._device_loop_form()
         features = inputs.shape[1]
@@ -135,9 +164,23 @@ class AutoregressiveTransform(Transform):
         if cache is None or cache[0] != key:
             cache = self.__dict__["_fc_made_inverse_pack"] = (key, ops.pack_made_inverse(net, features, per_dim))
         n = inputs.shape[0]
-        rows = inputs if n % ops.HIDDEN_ROWS == 0 else torch.nn.functional.pad(inputs, (0, 0, 0, -n % ops.HIDDEN_ROWS))
-        outputs, logabsdet = ops.made_inverse(rows, cache[1], len(net.blocks), per_dim, kind, rq)
-        return (outputs, logabsdet) if rows is inputs else (outputs[:n], logabsdet[:n])
+        pad = -n % ops.HIDDEN_ROWS
+        rows = inputs if pad == 0 else torch.nn.functional.pad(inputs, (0, 0, 0, pad))
+        if context is None:
+            outputs, logabsdet = ops.made_inverse(rows, cache[1], len(net.blocks), per_dim, kind, rq)
+        else:
+            ctx_layers = [net.context_layer] + [block.context_layer for block in net.blocks]
+            ctx_key = ops.cache_key(*[t for lin in ctx_layers for t in (lin.weight, lin.bias)])
+            ctx_cache = self.__dict__.get("_fc_made_inverse_context_pack")
+            if ctx_cache is None or ctx_cache[0] != ctx_key:
+                ctx_cache = self.__dict__["_fc_made_inverse_context_pack"] = (
+                    ctx_key, ops.pack_made_inverse_context(net, features, per_dim))
+            ctx_rows = context.detach().contiguous()
+            if pad:
+                ctx_rows = torch.nn.functional.pad(ctx_rows, (0, 0, 0, pad))
+            outputs, logabsdet = ops.made_inverse(rows, cache[1], len(net.blocks), per_dim, kind, rq, context=ctx_rows,
+                                                  context_pack=ctx_cache[1])
+        return (outputs, logabsdet) if pad == 0 else (outputs[:n], logabsdet[:n])
 
     def _incremental_ok(self, inputs):
         """Column-at-a-time inverse applies to a MADE: its input degrees are 1..D and its output

@@ -44,7 +44,8 @@ extern "C" {
  * FC_AFFINE_MAF_SOFTPLUS / FC_RQ_STREAMED_WEIGHTS; 3: the SPD-matrix entries fc_tril_pack, fc_matrix_diag,
  * fc_cholesky_outer(_backward), fc_cholesky and their FC_ERR_* bits).  The image-flow entries fc_squeeze / fc_conv1x1
  * were added under version 3: they change no existing entry, and a library without them fails to bind by name; the same
- * holds for the invertible-residual-block entries fc_iresnet_forward / fc_iresnet_inverse). */
+ * holds for the invertible-residual-block entries fc_iresnet_forward / fc_iresnet_inverse and for the conditional
+ * device loop fc_made_inverse_context). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -160,6 +161,28 @@ int fc_made_inverse(const float* z, float* y, float* logabsdet, const void* hidd
                     const float* hidden_bias, const void* final_frag, const float* final_unscale, const float* final_bias,
                     const int32_t* units_needed, uint32_t* err_flag, int64_t n, int32_t d, int32_t num_blocks, int32_t params_per_dim, int32_t kind,
                     const fc_rq_config* cfg, void* stream);
+
+/* fc_made_inverse for a CONDITIONAL MADE: the same D passes with the additive context terms of made.py:153-162 (initial
+ * layer: h = W0 x + b0 + relu(Wc[0] c + bc[0])) and made.py:108-118 (block i: Wc[1 + i] c + bc[1 + i] joins the first masked
+ * Linear's output before the second activation) -- the FC_CONTEXT_ADDITIVE form of fc_resnet_hidden_context.  The terms do
+ * not change from pass to pass: the 16 context rows of a block become one matrix-core operand (two f16 pieces, their OWN
+ * power-of-two row scale) before pass 0, and every pass redoes only the products for the unit tiles it computes.
+ * Everything fc_made_inverse takes means the same here (same element-wise inverses, units_needed prefix scheme,
+ * FC_RQ_ACCUMULATE_LOGABSDET, err_flag bits, n % 16 == 0); dim 0 reads no hidden unit, so its column does not depend on
+ * the context.  In addition:
+ *   context [n, context_features] row-major f32, 1 <= context_features <= 32.
+ *   context_frag: f16 [1 + num_blocks][4 tiles][2 pieces][64 lanes][8]: lane l of fragment (layer, t, piece) holds
+ *   2^S_layer Wc[layer][unit of row 16 t + (l & 15)][8 (l >> 4) + j] (zero beyond context_features / hidden), the rows in
+ *   the unit order of hidden_frag (the caller's units_needed renumbering applies to them as to every hidden layer);
+ *   context_unscale [1 + num_blocks] = 2^-S_layer; context_bias [1 + num_blocks][64] in the order of hidden_bias.
+ * Shapes whose LDS image (hidden stack + context layers + parameter strips) exceeds 160 KB have no instantiation and
+ * return hipErrorInvalidValue: num_blocks == 3 with params_per_dim > 32, or with d > 32 and params_per_dim > 16. */
+int fc_made_inverse_context(const float* z, const float* context, float* y, float* logabsdet, const void* hidden_frag,
+                            const float* hidden_unscale, const float* hidden_bias, const void* context_frag,
+                            const float* context_unscale, const float* context_bias, const void* final_frag,
+                            const float* final_unscale, const float* final_bias, const int32_t* units_needed,
+                            uint32_t* err_flag, int64_t n, int32_t d, int32_t context_features, int32_t num_blocks,
+                            int32_t params_per_dim, int32_t kind, const fc_rq_config* cfg, void* stream);
 
 /* Backward of fc_affine in the forward direction, per-sample parameters (coupling.py:234-252,
  * autoregressive.py:97-129 under torch.autograd): grad_x[n, cols[j]] = gy s; grad_params in the layout of
