@@ -219,12 +219,8 @@ class ResidualNet(ops.RuntimeCaches, nn.Module):
         """[where, DevicePack, packed] of the training-time images (not refreshed here)."""
         from flowconductor_amd import ops
 
-        where = self._storage_key()
-        plan = getattr(self, "_hip_packed_bwd", None)
-        if plan is None or plan[0] != where:
-            pack, packed = ops.device_pack_resnet_hidden_backward(self)
-            plan = self._hip_packed_bwd = [where, pack, packed]
-        return plan
+        return ops.device_plan(self, "_hip_packed_bwd", self._storage_key(),
+                               lambda: ops.device_pack_resnet_hidden_backward(self))
 
     def hidden_padded(self, inputs, context=None):
         """``hidden`` on PyTorch, zero-padded to the kernel's 64 columns (leftover rows next to ``hidden_hip``)."""
@@ -258,11 +254,8 @@ class ResidualNet(ops.RuntimeCaches, nn.Module):
             if self.training and self.hip_hidden_backward_supported():
                 w_frag, _, w_un, bias_acc, _ = self.hidden_backward_packed()
                 return ops.resnet_hidden_packed(rows, id_cols, (w_frag, w_un, bias_acc), in_features, len(self.blocks), act)
-            where = self._storage_key()
-            plan = getattr(self, "_hip_image", None)
-            if plan is None or plan[0] != where:
-                pack, packed = ops.device_pack_resnet_hidden_forward(self)
-                plan = self._hip_image = [where, pack, packed]
+            plan = ops.device_plan(self, "_hip_image", self._storage_key(),
+                                   lambda: ops.device_pack_resnet_hidden_forward(self))
             plan[1].refresh()
             return ops.resnet_hidden_packed(rows, id_cols, plan[2], in_features, len(self.blocks), act)
         key = ops.cache_key(*self._param_list())

@@ -328,6 +328,23 @@ DEFAULT_MIN_BIN_HEIGHT = 1e-3
 DEFAULT_MIN_DERIVATIVE = 1e-3
 
 
+def rq_param_count(num_bins, tails):
+    """Parameters per transformed dim of an RQ spline: K widths, K heights and the K - 1 inner derivatives with linear
+    tails (3K - 1), all K + 1 derivatives otherwise (3K + 1)."""
+    return 3 * num_bins - 1 if tails == "linear" else 3 * num_bins + 1
+
+
+def _logabsdet_target(logabsdet_accum, n, device):
+    """``(lad, flags)`` of a kernel that stores its logabsdet [N] or adds it onto a running total: a fresh tensor and 0, or
+    the checked ``logabsdet_accum`` and 1 (``FC_RQ_ACCUMULATE_LOGABSDET`` / ``LAD_ACCUMULATE``)."""
+    if logabsdet_accum is None:
+        return torch.empty(n, dtype=torch.float32, device=device), 0
+    lad = logabsdet_accum
+    if lad.dtype != torch.float32 or lad.shape != (n,) or not lad.is_contiguous() or lad.device != device:
+        raise ValueError("logabsdet_accum must be a contiguous float32 [N] tensor on the inputs' device")
+    return lad, 1
+
+
 def _rq_config(num_bins, tails, tail_bound, box, min_bin_width, min_bin_height, min_derivative,
                enable_identity_init, wh_divisor, inverse):
     cfg = _hip.RQConfig()
@@ -365,12 +382,9 @@ def rq_spline(inputs, params, cols=None, *, num_bins, tails=None, tail_bound=1.0
     n, d = x.shape
     cols = _as_cols(cols, x.device)
     d_t = d if cols is None else cols.numel()
-    if tails is None:
-        mult = 3 * num_bins + 1
-    elif tails == "linear":
-        mult = 3 * num_bins - 1
-    else:
+    if tails not in (None, "linear"):
         raise RuntimeError("{} tails are not implemented.".format(tails))
+    mult = rq_param_count(num_bins, tails)
     if min_bin_width * num_bins > 1.0:
         raise ValueError("Minimal bin width too large for the number of bins")
     if min_bin_height * num_bins > 1.0:
@@ -579,12 +593,42 @@ def _a_fragments(w):
     return torch.stack((frag(hi), frag(lo)), dim=2).contiguous()
 
 
+FRAG_ELEMS = 2 * 64 * 8                 # f16 values of one A fragment: (hi, lo) pieces x 64 lanes x 8
+FRAG_KSTEP = 4 * FRAG_ELEMS             # one 32-column k-step of a 64-row layer: four 16-row tiles
+
+
+def _hb_perm():
+    """Feature held by accumulator tile t, row rho of the hidden-layer kernels: 32 (t >> 1) + 8 g + 4 (t & 1) + r with
+    g = rho >> 2, r = rho & 3 (the order in which the C layout of one layer is the B operand of the next)."""
+    return torch.tensor([32 * (t >> 1) + 8 * (rho >> 2) + 4 * (t & 1) + (rho & 3) for t in range(4) for rho in range(16)])
+
+
+def _hidden_layer_fragments(w_scaled, perm=None):
+    """A scaled [rows, 32 ks] layer -> flat f16 fragments [ks][t][piece][lane][8]; row r of the image is row ``perm[r]``
+    of ``w_scaled`` (``_hb_perm``: the accumulator order; None: the rows as they are)."""
+    if perm is not None:
+        w_scaled = w_scaled[perm]
+    return _a_fragments(w_scaled).permute(1, 0, 2, 3, 4).reshape(-1)
+
+
+def _bias_accumulator_order(b, perm=None):
+    """A [64] bias as the hidden-layer kernels add it to their accumulators (``perm`` as in ``_hidden_layer_fragments``)."""
+    if perm is not None:
+        b = b[perm]
+    return b.reshape(4, 4, 4).permute(1, 0, 2).reshape(-1)
+
+
+def _hidden_linears(net):
+    """The Linear layers of a ResidualNet's / MADE's hidden stack in the order the kernels walk them."""
+    return [net.initial_layer] + [lin for block in net.blocks for lin in block.linear_layers]
+
+
 def pack_resnet_hidden_wide(net, width):
     """Hidden layers of a ResidualNet with 64 < hidden_features <= 256 (no context) as ``fc_resnet_hidden_wide``
     streams them: every layer's weight zero-padded to ``width`` (128 / 256) rows and 32-multiples of columns, scaled
     by a power of two per layer, split into two f16 pieces, in fragment order; all layers in one flat f16 buffer.
     Returns (w_frag, w_unscale [1 + 2 blocks], bias [1 + 2 blocks, width])."""
-    layers = [net.initial_layer] + [lin for block in net.blocks for lin in block.linear_layers]
+    layers = _hidden_linears(net)
     frags, uns, biases = [], [], []
     for i, lin in enumerate(layers):
         kin = (32 if lin.in_features <= 32 else 64) if i == 0 else width
@@ -704,8 +748,7 @@ def device_pack_final_layer(weight, bias, num_bins, tails, cols_chunks):
     """Forward and W^T fragments of the final Linear (hidden <= 64) for every group of <= 32 transformed dims, packed on
     the device.  ``cols_chunks``: [(row slice of the weight, cols tensor)].  Returns ``(pack, chunks)`` with chunks =
     [(w_frag, w_unscale, bias_pad, wt_frag, cols, row slice)]; call ``pack.run()`` whenever the weights changed."""
-    k = num_bins
-    p = 3 * k - 1 if tails == "linear" else 3 * k + 1
+    p = rq_param_count(num_bins, tails)
     pp = -(-p // 4) * 4
     t = pp // 4
     kk = -(-pp // 8)
@@ -728,29 +771,45 @@ def device_pack_final_layer(weight, bias, num_bins, tails, cols_chunks):
     return pack, chunks
 
 
+def _hidden_image(n_layers, k0s, device):
+    """Empty LDS weight image of a 64-wide hidden stack, ``(w_frag, w_unscale [L], bias_acc [L, 64])``: ``k0s`` k-steps
+    for the initial layer, two for every later one."""
+    w_frag = torch.empty((k0s + 2 * (n_layers - 1)) * FRAG_KSTEP, dtype=torch.float16, device=device)
+    w_un = torch.empty(n_layers, dtype=torch.float32, device=device)
+    bias_acc = torch.empty(n_layers, 64, dtype=torch.float32, device=device)
+    return w_frag, w_un, bias_acc
+
+
+def _hidden_image_fragments(frag, k0s, i):
+    """Layer ``i``'s slice of a fragment buffer laid out as ``_hidden_image`` lays out ``w_frag``."""
+    lo = 0 if i == 0 else k0s + 2 * (i - 1)
+    return frag[lo * FRAG_KSTEP:(lo + (k0s if i == 0 else 2)) * FRAG_KSTEP]
+
+
+def _add_hidden_jobs(pack, image, k0s, sources):
+    """One ``PACK_HIDDEN`` job per ``(weight, bias, track)`` of ``sources`` (layer order) into ``image``."""
+    w_frag, w_un, bias_acc = image
+    for i, (weight, bias, track) in enumerate(sources):
+        pack.add(PACK_HIDDEN, weight, bias, _hidden_image_fragments(w_frag, k0s, i), w_un[i:i + 1], bias_acc[i],
+                 nks=k0s if i == 0 else 2, nt=4, track=track)
+
+
 def device_pack_resnet_hidden_backward(net):
     """``pack_resnet_hidden_backward`` on the device: returns ``(pack, packed)``; ``pack.run()`` refreshes ``packed``."""
     dev = net.initial_layer.weight.device
-    k0 = net.initial_layer.in_features
-    k0s = 1 if k0 <= 32 else 2
-    layers = [net.initial_layer] + [lin for block in net.blocks for lin in block.linear_layers]
-    n_layers = len(layers)
-    frag0, frag_l = k0s * 4 * 2 * 64 * 8, 2 * 4 * 2 * 64 * 8
-    w_frag = torch.empty(frag0 + (n_layers - 1) * frag_l, dtype=torch.float16, device=dev)
-    wt_frag = torch.empty((n_layers - 1) * frag_l + 2 * (2 * k0s) * 2 * 64 * 8, dtype=torch.float16, device=dev)
-    w_un = torch.empty(n_layers, dtype=torch.float32, device=dev)
-    wt_un = torch.empty(n_layers, dtype=torch.float32, device=dev)
-    bias_acc = torch.empty(n_layers, 64, dtype=torch.float32, device=dev)
+    k0s = 1 if net.initial_layer.in_features <= 32 else 2
+    layers = _hidden_linears(net)
+    image = w_frag, w_un, bias_acc = _hidden_image(len(layers), k0s, dev)
+    wt_frag = torch.empty_like(w_frag)          # the same matrices transposed: layers 1.. first, W0^T last
+    wt_un = torch.empty_like(w_un)
     pack = DevicePack(dev)
-    off = 0
-    for i, lin in enumerate(layers):
-        size = frag0 if i == 0 else frag_l
-        pack.add(PACK_HIDDEN, lin.weight, lin.bias, w_frag[off:off + size], w_un[i:i + 1], bias_acc[i],
-                 nks=k0s if i == 0 else 2, nt=4)
-        off += size
+    _add_hidden_jobs(pack, image, k0s, [(lin.weight, lin.bias, True) for lin in layers])
+    per_layer = 2 * FRAG_KSTEP
     for i, lin in enumerate(layers[1:]):
-        pack.add(PACK_HIDDEN_T, lin.weight, None, wt_frag[i * frag_l:(i + 1) * frag_l], wt_un[i + 1:i + 2], None, nks=2, nt=4)
-    pack.add(PACK_HIDDEN_T0, layers[0].weight, None, wt_frag[(n_layers - 1) * frag_l:], wt_un[0:1], None, nks=2, nt=2 * k0s)
+        pack.add(PACK_HIDDEN_T, lin.weight, None, wt_frag[i * per_layer:(i + 1) * per_layer], wt_un[i + 1:i + 2], None,
+                 nks=2, nt=4)
+    pack.add(PACK_HIDDEN_T0, layers[0].weight, None, wt_frag[(len(layers) - 1) * per_layer:], wt_un[0:1], None, nks=2,
+             nt=2 * k0s)
     return pack, (w_frag, wt_frag, w_un, bias_acc, k0s)
 
 
@@ -759,19 +818,11 @@ def device_pack_resnet_hidden_forward(net):
     made on the device: returns ``(pack, (w_frag, w_unscale [L], bias_acc [L, 64]))``; ``pack.run()`` refreshes it."""
     dev = net.initial_layer.weight.device
     k0s = 1 if net.initial_layer.in_features <= 32 else 2
-    layers = [net.initial_layer] + [lin for block in net.blocks for lin in block.linear_layers]
-    frag0, frag_l = k0s * 4 * 2 * 64 * 8, 2 * 4 * 2 * 64 * 8
-    w_frag = torch.empty(frag0 + (len(layers) - 1) * frag_l, dtype=torch.float16, device=dev)
-    w_un = torch.empty(len(layers), dtype=torch.float32, device=dev)
-    bias_acc = torch.empty(len(layers), 64, dtype=torch.float32, device=dev)
+    layers = _hidden_linears(net)
+    image = _hidden_image(len(layers), k0s, dev)
     pack = DevicePack(dev)
-    off = 0
-    for i, lin in enumerate(layers):
-        size = frag0 if i == 0 else frag_l
-        pack.add(PACK_HIDDEN, lin.weight, lin.bias, w_frag[off:off + size], w_un[i:i + 1], bias_acc[i],
-                 nks=k0s if i == 0 else 2, nt=4)
-        off += size
-    return pack, (w_frag, w_un, bias_acc)
+    _add_hidden_jobs(pack, image, k0s, [(lin.weight, lin.bias, True) for lin in layers])
+    return pack, image
 
 
 def device_pack_affine_coupling(net, d_t, additive):
@@ -780,12 +831,8 @@ def device_pack_affine_coupling(net, d_t, additive):
     copy of the final layer lives in a staging buffer refreshed before every pack launch.  Returns ``(pack, packed)``."""
     dev = net.initial_layer.weight.device
     k0s = 1 if net.initial_layer.in_features <= 32 else 2
-    hidden_layers = [net.initial_layer] + [lin for block in net.blocks for lin in block.linear_layers]
-    n_layers = len(hidden_layers) + 1
-    frag0, frag_l = k0s * 4 * 2 * 64 * 8, 2 * 4 * 2 * 64 * 8
-    w_frag = torch.empty(frag0 + (n_layers - 1) * frag_l, dtype=torch.float16, device=dev)
-    w_un = torch.empty(n_layers, dtype=torch.float32, device=dev)
-    bias_acc = torch.empty(n_layers, 64, dtype=torch.float32, device=dev)
+    hidden_layers = _hidden_linears(net)
+    image = _hidden_image(len(hidden_layers) + 1, k0s, dev)
     lin = net.final_layer
     stage_w = torch.zeros(64, 64, dtype=torch.float32, device=dev)
     stage_b = torch.zeros(64, dtype=torch.float32, device=dev)
@@ -800,17 +847,11 @@ def device_pack_affine_coupling(net, d_t, additive):
                 stage_b[32:32 + d_t].copy_(lin.bias[d_t:2 * d_t])
 
     pack = DevicePack(dev)
-    off = 0
-    for i, layer in enumerate(hidden_layers):
-        size = frag0 if i == 0 else frag_l
-        pack.add(PACK_HIDDEN, layer.weight, layer.bias, w_frag[off:off + size], w_un[i:i + 1], bias_acc[i],
-                 nks=k0s if i == 0 else 2, nt=4)
-        off += size
-    pack.add(PACK_HIDDEN, stage_w, stage_b, w_frag[off:off + frag_l], w_un[n_layers - 1:n_layers], bias_acc[n_layers - 1],
-             nks=2, nt=4, track=False)
+    _add_hidden_jobs(pack, image, k0s, [(layer.weight, layer.bias, True) for layer in hidden_layers]
+                     + [(stage_w, stage_b, False)])
     pack.sources += [lin.weight, lin.bias]        # (the staging buffers' versions move only when these do)
     pack.prepare.append(stage)
-    return pack, (w_frag, w_un, bias_acc)
+    return pack, image
 
 
 def device_pack_made_affine(made, features):
@@ -819,13 +860,9 @@ def device_pack_made_affine(made, features):
     pack launch), the final masked Linear re-ordered from the interleaved [D, (u, shift)] rows to rows 0..31 = shift of dims
     0..31, rows 32..63 = u.  Returns ``(pack, packed)`` like ``device_pack_affine_coupling``."""
     dev = made.initial_layer.weight.device
-    hidden_layers = [made.initial_layer] + [lin for block in made.blocks for lin in block.linear_layers]
+    hidden_layers = _hidden_linears(made)
     n_layers = len(hidden_layers) + 1
-    k0s = 1
-    frag0, frag_l = k0s * 4 * 2 * 64 * 8, 2 * 4 * 2 * 64 * 8
-    w_frag = torch.empty(frag0 + (n_layers - 1) * frag_l, dtype=torch.float16, device=dev)
-    w_un = torch.empty(n_layers, dtype=torch.float32, device=dev)
-    bias_acc = torch.empty(n_layers, 64, dtype=torch.float32, device=dev)
+    image = _hidden_image(n_layers, 1, dev)
     final = made.final_layer
     stage_w = [torch.zeros(64, 32 if i == 0 else 64, dtype=torch.float32, device=dev) for i in range(n_layers)]
     stage_b = [torch.zeros(64, dtype=torch.float32, device=dev) for _ in range(n_layers)]
@@ -843,16 +880,24 @@ def device_pack_made_affine(made, features):
             stage_b[-1][32:32 + features].copy_(final.bias[0::2])
 
     pack = DevicePack(dev)
-    off = 0
-    for i in range(n_layers):
-        size = frag0 if i == 0 else frag_l
-        pack.add(PACK_HIDDEN, stage_w[i], stage_b[i], w_frag[off:off + size], w_un[i:i + 1], bias_acc[i],
-                 nks=k0s if i == 0 else 2, nt=4, track=False)
-        off += size
+    _add_hidden_jobs(pack, image, 1, [(w, b, False) for w, b in zip(stage_w, stage_b)])
     for lin in hidden_layers + [final]:
         pack.sources += [lin.weight, lin.bias]
     pack.prepare.append(stage)
-    return pack, (w_frag, w_un, bias_acc)
+    return pack, image
+
+
+def device_plan(owner, slot, where, build):
+    """The device pack plan ``[where, pack, packed, ...]`` that ``owner`` keeps in attribute ``slot``.  Its jobs hold raw
+    device pointers, so it is rebuilt (``build()`` -> ``(pack, packed, ...)``) whenever ``where`` -- the storages it reads
+    and whatever else it was built around -- differs from the one it was built for.  An object that ``where`` names by
+    ``id()`` must be returned by ``build()`` into the tail of the plan, so that the id cannot be reused while the plan
+    lives.  The caller refreshes ``plan[1]``."""
+    plan = getattr(owner, slot, None)
+    if plan is None or plan[0] != where:
+        plan = [where, *build()]
+        setattr(owner, slot, plan)
+    return plan
 
 
 MADE_AFFINE, MADE_RQ = 0, 1
@@ -892,7 +937,7 @@ def pack_made_inverse(made, features, per_dim):
     dev = made.initial_layer.weight.device
     perm = _hb_perm().to(dev)
     k0s = 1 if features <= 32 else 2
-    layers = [made.initial_layer] + [lin for block in made.blocks for lin in block.linear_layers]
+    layers = _hidden_linears(made)
     wf, uns, biases = [], [], []
     with torch.no_grad():
         order, need = _made_pass_prefix(made, features, per_dim, hw)
@@ -909,10 +954,10 @@ def pack_made_inverse(made, features, per_dim):
                 moved[slot.reshape(-1, 1), slot.reshape(1, -1)] = w[order.reshape(-1, 1), order.reshape(1, -1)]
             sc, un = _pow2_scale(moved.abs().amax().reshape(1))
             uns.append(un)
-            wf.append(_a_fragments((moved * sc)[perm]).permute(1, 0, 2, 3, 4).reshape(-1))        # [ks][t][piece][lane][8]
+            wf.append(_hidden_layer_fragments(moved * sc, perm))
             b = torch.zeros(hw, device=dev)
             b[slot] = _pad_to(lin.bias.detach().float(), (hw,))[order]
-            biases.append(b[perm].reshape(4, 4, 4).permute(1, 0, 2).reshape(-1))
+            biases.append(_bias_accumulator_order(b, perm))
         final = made.final_layer
         pt = -(-per_dim // 16)
         w = _pad_to((final.weight * final.mask).detach().float().reshape(features, per_dim, -1), (features, 16 * pt, hw))
@@ -947,9 +992,8 @@ def pack_made_inverse_context(made, features, per_dim):
             w = _pad_to(lin.weight.detach().float(), (hw, 32))[order]              # row r = the unit of rank r
             sc, un = _pow2_scale(w.abs().amax().reshape(1))
             uns.append(un)
-            wf.append(_a_fragments(w * sc).permute(1, 0, 2, 3, 4).reshape(-1))     # [ks = 1][t][piece][lane][8]
-            b = _pad_to(lin.bias.detach().float(), (hw,))[order]
-            biases.append(b.reshape(4, 4, 4).permute(1, 0, 2).reshape(-1))
+            wf.append(_hidden_layer_fragments(w * sc))                              # (one k-step)
+            biases.append(_bias_accumulator_order(_pad_to(lin.bias.detach().float(), (hw,))[order]))
     return torch.cat(wf).contiguous(), torch.cat(uns).float().contiguous(), torch.stack(biases).contiguous()
 
 
@@ -999,15 +1043,11 @@ def made_inverse(inputs, packed, num_blocks, per_dim, kind, rq=None, logabsdet_a
         if rq:
             raise TypeError("made_inverse: unknown spline arguments %s" % sorted(rq))
     y = torch.empty_like(z)
-    if logabsdet_accum is not None:
-        lad = logabsdet_accum
-        if lad.dtype != torch.float32 or lad.shape != (n,) or not lad.is_contiguous() or lad.device != z.device:
-            raise ValueError("logabsdet_accum must be a contiguous float32 [N] tensor on the inputs' device")
+    lad, flags = _logabsdet_target(logabsdet_accum, n, z.device)
+    if flags:
         if cfg is None:
             cfg = _hip.RQConfig()          # affine form: only the flags are read
-        cfg.flags = 1  # FC_RQ_ACCUMULATE_LOGABSDET
-    else:
-        lad = torch.empty(n, dtype=torch.float32, device=z.device)
+        cfg.flags = flags
     err = _err_word(z.device, True)
     hf, hu, hb, ff, fu, fb, need = packed
     if need.dtype != torch.int32 or need.numel() != d:
@@ -1054,16 +1094,10 @@ def affine_coupling_resnet(inputs, id_cols, tr_cols, packed, in_features, num_bl
     w_frag, w_un, bias_acc = packed
     ids, cols = _as_cols(id_cols, x.device), _as_cols(tr_cols, x.device)
     y = torch.empty_like(x)
-    if logabsdet_accum is not None:
-        lad = logabsdet_accum
-        if lad.dtype != torch.float32 or lad.shape != (n,) or not lad.is_contiguous() or lad.device != x.device:
-            raise ValueError("logabsdet_accum must be a contiguous float32 [N] tensor on the inputs' device")
-    else:
-        lad = torch.empty(n, dtype=torch.float32, device=x.device)
+    lad, accumulate = _logabsdet_target(logabsdet_accum, n, x.device)
     _call("fc_affine_coupling_resnet", lib.fc_affine_coupling_resnet, x.device, _hip.ptr(x), _hip.ptr(y), _hip.ptr(ids),
           _hip.ptr(cols), _hip.ptr(w_frag), _hip.ptr(w_un), _hip.ptr(bias_acc), _hip.ptr(lad), n, d, in_features,
-          cols.numel(), 64, num_blocks, int(activation), 1 if inverse else 0, 0 if logabsdet_accum is None else 1,
-          _hip.stream_ptr(x.device))
+          cols.numel(), 64, num_blocks, int(activation), 1 if inverse else 0, accumulate, _hip.stream_ptr(x.device))
     return y, lad
 
 
@@ -1088,12 +1122,6 @@ def resnet_hidden_packed(inputs, id_cols, packed, in_features, num_blocks, activ
     return h
 
 
-def _hb_perm():
-    """Feature held by accumulator tile t, row rho of the hidden-layer kernels: 32 (t >> 1) + 8 g + 4 (t & 1) + r with
-    g = rho >> 2, r = rho & 3 (the order in which the C layout of one layer is the B operand of the next)."""
-    return torch.tensor([32 * (t >> 1) + 8 * (rho >> 2) + 4 * (t & 1) + (rho & 3) for t in range(4) for rho in range(16)])
-
-
 def pack_resnet_hidden_backward(net):
     """Everything ``fc_resnet_hidden_backward`` needs of a ResidualNet with hidden <= 64, <= 2 ReLU blocks, no context:
     forward fragments (rows in accumulator order), fragments of the transposed weights for the W^T products, one
@@ -1103,7 +1131,7 @@ def pack_resnet_hidden_backward(net):
     perm = _hb_perm().to(net.initial_layer.weight.device)
     k0 = net.initial_layer.in_features
     k0s = 1 if k0 <= 32 else 2
-    layers = [net.initial_layer] + [lin for block in net.blocks for lin in block.linear_layers]
+    layers = _hidden_linears(net)
     wf, wt, uns, biases = [], [], [], []
     scaled = []
     for i, lin in enumerate(layers):
@@ -1111,11 +1139,11 @@ def pack_resnet_hidden_backward(net):
         sc, un = _pow2_scale(w.abs().amax().reshape(1))
         scaled.append(w * sc)
         uns.append(un)
-        wf.append(_a_fragments(scaled[-1][perm]).permute(1, 0, 2, 3, 4).reshape(-1))         # [ks][t][piece][lane][8]
-        biases.append(_pad_to(lin.bias.detach().float(), (hw,))[perm].reshape(4, 4, 4).permute(1, 0, 2).reshape(-1))
+        wf.append(_hidden_layer_fragments(scaled[-1], perm))
+        biases.append(_bias_accumulator_order(_pad_to(lin.bias.detach().float(), (hw,)), perm))
     for w in scaled[1:]:
-        wt.append(_a_fragments(w.t().contiguous()[perm]).permute(1, 0, 2, 3, 4).reshape(-1))
-    wt.append(_a_fragments(scaled[0].t().contiguous()).permute(1, 0, 2, 3, 4).reshape(-1))     # W0^T: rows natural
+        wt.append(_hidden_layer_fragments(w.t().contiguous(), perm))
+    wt.append(_hidden_layer_fragments(scaled[0].t().contiguous()))     # W0^T: rows natural
     return (torch.cat(wf).contiguous(), torch.cat(wt).contiguous(), torch.cat(uns).float().contiguous(),
             torch.stack(biases).contiguous(), k0s)
 
@@ -1208,7 +1236,7 @@ def pack_final_layer(weight, bias, num_bins=FUSED_BINS):
     [dp*24]): one zero row / entry appended per dim so that a dim is 24 = 6 x 4 accumulator registers, zero
     dims appended up to dp = ceil(d_t / 4) * 4 (a wave owns 4 dims), zero columns up to the kernel's 64 hidden
     units (they meet the zero activations of a zero-padded hidden stack)."""
-    p = 3 * num_bins - 1
+    p = rq_param_count(num_bins, "linear")
     d_t = weight.shape[0] // p
     dp = -(-d_t // 4) * 4
     hidden = weight.shape[1]
@@ -1243,21 +1271,10 @@ def rq_spline_fused_linear(inputs, hidden, w_pad, bias_pad, cols, *, num_bins, t
         raise ValueError("fused RQ layer: unsupported shapes %s / %s" % (tuple(x.shape), tuple(h.shape)))
     w_pad = _aligned16(_hip.dev_f32(w_pad.detach(), "weight"))
     bias_pad = _hip.dev_f32(bias_pad.detach(), "bias")
-    cfg = _hip.RQConfig()
-    cfg.num_bins, cfg.tails, cfg.inverse = num_bins, 1, 1 if inverse else 0
-    cfg.left, cfg.right, cfg.bottom, cfg.top = -tail_bound, tail_bound, -tail_bound, tail_bound
-    cfg.min_bin_width, cfg.min_bin_height, cfg.min_derivative = min_bin_width, min_bin_height, min_derivative
-    cfg.wh_divisor = wh_divisor
-    cfg.softplus_beta = (math.log(2) / (1 - min_derivative)) if enable_identity_init else 1.0
-    cfg.tail_constant = float(np.log(np.exp(1 - min_derivative) - 1))
+    cfg = _rq_config(num_bins, "linear", tail_bound, None, min_bin_width, min_bin_height, min_derivative,
+                     enable_identity_init, wh_divisor, inverse)
     y = torch.empty_like(x)
-    if logabsdet_accum is not None:
-        lad = logabsdet_accum
-        if lad.dtype != torch.float32 or lad.shape != (n,) or not lad.is_contiguous() or lad.device != x.device:
-            raise ValueError("logabsdet_accum must be a contiguous float32 [N] tensor on the inputs' device")
-        cfg.flags = 1  # FC_RQ_ACCUMULATE_LOGABSDET
-    else:
-        lad = torch.empty(n, dtype=torch.float32, device=x.device)
+    lad, cfg.flags = _logabsdet_target(logabsdet_accum, n, x.device)      # FC_RQ_ACCUMULATE_LOGABSDET
     if raw:
         cfg.flags |= 4  # FC_RQ_RAW_WEIGHTS
     err = _err_word(x.device, True)
@@ -1299,8 +1316,7 @@ def pack_final_layer_general(weight, bias, num_bins, tails, hidden_pad):
         bias_pad f32 [groups, 4, 4 T]
 
     (zero rows / dims / columns pad P to 4 T, d_t to 4 * groups, H to ``hidden_pad``)."""
-    k = num_bins
-    p = 3 * k - 1 if tails == "linear" else 3 * k + 1
+    p = rq_param_count(num_bins, tails)
     pp = -(-p // 4) * 4
     t = pp // 4
     d_t = weight.shape[0] // p
@@ -1330,8 +1346,7 @@ def pack_final_layer_transposed(weight, num_bins, tails):
     f16 [groups, 4 hidden tiles, KK, 2 (hi, lo), 64 lanes, 8], KK = ceil(4T / 8); lane l of fragment (group, ht, kk)
     holds 2^S W[dim 4 group + (l >> 4)][param 8 kk + j][hidden 16 ht + (l & 15)] -- the k order in which a lane of the
     kernel holds its own parameter gradients.  Same per-group scale as ``pack_final_layer_general``.  hidden <= 64."""
-    k = num_bins
-    p = 3 * k - 1 if tails == "linear" else 3 * k + 1
+    p = rq_param_count(num_bins, tails)
     pp = -(-p // 4) * 4
     pp8 = -(-pp // 8) * 8
     kk = pp8 // 8
@@ -1374,7 +1389,7 @@ def rq_fused_linear_backward(inputs, hidden, grad_outputs, grad_logabsdet, packe
         raise ValueError("fused RQ layer backward: unsupported shapes %s / %s" % (tuple(x.shape), tuple(h.shape)))
     cfg = _rq_config(num_bins, tails, tail_bound, (left, right, bottom, top), min_bin_width, min_bin_height,
                      min_derivative, enable_identity_init, wh_divisor, False)
-    p = 3 * num_bins - 1 if tails == "linear" else 3 * num_bins + 1
+    p = rq_param_count(num_bins, tails)
     pp = bias_pad.shape[-1]
     groups = bias_pad.shape[0]
     gx = torch.empty_like(x)
@@ -1396,7 +1411,7 @@ def fused_backward_supported(n, d, d_t, hidden, num_bins, tails):
     launch, D <= 128."""
     if tails not in (None, "linear") or num_bins not in GENERAL_BINS or hidden > 64:
         return False
-    p = 3 * num_bins - 1 if tails == "linear" else 3 * num_bins + 1
+    p = rq_param_count(num_bins, tails)
     return p <= 32 and 1 <= d_t <= FUSED_DT and d <= 128 and n >= FUSED_ROWS
 
 
@@ -1423,13 +1438,7 @@ def rq_spline_fused_general(inputs, hidden, w_frag, w_unscale, bias_pad, cols, *
     cfg = _rq_config(num_bins, tails, tail_bound, (left, right, bottom, top), min_bin_width, min_bin_height,
                      min_derivative, enable_identity_init, wh_divisor, inverse)
     y = torch.empty_like(x)
-    if logabsdet_accum is not None:
-        lad = logabsdet_accum
-        if lad.dtype != torch.float32 or lad.shape != (n,) or not lad.is_contiguous() or lad.device != x.device:
-            raise ValueError("logabsdet_accum must be a contiguous float32 [N] tensor on the inputs' device")
-        cfg.flags = 1  # FC_RQ_ACCUMULATE_LOGABSDET
-    else:
-        lad = torch.empty(n, dtype=torch.float32, device=x.device)
+    lad, cfg.flags = _logabsdet_target(logabsdet_accum, n, x.device)      # FC_RQ_ACCUMULATE_LOGABSDET
     if streamed_weights:
         cfg.flags |= 8  # FC_RQ_STREAMED_WEIGHTS
     err = _err_word(x.device, True)
@@ -1522,15 +1531,10 @@ def _affine_coupling_nograd(inputs, params, cols=None, *, activation=AFFINE_SIGM
     if p.numel() != want:
         raise ValueError("params has %d elements, expected %d" % (p.numel(), want))
     y = torch.empty_like(x)
-    if logabsdet_accum is not None:
-        lad = logabsdet_accum
-        if lad.dtype != torch.float32 or lad.shape != (n,) or not lad.is_contiguous() or lad.device != x.device:
-            raise ValueError("logabsdet_accum must be a contiguous float32 [N] tensor on the inputs' device")
-    else:
-        lad = torch.empty(n, dtype=torch.float32, device=x.device)
+    lad, accumulate = _logabsdet_target(logabsdet_accum, n, x.device)      # LAD_STORE / LAD_ACCUMULATE
     _call("fc_affine", lib.fc_affine, x.device, _hip.ptr(x), _hip.ptr(y), _hip.ptr(p), _hip.ptr(cols),
           _hip.ptr(lad), n, d, d_t, activation, 1 if inverse else 0, 1 if shared_params else 0,
-          LAD_STORE if logabsdet_accum is None else LAD_ACCUMULATE, _hip.stream_ptr(x.device))
+          accumulate, _hip.stream_ptr(x.device))
     return y, lad
 
 

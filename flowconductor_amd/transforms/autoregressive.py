@@ -10,6 +10,7 @@ import torch
 from torch.nn import functional as F
 
 from flowconductor_amd import ops, options
+from flowconductor_amd.transforms import fused_rq
 from flowconductor_amd.transforms import made as made_module
 from flowconductor_amd.transforms.base import Transform
 
@@ -278,11 +279,8 @@ class MaskedAffineAutoregressiveTransform(AutoregressiveTransform):
         net = self.autoregressive_net
         features = inputs.shape[1]
         where = tuple(p.data_ptr() for p in ops.param_list(net))
-        plan = getattr(self, "_tail_image", None)
-        if plan is None or plan[0] != where:
-            pack, packed = ops.device_pack_made_affine(net, features)
-            cols = torch.arange(features, dtype=torch.int32, device=inputs.device)
-            plan = self._tail_image = [where, pack, packed, cols]
+        plan = ops.device_plan(self, "_tail_image", where, lambda: ops.device_pack_made_affine(net, features) + (
+            torch.arange(features, dtype=torch.int32, device=inputs.device),))
         plan[1].refresh()
         n = inputs.shape[0]
         body = n - n % ops.HIDDEN_ROWS
@@ -376,12 +374,9 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
         super().__init__(made)
 
     def _output_dim_multiplier(self):
-        if self.tails == "linear":
-            return self.num_bins * 3 - 1
-        elif self.tails is None:
-            return self.num_bins * 3 + 1
-        else:
+        if self.tails not in (None, "linear"):
             raise ValueError
+        return ops.rq_param_count(self.num_bins, self.tails)
 
     def _elementwise(self, inputs, autoregressive_params, inverse=False):
         if self.tails not in (None, "linear"):
@@ -429,49 +424,32 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
                 and inputs.shape[0] >= ops.FUSED_ROWS and not ops.has_hooks(net) and not self._needs_grad(inputs)):
             return None
         n, d = inputs.shape
-        if ops.fused_linear_supported(n, d, d, net.final_layer.in_features, self.num_bins, self.tails):
-            return "k8"
-        if ops.fused_general_supported(n, d, d, 64, self.num_bins, self.tails):
-            return "general"
-        return None
+        return fused_rq.fused_mode(n, d, d, net.final_layer.in_features, self.num_bins, self.tails, 64)
 
     def _fused_forward_ok(self, inputs, context):
         return self._fused_forward_mode(inputs, context) is not None
 
-    def _packed_final_layer(self, device, mode="k8"):
+    def _pack_spec(self):
+        """What ``fused_rq.packed_chunks`` packs of this layer: the masked final Linear, hidden padded to 64, one chunk."""
         lin = self.autoregressive_net.final_layer
-        key = ops.cache_key(lin.weight, lin.bias)
-        if getattr(self, "_packed", None) is None or self._packed[0] != (key, mode):
-            masked = (lin.weight * lin.mask).detach()
-            if mode == "k8":
-                packed = ops.pack_final_layer(masked, lin.bias, self.num_bins)
-            else:
-                packed = ops.pack_final_layer_general(masked, lin.bias, self.num_bins, self.tails, 64)
-            cols = torch.arange(lin.out_features // self._output_dim_multiplier(), dtype=torch.int32, device=device)
-            self._packed = ((key, mode), masked) + tuple(packed) + (cols,)
-        return self._packed[1:]
+        cols = torch.arange(lin.out_features // self._output_dim_multiplier(), dtype=torch.int32, device=lin.weight.device)
+        return (lin.weight * lin.mask).detach(), 64, [(slice(None), cols)]
 
     def forward(self, inputs, context=None):
         mode = self._fused_forward_mode(inputs, context)
         if mode is None:
             return super().forward(inputs, context)
         hidden = self._hidden(inputs, context)
+        lin = self.autoregressive_net.final_layer
+        chunks = fused_rq.packed_chunks(self, lin, mode, self.num_bins, self.tails, self._pack_spec)
         kw = dict(num_bins=self.num_bins, tail_bound=self.tail_bound, min_bin_width=self.min_bin_width,
                   min_bin_height=self.min_bin_height, min_derivative=self.min_derivative, wh_divisor=1.0,
                   enable_identity_init=True)
-        n = inputs.shape[0]
-        body = n - n % ops.FUSED_ROWS
-        if mode == "k8":
-            _, w_pad, b_pad, cols = self._packed_final_layer(inputs.device)
-            outputs, logabsdet = ops.rq_spline_fused_linear(inputs[:body], hidden[:body], w_pad, b_pad, cols, **kw)
-        else:
-            _, w_frag, w_un, b_pad, cols = self._packed_final_layer(inputs.device, "general")
-            outputs, logabsdet = ops.rq_spline_fused_general(inputs[:body], hidden[:body], w_frag, w_un, b_pad, cols,
-                                                             tails=self.tails, left=-1.2, right=1.2, bottom=-1.2, top=1.2, **kw)
-        if body < n:   # the < 32 leftover rows: masked final Linear + the stand-alone kernel
-            out_b, lad_b = self._elementwise_forward(inputs[body:], self._final(hidden[body:]))
-            outputs, logabsdet = torch.cat((outputs, out_b)), torch.cat((logabsdet, lad_b))
-        return outputs, logabsdet
+        if mode == "general":
+            kw.update(tails=self.tails, left=-1.2, right=1.2, bottom=-1.2, top=1.2)
+        # the < 32 leftover rows: masked final Linear + the stand-alone kernel
+        return fused_rq.apply(inputs, hidden, chunks, mode, kw, None,
+                              lambda rows, h: self._elementwise_forward(rows, self._final(h)))
 
 
 class MaskedSumOfSigmoidsTransform(AutoregressiveTransform):

@@ -11,6 +11,7 @@ from torch.nn import functional as F
 
 from flowconductor_amd import ops, options
 from flowconductor_amd.nn.nets import MLP, ResidualNet
+from flowconductor_amd.transforms import fused_rq
 from flowconductor_amd.transforms.coupling import _is_plain_resnet
 from flowconductor_amd.transforms.base import Transform
 from flowconductor_amd.transforms.orthogonal import ParametrizedHouseHolder
@@ -369,12 +370,9 @@ class ConditionalPiecewiseRationalQuadraticTransform(ConditionalTransform):
                          dropout_probability=dropout_probability, use_batch_norm=use_batch_norm)
 
     def _output_dim_multiplier(self):
-        if self.tails == "linear":
-            return self.num_bins * 3 - 1
-        elif self.tails is None:
-            return self.num_bins * 3 + 1
-        else:
+        if self.tails not in (None, "linear"):
             raise ValueError
+        return ops.rq_param_count(self.num_bins, self.tails)
 
     def _elementwise(self, inputs, autoregressive_params, inverse=False):
         divisor = 1.0
@@ -403,42 +401,29 @@ class ConditionalPiecewiseRationalQuadraticTransform(ConditionalTransform):
             return None
         n, d = inputs.shape
         hidden = self.conditional_net.hidden_features
-        if ops.fused_linear_supported(n, d, d, hidden, self.num_bins, self.tails):
-            return "k8"
-        if hidden <= 64 and ops.fused_general_supported(n, d, d, 64, self.num_bins, self.tails):
-            return "general"
-        return None
+        return fused_rq.fused_mode(n, d, d, hidden, self.num_bins, self.tails, 64 if hidden <= 64 else None)
 
     def _fused_ok(self, inputs, context):
         return self._fused_mode(inputs, context) is not None
+
+    def _pack_spec(self):
+        """What ``fused_rq.packed_chunks`` packs of this layer: the raw final Linear, hidden padded to 64, one chunk."""
+        lin = self.conditional_net.final_layer
+        return lin.weight, 64, [(slice(None), torch.arange(self.features, dtype=torch.int32, device=lin.weight.device))]
 
     def _fused(self, inputs, context, inverse):
         mode = self._fused_mode(inputs, context)
         net = self.conditional_net
         lin = net.final_layer
-        key = (ops.cache_key(lin.weight, lin.bias), mode)
-        if getattr(self, "_packed", None) is None or self._packed[0] != key:
-            if mode == "k8":
-                packed = ops.pack_final_layer(lin.weight, lin.bias, self.num_bins)
-            else:
-                packed = ops.pack_final_layer_general(lin.weight, lin.bias, self.num_bins, self.tails, 64)
-            cols = torch.arange(self.features, dtype=torch.int32, device=lin.weight.device)
-            self._packed = (key,) + tuple(packed) + (cols,)
+        chunks = fused_rq.packed_chunks(self, lin, mode, self.num_bins, self.tails, self._pack_spec)
         hidden = self._hidden(context)
         kw = dict(num_bins=self.num_bins, tail_bound=self.tail_bound, min_bin_width=self.min_bin_width,
                   min_bin_height=self.min_bin_height, min_derivative=self.min_derivative,
                   wh_divisor=float(np.sqrt(net.hidden_features)), enable_identity_init=True, inverse=inverse)
-        n = inputs.shape[0]
-        body = n - n % ops.FUSED_ROWS
-        if mode == "k8":
-            outputs, logabsdet = ops.rq_spline_fused_linear(inputs[:body], hidden[:body], *self._packed[1:], **kw)
-        else:
-            outputs, logabsdet = ops.rq_spline_fused_general(inputs[:body], hidden[:body], *self._packed[1:], tails=self.tails,
-                                                             left=-1.2, right=1.2, bottom=-1.2, top=1.2, **kw)
-        if body < n:
-            out_b, lad_b = self._elementwise(inputs[body:].contiguous(), net.final_from_padded(hidden[body:]), inverse)
-            outputs, logabsdet = torch.cat((outputs, out_b)), torch.cat((logabsdet, lad_b))
-        return outputs, logabsdet
+        if mode == "general":
+            kw.update(tails=self.tails, left=-1.2, right=1.2, bottom=-1.2, top=1.2)
+        return fused_rq.apply(inputs, hidden, chunks, mode, kw, None,
+                              lambda rows, h: self._elementwise(rows, net.final_from_padded(h), inverse))
 
     def forward(self, inputs, context=None):
         if context is not None and self._fused_ok(inputs, context):

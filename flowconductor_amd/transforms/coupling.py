@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from flowconductor_amd import ops, options
+from flowconductor_amd.transforms import fused_rq
 from flowconductor_amd.transforms.base import Transform
 
 
@@ -228,12 +229,8 @@ class AffineCouplingTransform(CouplingTransform):
 
     def _one_kernel(self, inputs, inverse, total):
         net = self.transform_net
-        where = net._storage_key()
-        plan = getattr(self, "_tail_image", None)
-        if plan is None or plan[0] != where:
-            pack, packed = ops.device_pack_affine_coupling(net, self.num_transform_features,
-                                                           self._activation_code() == ops.AFFINE_ADDITIVE)
-            plan = self._tail_image = [where, pack, packed]
+        plan = ops.device_plan(self, "_tail_image", net._storage_key(), lambda: ops.device_pack_affine_coupling(
+            net, self.num_transform_features, self._activation_code() == ops.AFFINE_ADDITIVE))
         plan[1].refresh()
         n = inputs.shape[0]
         body = n - n % ops.HIDDEN_ROWS
@@ -345,9 +342,7 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
         super().__init__(mask, transform_net_create_fn, unconditional_transform=unconditional_transform)
 
     def _transform_dim_multiplier(self):
-        if self.tails == "linear":
-            return self.num_bins * 3 - 1
-        return self.num_bins * 3 + 1
+        return ops.rq_param_count(self.num_bins, self.tails)
 
     def _coupling_kernel(self, inputs, transform_params, inverse):
         # (records an autograd node when gradients are required: ops._RQSplineFunction)
@@ -377,42 +372,26 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
                 and inputs.dim() == 2 and inputs.is_cuda and inputs.dtype == torch.float32):
             return None
         n, d = inputs.shape
-        d_t = min(self.num_transform_features, ops.FUSED_DT)
-        if ops.fused_linear_supported(n, d, d_t, net.hidden_features, self.num_bins, self.tails):
-            return "k8"
-        if ops.fused_general_supported(n, d, d_t, net.hidden_features, self.num_bins, self.tails):
-            return "general"
-        return None
+        return fused_rq.fused_mode(n, d, min(self.num_transform_features, ops.FUSED_DT), net.hidden_features, self.num_bins,
+                                   self.tails, net.hidden_features)
 
     def _fused_ok(self, inputs):
         return self._fused_mode(inputs) is not None
 
-    def _fused_chunks(self, device, mode):
-        """Per group of <= 32 transformed dims: the final Linear's rows of those dims in the kernel's layout + their
-        column indices -- (w_pad, bias_pad, cols) for "k8", (w_frag, w_unscale, bias_pad, cols) for "general"."""
+    def _chunk_spec(self, device):
+        """[(rows of the final Linear, column indices)] per group of <= 32 transformed dims."""
+        per_dim = self._transform_dim_multiplier()
+        cols = self._cols(device)
+        spec = []
+        for lo in range(0, self.num_transform_features, ops.FUSED_DT):
+            hi = min(lo + ops.FUSED_DT, self.num_transform_features)
+            spec.append((slice(lo * per_dim, hi * per_dim), cols[lo:hi].contiguous()))
+        return spec
+
+    def _pack_spec(self):
+        """What ``fused_rq.packed_chunks`` packs of this layer: the raw final Linear, one chunk per <= 32 transformed dims."""
         lin = self.transform_net.final_layer
-        key = ops.cache_key(lin.weight, lin.bias)
-        cache = getattr(self, "_packed", None)
-        if cache is None or cache[0] != key:
-            cache = self._packed = (key, {})
-        if mode not in cache[1]:
-            per_dim = self._transform_dim_multiplier()
-            cols = self._cols(device)
-            hidden_pad = ops.general_hidden_width(lin.in_features)
-            chunks = []
-            for lo in range(0, self.num_transform_features, ops.FUSED_DT):
-                hi = min(lo + ops.FUSED_DT, self.num_transform_features)
-                rows = slice(lo * per_dim, hi * per_dim)
-                if mode == "k8":
-                    packed = ops.pack_final_layer(lin.weight[rows], lin.bias[rows], self.num_bins)
-                elif mode == "general":
-                    packed = ops.pack_final_layer_general(lin.weight[rows], lin.bias[rows], self.num_bins, self.tails,
-                                                          hidden_pad)
-                else:   # "transposed": W^T fragments of the backward product gh = W^T G
-                    packed = (ops.pack_final_layer_transposed(lin.weight[rows], self.num_bins, self.tails), rows)
-                chunks.append(packed + (cols[lo:hi].contiguous(),))
-            cache[1][mode] = chunks
-        return cache[1][mode]
+        return lin.weight, ops.general_hidden_width(lin.in_features), self._chunk_spec(lin.weight.device)
 
     def _train_chunks(self, device):
         """Training: forward + W^T fragments of the final Linear for every group of <= 32 dims, re-packed on the device
@@ -422,22 +401,19 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
         hidden_pack = None
         if getattr(net, "hip_hidden_backward_supported", None) is not None and net.hip_hidden_backward_supported():
             hidden_pack = net.hidden_backward_plan()[1]        # rebuilt by the net when ITS storages moved
-        where = (lin.weight.data_ptr(), lin.bias.data_ptr(), device)
-        plan = getattr(self, "_train_pack", None)
-        if plan is None or plan[0] is not lin.weight or plan[1] != where or plan[4] is not hidden_pack:
-            per_dim = self._transform_dim_multiplier()
-            cols = self._cols(device)
-            spec = []
-            for lo in range(0, self.num_transform_features, ops.FUSED_DT):
-                hi = min(lo + ops.FUSED_DT, self.num_transform_features)
-                spec.append((slice(lo * per_dim, hi * per_dim), cols[lo:hi].contiguous()))
+
+        def build():
             pack, chunks = ops.device_pack_final_layer(lin.weight.detach(), lin.bias.detach(), self.num_bins, self.tails,
-                                                       spec)
+                                                       self._chunk_spec(device))
             if hidden_pack is not None:
                 pack.merge(hidden_pack)      # the hidden stack's images ride in the same launch
-            plan = self._train_pack = [lin.weight, where, pack, chunks, hidden_pack]
-        plan[2].refresh()
-        return plan[3]
+            return pack, chunks, lin.weight, hidden_pack       # (the plan keeps alive what `where` names by id)
+
+        # also rebuilt when lin.weight is a new Parameter object or the hidden pack it merged is a different one
+        where = (id(lin.weight), lin.weight.data_ptr(), lin.bias.data_ptr(), device, id(hidden_pack))
+        plan = ops.device_plan(self, "_train_pack", where, build)
+        plan[1].refresh()
+        return plan[2]
 
     def _apply_accumulate(self, inputs, context, inverse, total):
         """CompositeTransform fast path: the fused kernel adds this layer's logabsdet onto ``total`` itself."""
@@ -450,9 +426,18 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
         return outputs
 
     def _fused_kw(self, net):
+        """Spline arguments the fused forward kernels and the fused backward kernel have in common."""
         return dict(num_bins=self.num_bins, tail_bound=self.tail_bound, min_bin_width=self.min_bin_width,
                     min_bin_height=self.min_bin_height, min_derivative=self.min_derivative,
                     wh_divisor=_softmax_divisor(net, warn=False))
+
+    def _fused_forward_kw(self, net, mode, inverse):
+        """``_fused_kw`` + the direction and, for "general", the tails ("k8" is linear tails only and takes none)."""
+        kw = self._fused_kw(net)
+        kw["inverse"] = inverse
+        if mode == "general":
+            kw["tails"] = self.tails
+        return kw
 
     def _hidden_for_fused(self, inputs, identity_split, context, width):
         """[N, width] hidden activation of the conditioner (zero columns beyond ``hidden_features``): the hidden-layer
@@ -511,7 +496,6 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
             return super()._run(inputs, context, inverse)
         self._check(inputs)
         net = self.transform_net
-        n = inputs.shape[0]
         identity_split = logabsdet_identity = None
         if self.unconditional_transform is not None:
             identity_split = inputs[:, self.identity_features]
@@ -519,39 +503,15 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
                 identity_split, logabsdet_identity = self.unconditional_transform.inverse(identity_split, context)
         width = 64 if mode == "k8" else ops.general_hidden_width(net.hidden_features)
         hidden = self._hidden_for_fused(inputs, identity_split, context, width)
-        chunks = self._fused_chunks(inputs.device, mode)
-        kw = dict(num_bins=self.num_bins, tail_bound=self.tail_bound, min_bin_width=self.min_bin_width,
-                  min_bin_height=self.min_bin_height, min_derivative=self.min_derivative,
-                  wh_divisor=_softmax_divisor(net, warn=False), inverse=inverse)
+        chunks = fused_rq.packed_chunks(self, net.final_layer, mode, self.num_bins, self.tails, self._pack_spec)
+        kw = self._fused_forward_kw(net, mode, inverse)
 
-        def fused(rows, h, accum):
-            # the groups only depend on the identity columns: any order, each launch passes the rest through
-            lad = accum
-            for chunk in chunks:
-                if mode == "k8":
-                    w_pad, bias_pad, cols = chunk
-                    rows, lad = ops.rq_spline_fused_linear(rows, h, w_pad, bias_pad, cols, logabsdet_accum=lad, **kw)
-                else:
-                    w_frag, w_un, bias_pad, cols = chunk
-                    rows, lad = ops.rq_spline_fused_general(rows, h, w_frag, w_un, bias_pad, cols, tails=self.tails,
-                                                            logabsdet_accum=lad, **kw)
-            return rows, lad
+        def leftover(rows, h):      # the final Linear + the stand-alone kernel
+            lin = net.final_layer
+            params = torch.nn.functional.linear(h[:, :lin.in_features], lin.weight, lin.bias)
+            return self._coupling_kernel(rows, params, inverse)
 
-        body = n - n % ops.FUSED_ROWS
-        if body == n:
-            outputs, logabsdet = fused(inputs, hidden, total)
-        else:
-            # the < 32 leftover rows go through the final Linear + the stand-alone kernel
-            out_a, lad_a = fused(inputs[:body], hidden[:body], None if total is None else total[:body])
-            tail_params = torch.nn.functional.linear(hidden[body:, :net.final_layer.in_features],
-                                                     net.final_layer.weight, net.final_layer.bias)
-            out_b, lad_b = self._coupling_kernel(inputs[body:].contiguous(), tail_params, inverse)
-            outputs = torch.cat((out_a, out_b))
-            if total is None:
-                logabsdet = torch.cat((lad_a, lad_b))
-            else:
-                total[body:] += lad_b
-                logabsdet = total
+        outputs, logabsdet = fused_rq.apply(inputs, hidden, chunks, mode, kw, total, leftover)
         if self.unconditional_transform is not None:
             if not inverse:
                 identity_split, logabsdet_identity = self.unconditional_transform(identity_split, context)
@@ -578,20 +538,18 @@ class _FusedRQCouplingFunction(torch.autograd.Function):
             if pad:       # whole 128-row rounds: zero rows (inside every spline's interval) that get zero upstream gradients
                 x = torch.cat((x, x.new_zeros(pad, x.shape[1])))
             hidden = layer._hidden_for_fused(x, None, None, 64)
-            kw = layer._fused_kw(net)
-            rows, lad = x, None
             # (raw weights: only a conditioner that IS 64 wide -- a narrower one is zero-padded by the packed fragments)
             k8 = net.hidden_features == ops.FUSED_HIDDEN and ops.fused_linear_supported(
                 x.shape[0], x.shape[1], min(layer.num_transform_features, ops.FUSED_DT), net.hidden_features,
                 layer.num_bins, layer.tails)
             lin = net.final_layer
-            for w_frag, w_un, bias_pad, _, cols, rows_slice in layer._train_chunks(x.device):
-                if k8:    # the hand-scheduled north-star kernel takes the f32 weights as they are
-                    rows, lad = ops.rq_spline_fused_linear(rows, hidden, lin.weight[rows_slice], lin.bias[rows_slice], cols,
-                                                           logabsdet_accum=lad, inverse=False, **kw)
-                else:
-                    rows, lad = ops.rq_spline_fused_general(rows, hidden, w_frag, w_un, bias_pad, cols,
-                                                            tails=layer.tails, logabsdet_accum=lad, inverse=False, **kw)
+            if k8:        # the hand-scheduled north-star kernel takes the f32 weights as they are
+                chunks = [(lin.weight[rows_slice], lin.bias[rows_slice], cols)
+                          for _, _, _, _, cols, rows_slice in layer._train_chunks(x.device)]
+            else:
+                chunks = [(w_frag, w_un, bias_pad, cols) for w_frag, w_un, bias_pad, _, cols, _ in layer._train_chunks(x.device)]
+            mode = "k8" if k8 else "general"
+            rows, lad = fused_rq.run_chunks(x, hidden, chunks, mode, layer._fused_forward_kw(net, mode, False))
         ctx.layer, ctx.n = layer, n
         # The backward re-packs and reads the LIVE weights (they are not copied): saving the parameters makes autograd's
         # version check refuse a backward after an optimizer step / in-place edit between forward and backward, exactly

@@ -449,7 +449,7 @@ def test_runtime_caches_do_not_travel_with_deepcopy_or_pickle():
     t = T.PiecewiseRationalQuadraticCouplingTransform(utils.create_alternating_binary_mask(8), _net, num_bins=4)
     pack = ops.DevicePack(torch.device("cpu"))
     pack.prepare.append(lambda: None)                  # a local closure, as the real plans hold
-    t._train_pack = [t.transform_net.final_layer.weight, 0, pack, []]
+    t._train_pack = [0, pack, [], t.transform_net.final_layer.weight, None]
     t._tail_image = [0, pack, (torch.zeros(3),)]
     t.transform_net._hip_image = [0, _hip.PackJob(), (torch.zeros(3),)]
     t.transform_net._hip_packed = ((1, 2), torch.zeros(5))
