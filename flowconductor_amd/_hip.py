@@ -121,6 +121,10 @@ SIGNATURES = {
     "fc_affine_coupling_resnet": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "fc_made_inverse": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, ctypes.POINTER(RQConfig), _P],
     "fc_made_inverse_context": [_P] * 15 + [_I64, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(RQConfig), _P],
+    "fc_mog_log_prob": [_P, _P, _P, _I64, _I32, _I32, _F, _I32, _P],
+    "fc_mog_log_prob_backward": [_P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _P],
+    "fc_made_mog_sample": [_P] * 11 + [_I64, _I32, _I32, _I32, _F, _P],
+    "fc_made_mog_sample_context": [_P] * 15 + [_I64, _I32, _I32, _I32, _I32, _F, _P],
     "fc_resnet_hidden_packed": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, ctypes.c_float, _P],
     "fc_resnet_hidden_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P],
     "fc_resnet_hidden_backward_accum": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P],

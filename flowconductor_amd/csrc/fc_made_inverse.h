@@ -34,6 +34,7 @@
 #include "fc_device.h"
 #include "fc_lane.h"
 #include "fc_math.h"
+#include "fc_mog_op.h"
 #include "fc_rq_op.h"
 #include "fc_split.h"
 #include "../../include/flowcon_hip.h"
@@ -74,15 +75,31 @@ struct MadeInvCtxArgs : MadeInvArgs {
   int C;
 };
 
+// the sampler of a mixture-of-Gaussians MADE (FC_MADE_MOG, nn/nde/made.py:355-388): z is the normal noise, `uniform` picks the
+// component of every column, P = 3 c parameters per dim; the [N] output is the log-density of the draw
+struct MadeMogNoise {
+  const float* uniform;     // [N, D]
+  float eps;                // std = softplus(ustd) + eps
+  int c;                    // components, <= 16
+};
+struct MadeMogArgs : MadeInvArgs, MadeMogNoise {};
+struct MadeMogCtxArgs : MadeInvCtxArgs, MadeMogNoise {};
+constexpr int kMiMog = -1;  // kKind of the mixture column step (the host's FC_MADE_MOG)
+
 // kind: 0 = affine (P = 2: unconstrained scale, shift), 1 = rational-quadratic spline with a run-time bin count (parameters read
 // from the strip as they are needed), 8 / 10 = the same with K = 8 / 10 bins fixed at compile time: the lane copies its 3K -/+ 1
-// parameters from its strip and runs the unrolled evaluation of the stand-alone kernels (RQOp<K>::eval_core, two-sided knot walk)
+// parameters from its strip and runs the unrolled evaluation of the stand-alone kernels (RQOp<K>::eval_core, two-sided knot walk);
+// kMiMog = mixture of Gaussians: inverse-CDF choice of a component on `uniform`, the draw, and the column's log mixture
+// density at the draw in the place of the log-determinant (fc_mog_op.h).  Its context enters the initial layer WITHOUT an
+// activation (nn/nde/made.py:274-281, unlike transforms/made.py)
 // BPW: 16-row blocks a wave carries together -- every pass is a serial chain (five layers, each row maximum -> split ->
 // products -> bias), so a second, independent block fills its waits, and each weight fragment read from LDS serves both
-// Args: MadeInvArgs, or MadeInvCtxArgs for the conditional form (the context code below is compiled for that one only)
+// Args: MadeInvArgs, or MadeInvCtxArgs for the conditional form (the context code below is compiled for that one only);
+// MadeMogArgs / MadeMogCtxArgs for the mixture sampler
 template <int NB, int K0S, int PT, int kKind, int BPW, class Args = MadeInvArgs>
 __global__ __launch_bounds__(kMiThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void made_inverse_kernel(Args a, RQOp<(kKind > 1 ? kKind : 0)> op) {
-  constexpr bool kCtx = std::is_same<Args, MadeInvCtxArgs>::value;
+  constexpr bool kCtx = std::is_base_of<MadeInvCtxArgs, Args>::value;
+  constexpr bool kMog = kKind == kMiMog;
   constexpr int kLayers = 1 + 2 * NB, kMiPS = mi_strip_row(PT);
   constexpr int kFrag0 = K0S * 4 * 2, kFragL = 2 * 4 * 2, kFrags = kFrag0 + 2 * NB * kFragL;
   extern __shared__ __attribute__((aligned(16))) unsigned char msm[];
@@ -213,6 +230,14 @@ __global__ __launch_bounds__(kMiThreads) __attribute__((amdgpu_waves_per_eu(2, 2
       lad_sum[b] = 0.f;
       znext[b] = zrow[b][0];
     }
+    [[maybe_unused]] const float* urow[BPW];
+    [[maybe_unused]] float unext[BPW];
+    if constexpr (kMog) {
+      FC_EACH_BLOCK {
+        urow[b] = a.uniform + (blk_of(grp, b) * 16 + s16) * D;
+        unext[b] = urow[b][0];
+      }
+    }
     // the block's context rows as one operand (k = 8 g + j < C), under their own row scale
     f16x8 ch[BPW][2], cl[BPW][2];
     float cun[BPW];
@@ -233,6 +258,13 @@ __global__ __launch_bounds__(kMiThreads) __attribute__((amdgpu_waves_per_eu(2, 2
       FC_EACH_BLOCK {
         zval[b] = znext[b];
         znext[b] = zrow[b][d + 1 < D ? d + 1 : d];      // next pass's input, one pass ahead
+      }
+      [[maybe_unused]] float uval[BPW];
+      if constexpr (kMog) {
+        FC_EACH_BLOCK {
+          uval[b] = unext[b];
+          unext[b] = urow[b][d + 1 < D ? d + 1 : d];
+        }
       }
       // the final-layer fragments of dim d: requested now, used after the hidden stack
       f16x8 fh[2][PT], fl[2][PT];
@@ -302,7 +334,7 @@ __global__ __launch_bounds__(kMiThreads) __attribute__((amdgpu_waves_per_eu(2, 2
         FC_EACH_BLOCK un[b] = make_operand(std::integral_constant<int, 2 * K0S>{}, xin[b], bh[b], bl[b]);
         layer(nts_c, std::integral_constant<int, K0S>{}, 0, bh, bl, acc);
         FC_EACH_BLOCK finish(nts_c, 0, un[b], acc[b], h[b]);
-        if constexpr (kCtx) add_context(nts_c, std::true_type{}, 0, h);
+        if constexpr (kCtx) add_context(nts_c, std::integral_constant<bool, !kMog>{}, 0, h);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
           FC_EACH_BLOCK {
@@ -386,6 +418,13 @@ __global__ __launch_bounds__(kMiThreads) __attribute__((amdgpu_waves_per_eu(2, 2
           const float sc = softplus_lean(p[0], 1.f) + 1e-3f;
           yv = div_lean(zmine - p[1], sc);
           ladv = -log_lean(sc);
+        } else if constexpr (kMog) {
+          float umine = uval[0];
+#pragma unroll
+          for (int b = 1; b < BPW; ++b) umine = g == b ? uval[b] : umine;
+          yv = mog_draw(p, a.c, a.eps, zmine, umine);
+          // (the density pass reuses the lane's strip row as scratch: the next pass rewrites it)
+          ladv = mog_log_density(strip + (g * 16 + s16) * kMiPS, a.c, a.eps, yv);
         } else {
           static_assert(kKind == 1 || PT == 2, "3K -/+ 1 parameters in two 16-row tiles");
           op.template eval_core<false>(p, zmine, yv, ladv, err);     // K static (8 / 10): the unrolled two-sided walk on the strip
@@ -434,7 +473,7 @@ constexpr bool mi_ctx_pairs_fit_registers(int nb, int k0s, int pt, int kind) {
 }
 
 template <class Args>
-constexpr bool kMiHasContext = std::is_same<Args, MadeInvCtxArgs>::value;
+constexpr bool kMiHasContext = std::is_base_of<MadeInvCtxArgs, Args>::value;
 // LDS of an instantiation; the context form carries its layers' images behind the strips
 template <class Args>
 constexpr size_t mi_total_lds(int nb, int k0s, int pt, int bpw) {
@@ -442,9 +481,16 @@ constexpr size_t mi_total_lds(int nb, int k0s, int pt, int bpw) {
 }
 
 // two blocks per wave need their registers: all forms without a context carry a pair; with one, see the .hip file's table
+// mixture sampler without a context: the pair spills (20-76 bytes of scratch per lane) with two k-steps of inputs (D > 32) and
+// one or two blocks at three parameter tiles, or three blocks at two (kernel-resource-usage, DESIGN.md "Mixture-of-Gaussians
+// MADE"); with a context the table above holds for it as well
+constexpr bool mi_mog_pairs_fit_registers(int nb, int k0s, int pt) {
+  return !(k0s == 2 && ((nb >= 1 && pt == 3) || (nb == 3 && pt == 2)));
+}
 template <class Args>
 constexpr bool mi_pairs_fit_registers(int nb, int k0s, int pt, int kind) {
-  return !kMiHasContext<Args> || mi_ctx_pairs_fit_registers(nb, k0s, pt, kind);
+  if (kMiHasContext<Args>) return mi_ctx_pairs_fit_registers(nb, k0s, pt, kind);
+  return kind != kMiMog || mi_mog_pairs_fit_registers(nb, k0s, pt);
 }
 
 template <int NB, int K0S, int PT, int kKind, int BPW, class Args>
@@ -533,6 +579,47 @@ hipError_t dispatch_made_inverse(const Args& a, const RQOp<0>& op, int num_block
     default: return hipErrorInvalidValue;
   }
 #undef FC_MI
+}
+
+// ---- the mixture-of-Gaussians sampler (fc_made_mog_sample.hip, fc_made_mog_sample_context.hip) ----------------------------
+// argument checks both entries share; hipSuccess with *run = false: nothing to do (n == 0)
+inline hipError_t made_mog_prepare(const void* normal, const void* uniform, const void* x, const void* logp, const void* hidden_frag,
+                                   const void* hidden_unscale, const void* hidden_bias, const void* final_frag,
+                                   const void* final_unscale, const void* final_bias, int64_t n, int32_t d, int32_t num_blocks,
+                                   int32_t c, bool* run) {
+  *run = false;
+  if (n < 0 || d < 1 || d > 64 || num_blocks < 0 || num_blocks > 3 || c < 1 || c > kMogMaxComponents) return hipErrorInvalidValue;
+  if (n % 16 != 0) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  if (!normal || !uniform || !x || !logp || !hidden_frag || !hidden_unscale || !hidden_bias || !final_frag || !final_unscale || !final_bias)
+    return hipErrorInvalidValue;
+  if ((((uintptr_t)hidden_frag | (uintptr_t)final_frag | (uintptr_t)final_bias) & 15u) != 0) return hipErrorInvalidValue;
+  *run = true;
+  return hipSuccess;
+}
+
+template <int NB, int K0S, class Args>
+hipError_t dispatch_made_mog_pt(const Args& a, hipStream_t s) {
+  const RQOp<0> op{};
+  switch ((a.P + 15) / 16) {      // 3 c parameters per dim: c <= 5, <= 10, <= 16
+    case 1: return launch_made_inverse<NB, K0S, 1, kMiMog>(a, op, s);
+    case 2: return launch_made_inverse<NB, K0S, 2, kMiMog>(a, op, s);
+    case 3: return launch_made_inverse<NB, K0S, 3, kMiMog>(a, op, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+template <class Args>
+hipError_t dispatch_made_mog(const Args& a, int num_blocks, hipStream_t s) {
+  const bool wide = a.D > 32;
+#define FC_MM(NBV) \
+  case NBV:        \
+    return wide ? dispatch_made_mog_pt<NBV, 2>(a, s) : dispatch_made_mog_pt<NBV, 1>(a, s);
+  switch (num_blocks) {
+    FC_MM(0) FC_MM(1) FC_MM(2) FC_MM(3)
+    default: return hipErrorInvalidValue;
+  }
+#undef FC_MM
 }
 
 }  // namespace fc

@@ -1,2 +1,2 @@
-from flowconductor_amd.nn import nets  # noqa: F401
+from flowconductor_amd.nn import nde, nets  # noqa: F401
 from flowconductor_amd.nn.nets import ConvResidualBlock, ConvResidualNet  # noqa: F401

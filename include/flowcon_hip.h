@@ -44,8 +44,9 @@ extern "C" {
  * FC_AFFINE_MAF_SOFTPLUS / FC_RQ_STREAMED_WEIGHTS; 3: the SPD-matrix entries fc_tril_pack, fc_matrix_diag,
  * fc_cholesky_outer(_backward), fc_cholesky and their FC_ERR_* bits).  The image-flow entries fc_squeeze / fc_conv1x1
  * were added under version 3: they change no existing entry, and a library without them fails to bind by name; the same
- * holds for the invertible-residual-block entries fc_iresnet_forward / fc_iresnet_inverse and for the conditional
- * device loop fc_made_inverse_context). */
+ * holds for the invertible-residual-block entries fc_iresnet_forward / fc_iresnet_inverse, for the conditional
+ * device loop fc_made_inverse_context and for the mixture-of-Gaussians entries fc_mog_log_prob(_backward) /
+ * fc_made_mog_sample(_context)). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -183,6 +184,43 @@ int fc_made_inverse_context(const float* z, const float* context, float* y, floa
                             const float* final_unscale, const float* final_bias, const int32_t* units_needed,
                             uint32_t* err_flag, int64_t n, int32_t d, int32_t context_features, int32_t num_blocks,
                             int32_t params_per_dim, int32_t kind, const fc_rq_config* cfg, void* stream);
+
+/* ---- mixture-of-Gaussians MADE (flowcon/nn/nde/made.py:284-426, distributions/mixture.py) --------------------------------- */
+/* Density on the final layer's output (nn/nde/made.py:328-353):
+ *   logp[i] = sum_j logsumexp_k( log_softmax(logit_ij.)_k - 0.5 (log 2 pi + 2 log std_ijk + ((x_ij - mean_ijk) / std_ijk)^2) ),
+ *   std = softplus(ustd) + epsilon.
+ * x [n, d]; params [n, d * 3c], per element the c components interleaved as (logit, mean, ustd) -- the reference's
+ * outputs.reshape(n, d, c, 3); logp [n], added onto with FC_RQ_ACCUMULATE_LOGABSDET in flags.  1 <= c <= 16, d >= 1, n >= 0.
+ * Maxima are taken before every exponential (logits and summed terms). */
+int fc_mog_log_prob(const float* x, const float* params, float* logp, int64_t n, int32_t d, int32_t c, float epsilon,
+                    int32_t flags, void* stream);
+
+/* Backward of fc_mog_log_prob: grad_x [n, d] and grad_params (layout of params) of sum_i grad_logp[i] logp[i]; the
+ * responsibilities are recomputed from x and params.  grad_params must not alias params. */
+int fc_mog_log_prob_backward(const float* grad_logp, const float* x, const float* params, float* grad_x, float* grad_params,
+                             int64_t n, int32_t d, int32_t c, float epsilon, void* stream);
+
+/* Ancestral sampler of a MixtureOfGaussiansMADE (nn/nde/made.py:355-388) as ONE kernel: fc_made_inverse with a mixture
+ * column step (3c parameters per dim).  Pass j picks component k = min{k : uniform_ij S < sum_{l <= k} e_l},
+ * e_l = exp(logit_l - max logit), S = sum_l e_l (the last component when no partial sum exceeds uniform_ij S) and sets
+ * x_ij = mean_k + std_k normal_ij; logp [n] = the log mixture density of the finished row (the sum over the columns of
+ * fc_mog_log_prob's term at the draw).  normal, uniform, x [n, d]; 1 <= c <= 16; the image, final-layer fragments
+ * (params_per_dim = 3c) and units_needed as for fc_made_inverse; n % 16 == 0, d <= 64, num_blocks <= 3. */
+#define FC_MADE_MOG 2
+int fc_made_mog_sample(const float* normal, const float* uniform, float* x, float* logp, const void* hidden_frag,
+                       const float* hidden_unscale, const float* hidden_bias, const void* final_frag, const float* final_unscale,
+                       const float* final_bias, const int32_t* units_needed, int64_t n, int32_t d, int32_t num_blocks, int32_t c,
+                       float epsilon, void* stream);
+
+/* The conditional form: context arguments as for fc_made_inverse_context, but the initial layer's context term enters
+ * WITHOUT an activation (nn/nde/made.py:274-281: temps = initial_layer(inputs) + context_layer(context)).  Shapes whose LDS
+ * image exceeds 160 KB (fc_made_inverse_context's rule with params_per_dim = 3c) return hipErrorInvalidValue. */
+int fc_made_mog_sample_context(const float* normal, const float* uniform, const float* context, float* x, float* logp,
+                               const void* hidden_frag, const float* hidden_unscale, const float* hidden_bias,
+                               const void* context_frag, const float* context_unscale, const float* context_bias,
+                               const void* final_frag, const float* final_unscale, const float* final_bias,
+                               const int32_t* units_needed, int64_t n, int32_t d, int32_t context_features, int32_t num_blocks,
+                               int32_t c, float epsilon, void* stream);
 
 /* Backward of fc_affine in the forward direction, per-sample parameters (coupling.py:234-252,
  * autoregressive.py:97-129 under torch.autograd): grad_x[n, cols[j]] = gy s; grad_params in the layout of
