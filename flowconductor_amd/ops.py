@@ -1844,6 +1844,42 @@ def lu_linear_autograd(inputs, lower, upper, bias, inverse=False):
     return _LULinearFunction.apply(_prep_2d(inputs), lower, upper, bias, inverse)
 
 
+class _UpperLinearFunction(torch.autograd.Function):
+    """``y = R x`` / ``y = R^-1 x`` with an upper-triangular ``R`` by the ``fc_linear`` kernel (the inverse is its back
+    substitution: ``LINEAR_LU_INVERSE`` with a unit lower factor); gradients by library GEMMs and one triangular solve
+    (qr.py:45-82 under autograd)."""
+
+    @staticmethod
+    def forward(ctx, inputs, upper, inverse):
+        with torch.no_grad():
+            outputs = upper_linear(inputs, upper, inverse=inverse)
+        ctx.save_for_backward(outputs if inverse else inputs, upper)
+        ctx.inverse = inverse
+        return outputs
+
+    @staticmethod
+    def backward(ctx, gy):
+        saved, upper = ctx.saved_tensors
+        if not ctx.inverse:
+            return gy @ upper, gy.T @ saved, None
+        # y = R^-1 x:  gx = R^-T gy;  dR = -gx^T y
+        gx = torch.linalg.solve_triangular(upper.T, gy.T, upper=False).T
+        return gx, -(gx.T @ saved), None
+
+
+def upper_linear(inputs, upper, bias=None, inverse=False):
+    """``R x + bias`` or the back substitution ``R^-1 (x - bias)`` for an upper-triangular ``R`` (``fc_linear``)."""
+    if not inverse:
+        return linear(inputs, upper, bias=bias, mode=LINEAR_DENSE)
+    eye = torch.eye(upper.shape[0], dtype=torch.float32, device=inputs.device)
+    return linear(inputs, upper, eye, bias, mode=LINEAR_LU_INVERSE)
+
+
+def upper_linear_autograd(inputs, upper, inverse=False):
+    """Upper-triangular linear map with an autograd node (training / differentiable sampling)."""
+    return _UpperLinearFunction.apply(_prep_2d(inputs), upper, inverse)
+
+
 def batchnorm_eval(inputs, mean, std, weight, bias, inverse=False):
     """Eval-mode BatchNorm map and its inverse (reference normalization.py:98-141)."""
     lib = _hip.load()
@@ -1995,6 +2031,92 @@ def householder_autograd(inputs, q_vectors, reverse=False):
         x = _prep_2d(inputs)
         return _HouseholderFunction.apply(x, q_vectors, bool(reverse)), x.new_zeros(x.shape[0])
     return householder(inputs, q_vectors, reverse=reverse), inputs.new_zeros(inputs.shape[0])
+
+
+HDH_MAX_REFLECTIONS = 4096      # ka + kb of fc_hdh_linear: the table of 2 / |q|^2 factors lives in LDS
+
+
+def _hdh_operands(device, d, q_a, q_b, scale, pre, post):
+    """(q_a, q_b, scale, pre, post) of ``fc_hdh_linear`` as device f32 tensors; an absent or empty sequence becomes
+    ``None`` (a NULL pointer with a count of 0)."""
+    qs = []
+    for q, name in ((q_a, "q_a"), (q_b, "q_b")):
+        if q is not None and q.shape[0] > 0:
+            q = _hip.dev_f32(q.detach().to(device), name)
+            if q.dim() != 2 or q.shape[1] != d:
+                raise ValueError("%s of shape %s does not match %d features" % (name, tuple(q.shape), d))
+        else:
+            q = None
+        qs.append(q)
+    if sum(q.shape[0] for q in qs if q is not None) > HDH_MAX_REFLECTIONS:
+        raise ValueError("flowconductor_amd: more than %d reflections in one fc_hdh_linear call" % HDH_MAX_REFLECTIONS)
+    vecs = []
+    for v, name in ((scale, "scale"), (pre, "pre"), (post, "post")):
+        if v is not None:
+            v = _hip.dev_f32(v.detach().to(device).reshape(-1), name)
+            if v.numel() != d:
+                raise ValueError("%s must have %d entries" % (name, d))
+        vecs.append(v)
+    if vecs[0] is None:
+        raise ValueError("scale is required")
+    return qs[0], qs[1], vecs[0], vecs[1], vecs[2]
+
+
+def hdh_linear(inputs, q_a, q_b, scale, pre=None, post=None, reverse_a=False, reverse_b=False):
+    """``post + H_b(scale * H_a(inputs - pre))`` in one launch (``fc_hdh_linear``): ``H_a`` / ``H_b`` the Householder
+    sequences ``q_a [Ka, D]`` / ``q_b [Kb, D]`` (``None`` or empty: no reflection), each in index order or reversed;
+    ``scale`` [D]; ``pre`` / ``post`` [D] or ``None``.  Both directions of ``SVDLinear`` (reference svd.py:56-95)."""
+    lib = _hip.load()
+    x = _rows(inputs)
+    _hip.require_no_grad(inputs, q_a, q_b, scale, pre, post)
+    n, d = x.shape
+    qa, qb, sc, pr, po = _hdh_operands(x.device, d, q_a, q_b, scale, pre, post)
+    y = torch.empty_like(x)
+    _call("fc_hdh_linear", lib.fc_hdh_linear, x.device, _hip.ptr(x), _hip.ptr(y), _hip.ptr(qa), _hip.ptr(qb), _hip.ptr(sc),
+          _hip.ptr(pr), _hip.ptr(po), n, d, 0 if qa is None else qa.shape[0], 0 if qb is None else qb.shape[0],
+          1 if reverse_a else 0, 1 if reverse_b else 0, _hip.stream_ptr(x.device))
+    return y
+
+
+class _HDHLinearFunction(torch.autograd.Function):
+    """``hdh_linear`` with its HIP backward kernel (``fc_hdh_linear_backward``): one node and one saved [N, D] tensor, the
+    OUTPUT -- every stage of the map is invertible, so the kernel recovers the intermediates by walking back."""
+
+    @staticmethod
+    def forward(ctx, inputs, q_a, q_b, scale, pre, post, reverse_a, reverse_b):
+        with torch.no_grad():
+            outputs = hdh_linear(inputs, q_a, q_b, scale, pre, post, reverse_a, reverse_b)
+        ctx.save_for_backward(outputs, q_a, q_b, scale, post)
+        ctx.has_pre, ctx.reverse = pre is not None, (reverse_a, reverse_b)
+        return outputs
+
+    @staticmethod
+    def backward(ctx, grad_outputs):
+        outputs, q_a, q_b, scale, post = ctx.saved_tensors
+        lib = _hip.load()
+        y = _hip.dev_f32(outputs, "outputs")
+        gy = _hip.dev_f32(grad_outputs, "grad_outputs")
+        n, d = y.shape
+        qa, qb, sc, _, po = _hdh_operands(y.device, d, q_a, q_b, scale, None, post)
+        ka, kb = (0 if q is None else q.shape[0] for q in (qa, qb))
+        gx = torch.empty_like(y)
+        gpar = torch.zeros(ka + kb + 3, d, dtype=torch.float32, device=y.device)    # gq_a | gq_b | gscale | gpre | gpost
+        gqa, gqb, gsc, gpr, gpo = gpar[:ka], gpar[ka:ka + kb], gpar[ka + kb], gpar[ka + kb + 1], gpar[ka + kb + 2]
+        _call("fc_hdh_linear_backward", lib.fc_hdh_linear_backward, y.device, _hip.ptr(y), _hip.ptr(gy), _hip.ptr(qa),
+              _hip.ptr(qb), _hip.ptr(sc), _hip.ptr(po), _hip.ptr(gx), _hip.ptr(gqa) if ka else None,
+              _hip.ptr(gqb) if kb else None, _hip.ptr(gsc), _hip.ptr(gpr) if ctx.has_pre else None,
+              _hip.ptr(gpo) if post is not None else None, n, d, ka, kb, 1 if ctx.reverse[0] else 0,
+              1 if ctx.reverse[1] else 0, _hip.stream_ptr(y.device))
+        return (gx, None if q_a is None else gqa.view_as(q_a), None if q_b is None else gqb.view_as(q_b), gsc.view_as(scale),
+                gpr if ctx.has_pre else None, None if post is None else gpo.view_as(post), None, None)
+
+
+def hdh_linear_autograd(inputs, q_a, q_b, scale, pre=None, post=None, reverse_a=False, reverse_b=False):
+    """``hdh_linear``; under autograd one ``_HDHLinearFunction`` node (one launch forward, one backward)."""
+    operands = (inputs, q_a, q_b, scale, pre, post)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands):
+        return _HDHLinearFunction.apply(_prep_2d(inputs), q_a, q_b, scale, pre, post, bool(reverse_a), bool(reverse_b))
+    return hdh_linear(inputs, q_a, q_b, scale, pre, post, reverse_a, reverse_b)
 
 
 class _PlanarFunction(torch.autograd.Function):

@@ -43,6 +43,8 @@ from flowconductor_amd.transforms.coupling import (  # noqa: F401
 from flowconductor_amd.transforms.adaptive_sigmoids import SumOfSigmoids  # noqa: F401
 from flowconductor_amd.transforms.linear import Linear, ScalarScale, ScalarShift  # noqa: F401
 from flowconductor_amd.transforms.lu import LULinear  # noqa: F401
+from flowconductor_amd.transforms.qr import QRLinear  # noqa: F401
+from flowconductor_amd.transforms.svd import SVDLinear  # noqa: F401
 from flowconductor_amd.transforms.no_analytic_inv import (  # noqa: F401
     MonotonicTransform,
     PlanarTransform,

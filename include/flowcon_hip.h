@@ -46,7 +46,7 @@ extern "C" {
  * were added under version 3: they change no existing entry, and a library without them fails to bind by name; the same
  * holds for the invertible-residual-block entries fc_iresnet_forward / fc_iresnet_inverse, for the conditional
  * device loop fc_made_inverse_context and for the mixture-of-Gaussians entries fc_mog_log_prob(_backward) /
- * fc_made_mog_sample(_context)). */
+ * fc_made_mog_sample(_context), and for the Householder-diagonal-Householder entries fc_hdh_linear(_backward)). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -585,6 +585,26 @@ int fc_planar_backward(const float* x, const float* grad_y, const float* grad_lo
  * What torch.autograd yields for orthogonal.py:144-194. */
 int fc_householder_backward(const float* y, const float* grad_y, const float* q, float* grad_x, float* grad_q,
                             int64_t n, int32_t d, int32_t num_transforms, int32_t reverse, void* stream);
+
+/* Householder - diagonal - Householder linear map with batch-shared parameters, one launch:
+ *   y = post + H_b( scale o H_a( x - pre ) )
+ * H_a / H_b: the reflections of q_a [ka, d] / q_b [kb, d] in index order (reverse_* != 0: last row first), the
+ * arithmetic of fc_householder; scale [d]; pre / post [d] or NULL (zeros).  ka and kb may be 0 (q NULL then);
+ * ka + kb <= 4096.  Both directions of SVDLinear (transforms/svd.py:56-95): forward a = orthogonal_2, b = orthogonal_1,
+ * scale = diagonal, post = bias; inverse a = orthogonal_1 reversed, b = orthogonal_2 reversed, scale = 1 / diagonal,
+ * pre = bias (subtracted before anything else).  The 2 / |q|^2 factors are computed once per workgroup. */
+int fc_hdh_linear(const float* x, float* y, const float* q_a, const float* q_b, const float* scale, const float* pre,
+                  const float* post, int64_t n, int32_t d, int32_t ka, int32_t kb, int32_t reverse_a, int32_t reverse_b,
+                  void* stream);
+
+/* Backward of fc_hdh_linear from its saved OUTPUT y (every stage is invertible: post comes off, H_b is walked back, the
+ * row is divided by scale, H_a is walked back).  grad_x [n, d] is written; grad_q_a [ka, d], grad_q_b [kb, d],
+ * grad_scale [d], grad_pre [d] (= -sum grad_x) and grad_post [d] (= sum grad_y) are ACCUMULATED (zero them first);
+ * grad_pre / grad_post may be NULL.  reverse_* as in the forward call. */
+int fc_hdh_linear_backward(const float* y, const float* grad_y, const float* q_a, const float* q_b, const float* scale,
+                           const float* post, float* grad_x, float* grad_q_a, float* grad_q_b, float* grad_scale,
+                           float* grad_pre, float* grad_post, int64_t n, int32_t d, int32_t ka, int32_t kb,
+                           int32_t reverse_a, int32_t reverse_b, void* stream);
 
 /* Element-wise middle of the backward of fc_sylvester with batch-shared parameters (no_analytic_inv/planar.py:144-166):
  * pre [n, d] = R1 Q^T z + b (recomputed by the caller), grad_act_inout [n, d] = gradient wrt tanh(pre) coming from the
