@@ -1,6 +1,7 @@
 from flowconductor_amd.transforms.autoregressive import (  # noqa: F401
     AutoregressiveTransform,
     MaskedAffineAutoregressiveTransform,
+    MaskedDeepSigmoidTransform,
     MaskedPiecewiseCubicAutoregressiveTransform,
     MaskedPiecewiseLinearAutoregressiveTransform,
     MaskedPiecewiseQuadraticAutoregressiveTransform,
@@ -40,7 +41,7 @@ from flowconductor_amd.transforms.coupling import (  # noqa: F401
     PiecewiseQuadraticCouplingTransform,
     PiecewiseRationalQuadraticCouplingTransform,
 )
-from flowconductor_amd.transforms.adaptive_sigmoids import SumOfSigmoids  # noqa: F401
+from flowconductor_amd.transforms.adaptive_sigmoids import DeepSigmoid, SumOfSigmoids  # noqa: F401
 from flowconductor_amd.transforms.linear import Linear, ScalarScale, ScalarShift  # noqa: F401
 from flowconductor_amd.transforms.lu import LULinear  # noqa: F401
 from flowconductor_amd.transforms.qr import QRLinear  # noqa: F401

@@ -12,6 +12,7 @@ from torch.nn import functional as F
 from flowconductor_amd import ops, options
 from flowconductor_amd.transforms import fused_rq
 from flowconductor_amd.transforms import made as made_module
+from flowconductor_amd.transforms.adaptive_sigmoids import DeepSigmoidModule
 from flowconductor_amd.transforms.base import Transform
 
 
@@ -473,6 +474,45 @@ class MaskedSumOfSigmoidsTransform(AutoregressiveTransform):
 
     def _elementwise_inverse(self, inputs, autoregressive_params):
         return ops.sum_of_sigmoids_autograd(inputs, autoregressive_params, self.n_sigmoids, inverse=True, offset=0.5)
+
+
+class MaskedDeepSigmoidTransform(AutoregressiveTransform):
+    """Deep-sigmoidal-flow AR layer (autoregressive/deep_sigmoid.py): the MADE emits ``3 * n_sigmoids`` raw values per
+    feature, evaluated as ``dsparams = made_output.view(N, features, 3S) / 5`` by a ``DeepSigmoidModule`` with
+    ``eps = 3e-5`` (the division happens inside the kernel).
+
+    The inverse deliberately extends the reference, whose ``_elementwise_inverse`` raises ``NotImplementedError("..")``:
+    the module's numerical inverse runs per pass of the host loop (or per column of the column-at-a-time path), which
+    gives ``inverse`` and ``Flow.sample``.  The one-kernel MADE inverse does not take this layer (``3S`` parameters per
+    dim are beyond what it holds)."""
+
+    class DeepSigmoidMadeModule(DeepSigmoidModule):
+        def forward(self, inputs, context=None):
+            raise NotImplementedError("Do not directly use this class.")
+
+    def __init__(self, features, hidden_features, n_sigmoids=30, context_features=None, num_blocks=2,
+                 use_residual_blocks=True, random_mask=False, activation=F.relu, dropout_probability=0.0,
+                 use_batch_norm=False):
+        self.features = features
+        self.n_sigmoids = n_sigmoids
+        made = _made(self, features, hidden_features, context_features, num_blocks, use_residual_blocks,
+                     random_mask, activation, dropout_probability, use_batch_norm)
+        super().__init__(made)
+        self.deep_sigmoid_module = self.DeepSigmoidMadeModule(n_sigmoids=n_sigmoids, eps=3e-5, num_inverse_iterations=50)
+
+    def _output_dim_multiplier(self):
+        return 3 * self.n_sigmoids
+
+    def _elementwise(self, inputs, autoregressive_params, inverse):
+        # (the column-at-a-time inverse hands over one column and its 3S parameters)
+        ds_params = autoregressive_params.view(inputs.shape[0], inputs.shape[1], self._output_dim_multiplier())
+        return self.deep_sigmoid_module._given_params(inputs, ds_params, inverse=inverse, divisor=5.0)
+
+    def _elementwise_forward(self, inputs, autoregressive_params):
+        return self._elementwise(inputs, autoregressive_params, inverse=False)
+
+    def _elementwise_inverse(self, inputs, autoregressive_params):
+        return self._elementwise(inputs, autoregressive_params, inverse=True)
 
 
 def _ar_divisor(net):

@@ -46,7 +46,8 @@ extern "C" {
  * were added under version 3: they change no existing entry, and a library without them fails to bind by name; the same
  * holds for the invertible-residual-block entries fc_iresnet_forward / fc_iresnet_inverse, for the conditional
  * device loop fc_made_inverse_context and for the mixture-of-Gaussians entries fc_mog_log_prob(_backward) /
- * fc_made_mog_sample(_context), and for the Householder-diagonal-Householder entries fc_hdh_linear(_backward)). */
+ * fc_made_mog_sample(_context), for the Householder-diagonal-Householder entries fc_hdh_linear(_backward) and for the
+ * deep-sigmoidal-flow entries fc_deep_sigmoid / fc_deep_sigmoid_backward(_rows)). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -555,6 +556,42 @@ int fc_sum_of_sigmoids(const float* x, float* y, const float* params, const int3
 int fc_sum_of_sigmoids_backward(const float* x, const float* params, const float* grad_y,
                                 const float* grad_logabsdet, float* grad_x, float* grad_params, int64_t n, int32_t d,
                                 int32_t n_sigmoids, float log_scale_postact, void* stream);
+
+/* ---- deep sigmoidal flow ----------------------------------------------------------------------- */
+/* Monotone bijector of Neural Autoregressive Flows with per-(sample, dim) raw rows [S raw_a | S raw_b | S raw_w]
+ * (rowlen = d_t * 3S).  With r = prescale * raw:  a_k = softplus(r_a_k) (1 - mollify) + mollify,
+ * b_k = r_b_k (1 - mollify), w = softmax(r_w), pre_k = a_k x + b_k, s = sum_k w_k sigmoid(pre_k),
+ * c = (1 - eps) s + eps / 2 (1 - c is formed from sum_k w_k sigmoid(-pre_k), not by subtraction):
+ *   y = log c - log(1 - c)
+ *   logabsdet = sum_j [logsumexp_k(log w_k + log a_k + logsigmoid(pre_k) + logsigmoid(-pre_k)) - 2 eps + log(1 - eps)
+ *                      - log c - log(1 - c)]          (the -2 eps is the reference's: its logsigmoid carries -eps)
+ * inverse != 0: x = f^-1(y) per element: |y| >= log((1 - eps / 2) / (eps / 2)) (the range of the map; eps as the
+ * float passed in) sets the outside-domain bit; otherwise a bracket doubled out from [-lim, lim], a safeguarded Newton
+ * search on f(x) = y (at most `inverse_iterations` steps), two closing Newton steps; logabsdet = -logabsdet_f(x); a
+ * non-finite result sets the non-finite bit.  prescale multiplies every raw value first (1 for DeepSigmoid, 0.2 for the
+ * MADE form).  cols / shared_params / lad_mode / err_flag as for fc_sum_of_sigmoids.
+ * Replaces DeepSigmoidModule.forward_given_params (adaptive_sigmoids.py:177-210) and
+ * MaskedDeepSigmoidTransform._elementwise_forward (autoregressive/deep_sigmoid.py:69-72); the reference has no inverse. */
+int fc_deep_sigmoid(const float* x, float* y, const float* params, const int32_t* cols, float* logabsdet,
+                    uint32_t* err_flag, int64_t n, int32_t d, int32_t d_t, int32_t n_sigmoids, int32_t inverse,
+                    int32_t inverse_iterations, float inverse_lim, float mollify, float eps, float prescale,
+                    int32_t shared_params, int32_t lad_mode, void* stream);
+
+/* Backward of fc_deep_sigmoid in the forward direction, all d columns transformed: grad_x [n, d] and grad_raw from
+ * grad_y [n, d] and grad_logabsdet [n] (NULL = zeros); closed-form derivatives, the chain through softplus, the mollifier,
+ * the softmax and the pre-scale included.
+ * shared_params == 0: raw and grad_raw are [n, d * 3S].
+ * shared_params != 0: raw is one row [d * 3S]; its gradient is summed over the batch inside the kernel (workgroup
+ * partial sums, then a second kernel: no atomics, bit-identical from run to run).  grad_raw must then hold
+ * (1 + fc_deep_sigmoid_backward_rows(n, d, S)) * d * 3S floats: the first d * 3S receive the gradient, the rest is
+ * workspace.  Returns hipErrorInvalidConfiguration when fc_deep_sigmoid_backward_rows is 0. */
+int fc_deep_sigmoid_backward(const float* x, const float* raw, const float* grad_y, const float* grad_logabsdet,
+                             float* grad_x, float* grad_raw, int64_t n, int32_t d, int32_t n_sigmoids, float mollify,
+                             float eps, float prescale, int32_t shared_params, void* stream);
+
+/* Workspace rows of the shared-row mode above (a count, not an error code); 0: the row does not fit the reduction's
+ * LDS plan, expand it to per-sample rows instead. */
+int fc_deep_sigmoid_backward_rows(int64_t n, int32_t d, int32_t n_sigmoids);
 
 /* ---- row-per-wavefront bijectors with dense parameters (d <= 512) ------------------------------ */
 /* K Householder reflections out -= (out.q_k)(2/|q_k|^2) q_k, k = 0..K-1 (reverse != 0: K-1..0).

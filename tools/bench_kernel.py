@@ -106,6 +106,26 @@ def main():
         iters = -50 if which == "sos_inv_bisect" else 50
         fn = lambda: ops.sum_of_sigmoids(x, params, ns, inverse=which != "sos_fwd", iterations=iters)  # noqa: E731
         name = "fc_sum_of_sigmoids"
+    elif which in ("ds_fwd", "ds_inv", "ds_bwd"):
+        # deep sigmoidal flow (S = 30: 90 raw values per dim, the MADE form's pre-scale), D = 8 all transformed
+        d, d_t, ns = 8, 8, 30
+        p = 3 * ns
+        x = torch.randn(n, d, device=dev) * 2.0
+        params = torch.randn(n, d * p, device=dev) * 5.0
+        kw = dict(eps=3e-5, prescale=0.2, iterations=50)
+        if which == "ds_bwd":
+            gy, gl = torch.randn(n, d, device=dev), torch.randn(n, device=dev)
+            xg, pg = x.clone().requires_grad_(True), params.clone().requires_grad_(True)
+
+            def fn():
+                y, lad = ops.deep_sigmoid_autograd(xg, pg, ns, **kw)
+                torch.autograd.grad((y, lad), (xg, pg), (gy, gl))
+            name = "fc_deep_sigmoid_backward"
+        else:
+            if which == "ds_inv":
+                x = ops.deep_sigmoid(x, params, ns, **kw)[0]
+            fn = lambda: ops.deep_sigmoid(x, params, ns, inverse=which == "ds_inv", **kw)  # noqa: E731
+            name = "fc_deep_sigmoid"
     elif which == "hidden":
         from flowconductor_amd.nn import nets
         p = 0
