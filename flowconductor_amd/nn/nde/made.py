@@ -16,7 +16,7 @@ import torch
 from torch.nn import functional as F
 
 from flowconductor_amd import ops, options
-from flowconductor_amd.transforms.made import MADE
+from flowconductor_amd.transforms.made import MADE, pad_rows
 
 
 class MixtureOfGaussiansMADE(MADE):
@@ -162,35 +162,15 @@ class MixtureOfGaussiansMADE(MADE):
                                                                       3 * self.num_mixture_components)))
 
         key = (normal.shape[1], None if context is None else context.shape[1]) + ops.structure_key(self)
-        return ops.static_memo(self, "_fc_mog_sample_ok", key, structure_ok) and not ops.has_hooks(self)
+        return ops.static_memo(self, "mog_sample_ok", key, structure_ok) and not ops.has_hooks(self)
 
     def _sample_device_loop(self, normal, uniform, context):
-        per_dim = 3 * self.num_mixture_components
-        layers = [self.initial_layer, self.final_layer] + [lin for block in self.blocks for lin in block.linear_layers]
-        key = ops.cache_key(*[t for lin in layers for t in (lin.weight, lin.bias)])
-        cache = self.__dict__.get("_fc_made_inverse_pack")
-        if cache is None or cache[0] != key:
-            cache = self.__dict__["_fc_made_inverse_pack"] = (key, ops.pack_made_inverse(self, self.features, per_dim))
+        pack, context_pack = self.inverse_packs(3 * self.num_mixture_components, context is not None)
         n = normal.shape[0]
-        pad = -n % ops.HIDDEN_ROWS
-
-        def rows(t):
-            t = t.detach().contiguous()
-            return t if pad == 0 else F.pad(t, (0, 0, 0, pad))
-
-        ctx_rows = ctx_pack = None
-        if context is not None:
-            ctx_layers = [self.context_layer] + [block.context_layer for block in self.blocks]
-            ctx_key = ops.cache_key(*[t for lin in ctx_layers for t in (lin.weight, lin.bias)])
-            ctx_cache = self.__dict__.get("_fc_made_inverse_context_pack")
-            if ctx_cache is None or ctx_cache[0] != ctx_key:
-                ctx_cache = self.__dict__["_fc_made_inverse_context_pack"] = (
-                    ctx_key, ops.pack_made_inverse_context(self, self.features, per_dim))
-            ctx_rows, ctx_pack = rows(context), ctx_cache[1]
-        draws, log_prob = ops.made_mog_sample(rows(normal), rows(uniform), cache[1], len(self.blocks),
-                                              self.num_mixture_components, self.epsilon, context=ctx_rows,
-                                              context_pack=ctx_pack)
-        return (draws, log_prob) if pad == 0 else (draws[:n], log_prob[:n])
+        draws, log_prob = ops.made_mog_sample(
+            pad_rows(normal), pad_rows(uniform), pack, len(self.blocks), self.num_mixture_components, self.epsilon,
+            context=None if context is None else pad_rows(context), context_pack=context_pack)
+        return (draws, log_prob) if draws.shape[0] == n else (draws[:n], log_prob[:n])
 
     def _sample_host_loop(self, normal, uniform, context):
         """D conditioner passes, pass d fixing column d with the selection rule of ``_sample_from_noise`` on the same

@@ -46,7 +46,7 @@ class ResidualBlock(nn.Module):
         return inputs + h
 
 
-class ResidualNet(ops.RuntimeCaches, nn.Module):
+class ResidualNet(nn.Module):
     """Linear -> num_blocks x ResidualBlock -> Linear, for 1-dim feature vectors."""
 
     def __init__(self, in_features, out_features, hidden_features, context_features=None,
@@ -80,9 +80,8 @@ class ResidualNet(ops.RuntimeCaches, nn.Module):
             # inference on a HIP device: hidden stack in fc_resnet_hidden, the < 16 leftover rows on PyTorch
             n = inputs.shape[0]
             body = n - n % 16
-            ids = getattr(self, "_all_cols", None)
-            if ids is None or ids.device != inputs.device or ids.numel() != inputs.shape[1]:
-                ids = self._all_cols = torch.arange(inputs.shape[1], dtype=torch.int32, device=inputs.device)
+            ids = ops.memo(self, "all_cols", (inputs.shape[1], inputs.device),
+                           lambda: torch.arange(inputs.shape[1], dtype=torch.int32, device=inputs.device))
             hidden = self.hidden_hip(inputs[:body], ids, None if context is None else context[:body])
             if body < n:
                 hidden = torch.cat((hidden, self.hidden_padded(inputs[body:],
@@ -171,12 +170,10 @@ class ResidualNet(ops.RuntimeCaches, nn.Module):
         from flowconductor_amd import ops
 
         width = ops.general_hidden_width(self.hidden_features)
-        key = ops.cache_key(*self._param_list(), extra=("wide", width))
-        if getattr(self, "_hip_packed_wide", None) is None or self._hip_packed_wide[0] != key:
-            self._hip_packed_wide = (key, ops.pack_resnet_hidden_wide(self, width))
+        packed = ops.memo(self, "hip_packed_wide", ops.cache_key(*self._param_list(), extra=("wide", width)),
+                          lambda: ops.pack_resnet_hidden_wide(self, width))
         act = ops.activation_code(self.blocks[0].activation) if len(self.blocks) else (ops.ACT_RELU, 0.0)
-        return ops.resnet_hidden_wide(rows, id_cols, self._hip_packed_wide[1], self.initial_layer.in_features,
-                                      len(self.blocks), width, act)
+        return ops.resnet_hidden_wide(rows, id_cols, packed, self.initial_layer.in_features, len(self.blocks), width, act)
 
     def hip_hidden_backward_supported(self):
         """True when ``fc_resnet_hidden_backward`` covers this net: hidden <= 64, <= 2 blocks, ReLU, no context, no batch
@@ -204,22 +201,22 @@ class ResidualNet(ops.RuntimeCaches, nn.Module):
     def _apply(self, fn, *args, **kwargs):
         # .to() / .cuda() / .float(): new storages (and possibly new Parameter objects)
         out = super()._apply(fn, *args, **kwargs)
-        self.__dict__.pop("_fc_param_list", None)
+        ops.drop_param_list(self)
         return out
 
     def hidden_backward_packed(self):
         from flowconductor_amd import ops
 
         # persistent device-side pack plan (one launch per refresh); rebuilt when the parameter storages moved
-        plan = self.hidden_backward_plan()
-        plan[1].refresh()
-        return plan[2]
+        pack, packed = self.hidden_backward_plan()
+        pack.refresh()
+        return packed
 
     def hidden_backward_plan(self):
-        """[where, DevicePack, packed] of the training-time images (not refreshed here)."""
+        """(DevicePack, packed) of the training-time images (not refreshed here)."""
         from flowconductor_amd import ops
 
-        return ops.device_plan(self, "_hip_packed_bwd", self._storage_key(),
+        return ops.device_plan(self, "hip_packed_bwd", self._storage_key(),
                                lambda: ops.device_pack_resnet_hidden_backward(self))
 
     def hidden_padded(self, inputs, context=None):
@@ -234,10 +231,9 @@ class ResidualNet(ops.RuntimeCaches, nn.Module):
         lin = self.final_layer
         if lin.in_features == 64:
             return lin(hidden64)
-        key = ops.cache_key(lin.weight)
-        if getattr(self, "_final_padded", None) is None or self._final_padded[0] != key:
-            self._final_padded = (key, F.pad(lin.weight.detach(), (0, 64 - lin.in_features)))
-        return F.linear(hidden64, self._final_padded[1], lin.bias)
+        weight = ops.memo(self, "final_padded", ops.cache_key(lin.weight),
+                          lambda: F.pad(lin.weight.detach(), (0, 64 - lin.in_features)))
+        return F.linear(hidden64, weight, lin.bias)
 
     def hidden_hip(self, rows, id_cols, context=None):
         """h [N, 64] from FULL input rows + the identity column indices (N a multiple of 16) [+ context rows]; for a
@@ -254,14 +250,12 @@ class ResidualNet(ops.RuntimeCaches, nn.Module):
             if self.training and self.hip_hidden_backward_supported():
                 w_frag, _, w_un, bias_acc, _ = self.hidden_backward_packed()
                 return ops.resnet_hidden_packed(rows, id_cols, (w_frag, w_un, bias_acc), in_features, len(self.blocks), act)
-            plan = ops.device_plan(self, "_hip_image", self._storage_key(),
-                                   lambda: ops.device_pack_resnet_hidden_forward(self))
-            plan[1].refresh()
-            return ops.resnet_hidden_packed(rows, id_cols, plan[2], in_features, len(self.blocks), act)
-        key = ops.cache_key(*self._param_list())
-        if getattr(self, "_hip_packed", None) is None or self._hip_packed[0] != key:
-            self._hip_packed = (key, ops.pack_resnet_hidden(self))
-        return ops.resnet_hidden(rows, id_cols, self._hip_packed[1], in_features, len(self.blocks), context, act)
+            pack, image = ops.device_plan(self, "hip_image", self._storage_key(),
+                                          lambda: ops.device_pack_resnet_hidden_forward(self))
+            pack.refresh()
+            return ops.resnet_hidden_packed(rows, id_cols, image, in_features, len(self.blocks), act)
+        packed = ops.memo(self, "hip_packed", ops.cache_key(*self._param_list()), lambda: ops.pack_resnet_hidden(self))
+        return ops.resnet_hidden(rows, id_cols, packed, in_features, len(self.blocks), context, act)
 
 
 class ConvResidualBlock(nn.Module):

@@ -13,6 +13,10 @@ import numpy as np
 import torch
 
 from flowconductor_amd import _hip, options
+# the run-time caches, re-exported: call sites say ``ops.memo`` / ``ops.cache_key`` / ``ops.invalidate_hip_caches``
+from flowconductor_amd.runtime_cache import (  # noqa: F401
+    buffer_list, cache_key, cached, device_plan, drop_param_list, has_hooks, invalidate_hip_caches, memo,
+    module_list, param_list, static_memo, structure_key)
 
 
 class InverseNotAvailable(Exception):
@@ -169,111 +173,6 @@ def _aligned16(t):
     """The matrix-core kernels move rows as 16-byte pieces: a contiguous view that starts off a 16-byte boundary
     (``data[1:]`` with a feature count that is not a multiple of 4) is copied to a fresh allocation first."""
     return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
-# ---- packed-weight caches ---------------------------------------------------------------------------------------
-#
-# Layers cache kernel-layout copies of their weights (pre-masked, zero-padded, folded matrices), keyed on the
-# parameters' version counters and storage pointers.  In-place writes THROUGH ``.data`` (``p.data.copy_(ema)``,
-# ``p.data.clamp_()``, some checkpoint loaders) change neither; ``invalidate_hip_caches()`` bumps an epoch that is
-# part of every key.  ``nn.Module.train()`` of this package's modules calls it, so a cache never survives a switch
-# into or out of training mode; after ``.data`` surgery on an eval-mode model call it yourself.
-
-_cache_epoch = 0
-
-
-def invalidate_hip_caches():
-    """Drop every packed-weight cache of this package (re-packed on the next call that needs them)."""
-    global _cache_epoch
-    _cache_epoch += 1
-
-
-def cache_epoch():
-    return _cache_epoch
-
-
-_paranoid_tick = 0
-
-
-def cache_key(*tensors, extra=()):
-    """Key of a packed copy of ``tensors``: version counter, storage pointer and device of each + the epoch.  With
-    ``options.paranoid_caches`` no two keys are equal: every lookup misses and re-packs."""
-    global _paranoid_tick
-    if options.get("paranoid_caches"):
-        _paranoid_tick += 1
-        return (("paranoid", _paranoid_tick),) + (_cache_epoch,) + tuple(extra)
-    return tuple((t._version, t.data_ptr(), t.device) for t in tensors) + (_cache_epoch,) + tuple(extra)
-
-
-# Attributes in which this package's modules keep run-time state derived from their parameters (kernel-layout weight
-# images, DevicePack plans with raw device pointers, index tensors, memo lists).  None of it is model state: it is
-# rebuilt on demand and must not travel with ``copy.deepcopy`` / ``pickle`` / ``torch.save(module)``.
-RUNTIME_CACHE_ATTRS = frozenset((
-    "_hip_packed", "_hip_packed_wide", "_hip_packed_bwd", "_hip_image", "_final_padded", "_tail_image", "_train_pack",
-    "_packed", "_masked_final", "_mm_cache", "_dense_cache", "_sp_cache", "_all_cols", "_ctx_cols", "_cols_cache",
-    "_id_cols_cache", "_fc_param_list", "_fc_module_list", "_fc_static_ok", "_conv1x1_cache", "_ires_image",
-    "_ires_iters", "_fc_made_inverse_pack", "_fc_made_inverse_context_pack", "_fc_device_loop_ok",
-    "_fc_device_loop_context_ok", "_fc_mog_sample_ok"))
-
-
-class RuntimeCaches:
-    """Mixin (before ``nn.Module`` in the bases): ``copy.deepcopy``, ``pickle`` and ``torch.save`` of the module see the
-    run-time caches of ``RUNTIME_CACHE_ATTRS`` as ``None`` -- a copy starts cold and re-packs from ITS OWN parameters; a
-    checkpoint of the whole module holds parameters and buffers only (``fc_pack_job`` structs carry raw device
-    pointers and cannot be pickled at all)."""
-
-    def __getstate__(self):
-        state = dict(super().__getstate__())
-        for name in RUNTIME_CACHE_ATTRS:
-            if state.get(name) is not None:
-                state[name] = None
-        return state
-
-
-def param_list(module):
-    """``tuple(module.parameters())`` memoised on the module (walking the module tree on every call is a third of the
-    per-layer host time of a small batch) together with WHERE each parameter hangs: the memo is valid only while every slot
-    still holds the same Parameter object (``lin.weight = nn.Parameter(...)``, ``load_state_dict(assign=True)`` and late
-    parametrizations replace objects without touching versions or pointers of the orphans) and the cache epoch stands;
-    modules drop it in ``_apply`` (.to / .cuda / .float)."""
-    memo = module.__dict__.get("_fc_param_list")
-    if memo is None or memo[0] != _cache_epoch or not all(m._parameters.get(n) is p for m, n, p in memo[2]):
-        slots = tuple((m, n, p) for m in module.modules() for n, p in m._parameters.items() if p is not None)
-        memo = module.__dict__["_fc_param_list"] = (_cache_epoch, tuple(module.parameters()), slots)
-    return memo[1]
-
-
-def static_memo(module, slot, key, compute):
-    """``compute()`` memoised on ``module`` under ``slot`` for as long as ``key`` and the cache epoch stand -- for the parts of
-    a fast-path predicate that only depend on how the module is built (layer types, widths, activations, training flag):
-    re-deriving them on every call was a fifth of the host time of a small batch."""
-    memo = module.__dict__.get(slot)
-    full = (_cache_epoch,) + tuple(key)
-    if memo is None or memo[0] != full:
-        memo = module.__dict__[slot] = (full, compute())
-    return memo[1]
-
-
-def structure_key(net):
-    """The cheap MUTABLE inputs of a conditioner's fast-path predicate, for ``static_memo`` keys: per residual block the
-    identity of its activation, its dropout probability and its own training flag (``block.train()`` / a swapped
-    activation / ``dropout.p = 0.1`` after the first call must re-derive the predicate)."""
-    blocks = getattr(net, "blocks", ())
-    return (net.training, id(getattr(net, "activation", None))) + tuple(
-        (id(getattr(b, "activation", None)), getattr(getattr(b, "dropout", None), "p", 0.0), b.training) for b in blocks)
-
-
-def has_hooks(module):
-    """True when ``module`` or a sub-module carries forward (pre-)hooks (old-style weight_norm refreshes ``weight``
-    in one): the fast paths read the weights directly and never go through ``__call__``, so they step aside.
-    (The sub-module list is kept on the module and rebuilt when the cache epoch moves or a child is added / removed:
-    walking ``modules()`` on every call was the largest single item of the per-layer host time.)"""
-    memo = module.__dict__.get("_fc_module_list")
-    count = len(module._modules)
-    if memo is None or memo[0] != _cache_epoch or memo[1] != count:
-        memo = (_cache_epoch, count, tuple(module.modules()))
-        module.__dict__["_fc_module_list"] = memo
-    return any(m._forward_hooks or m._forward_pre_hooks for m in memo[2])
 
 
 LAD_STORE, LAD_ACCUMULATE, LAD_STORE_NEG, LAD_ACCUMULATE_NEG = 0, 1, 2, 3
@@ -885,19 +784,6 @@ def device_pack_made_affine(made, features):
         pack.sources += [lin.weight, lin.bias]
     pack.prepare.append(stage)
     return pack, image
-
-
-def device_plan(owner, slot, where, build):
-    """The device pack plan ``[where, pack, packed, ...]`` that ``owner`` keeps in attribute ``slot``.  Its jobs hold raw
-    device pointers, so it is rebuilt (``build()`` -> ``(pack, packed, ...)``) whenever ``where`` -- the storages it reads
-    and whatever else it was built around -- differs from the one it was built for.  An object that ``where`` names by
-    ``id()`` must be returned by ``build()`` into the tail of the plan, so that the id cannot be reused while the plan
-    lives.  The caller refreshes ``plan[1]``."""
-    plan = getattr(owner, slot, None)
-    if plan is None or plan[0] != where:
-        plan = [where, *build()]
-        setattr(owner, slot, plan)
-    return plan
 
 
 MADE_AFFINE, MADE_RQ = 0, 1

@@ -127,7 +127,7 @@ class AutoregressiveTransform(Transform):
                     and code is not None and code[0] == ops.ACT_RELU and form[1] <= 48
                     and net.final_layer.out_features == form[1] * inputs.shape[1])
 
-        return (ops.static_memo(self, "_fc_device_loop_ok", (inputs.shape[1],) + ops.structure_key(net), structure_ok)
+        return (ops.static_memo(self, "device_loop_ok", (inputs.shape[1],) + ops.structure_key(net), structure_ok)
                 and not ops.has_hooks(net))
 
     def _device_loop_context_ok(self, inputs, context):
@@ -154,35 +154,17 @@ class AutoregressiveTransform(Transform):
                     and ops.made_inverse_context_fits(inputs.shape[1], len(net.blocks), form[1]))
 
         key = (inputs.shape[1], context.shape[1]) + ops.structure_key(net)
-        return ops.static_memo(self, "_fc_device_loop_context_ok", key, structure_ok) and not ops.has_hooks(net)
+        return ops.static_memo(self, "device_loop_context_ok", key, structure_ok) and not ops.has_hooks(net)
 
     def _inverse_device_loop(self, inputs, context=None):
         net = self.autoregressive_net
         kind, per_dim, rq = self._device_loop_form()
-        features = inputs.shape[1]
-        layers = [net.initial_layer, net.final_layer] + [lin for block in net.blocks for lin in block.linear_layers]
-        key = ops.cache_key(*[t for lin in layers for t in (lin.weight, lin.bias)])
-        cache = self.__dict__.get("_fc_made_inverse_pack")
-        if cache is None or cache[0] != key:
-            cache = self.__dict__["_fc_made_inverse_pack"] = (key, ops.pack_made_inverse(net, features, per_dim))
+        pack, context_pack = net.inverse_packs(per_dim, context is not None)
         n = inputs.shape[0]
-        pad = -n % ops.HIDDEN_ROWS
-        rows = inputs if pad == 0 else torch.nn.functional.pad(inputs, (0, 0, 0, pad))
-        if context is None:
-            outputs, logabsdet = ops.made_inverse(rows, cache[1], len(net.blocks), per_dim, kind, rq)
-        else:
-            ctx_layers = [net.context_layer] + [block.context_layer for block in net.blocks]
-            ctx_key = ops.cache_key(*[t for lin in ctx_layers for t in (lin.weight, lin.bias)])
-            ctx_cache = self.__dict__.get("_fc_made_inverse_context_pack")
-            if ctx_cache is None or ctx_cache[0] != ctx_key:
-                ctx_cache = self.__dict__["_fc_made_inverse_context_pack"] = (
-                    ctx_key, ops.pack_made_inverse_context(net, features, per_dim))
-            ctx_rows = context.detach().contiguous()
-            if pad:
-                ctx_rows = torch.nn.functional.pad(ctx_rows, (0, 0, 0, pad))
-            outputs, logabsdet = ops.made_inverse(rows, cache[1], len(net.blocks), per_dim, kind, rq, context=ctx_rows,
-                                                  context_pack=ctx_cache[1])
-        return (outputs, logabsdet) if pad == 0 else (outputs[:n], logabsdet[:n])
+        outputs, logabsdet = ops.made_inverse(
+            made_module.pad_rows(inputs), pack, len(net.blocks), per_dim, kind, rq,
+            context=None if context is None else made_module.pad_rows(context), context_pack=context_pack)
+        return (outputs, logabsdet) if outputs.shape[0] == n else (outputs[:n], logabsdet[:n])
 
     def _incremental_ok(self, inputs):
         """Column-at-a-time inverse applies to a MADE: its input degrees are 1..D and its output
@@ -273,19 +255,20 @@ class MaskedAffineAutoregressiveTransform(AutoregressiveTransform):
                     and ops.activation_code(net.activation)[0] == ops.ACT_RELU
                     and ops.affine_tail_fits(inputs.shape[1], len(net.blocks), inputs.shape[1]))
 
-        return (ops.static_memo(self, "_fc_static_ok", (inputs.shape[1],) + ops.structure_key(net), structure_ok)
+        return (ops.static_memo(self, "static_ok", (inputs.shape[1],) + ops.structure_key(net), structure_ok)
                 and not ops.has_hooks(net) and not self._needs_grad(inputs))
 
     def _one_kernel(self, inputs, total=None):
         net = self.autoregressive_net
         features = inputs.shape[1]
         where = tuple(p.data_ptr() for p in ops.param_list(net))
-        plan = ops.device_plan(self, "_tail_image", where, lambda: ops.device_pack_made_affine(net, features) + (
-            torch.arange(features, dtype=torch.int32, device=inputs.device),))
-        plan[1].refresh()
+        pack, image, ids = ops.device_plan(
+            self, "tail_image", where, lambda: ops.device_pack_made_affine(net, features) + (
+                torch.arange(features, dtype=torch.int32, device=inputs.device),))
+        pack.refresh()
         n = inputs.shape[0]
         body = n - n % ops.HIDDEN_ROWS
-        args = (plan[3], plan[3], plan[2], features, len(net.blocks), ops.AFFINE_MAF_SOFTPLUS)
+        args = (ids, ids, image, features, len(net.blocks), ops.AFFINE_MAF_SOFTPLUS)
         if body == n:
             return ops.affine_coupling_resnet(inputs, *args, logabsdet_accum=total)
         out_a, lad_a = ops.affine_coupling_resnet(inputs[:body], *args,

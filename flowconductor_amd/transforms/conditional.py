@@ -74,9 +74,8 @@ class ConditionalTransform(Transform):
         context rows; zero-padded columns for a narrower net); the leftover < 16 rows on PyTorch."""
         net = self.conditional_net
         n = context.shape[0]
-        ids = getattr(self, "_ctx_cols", None)
-        if ids is None or ids.device != context.device or ids.numel() != context.shape[1]:
-            ids = self._ctx_cols = torch.arange(context.shape[1], dtype=torch.int32, device=context.device)
+        ids = ops.memo(self, "ctx_cols", (context.shape[1], context.device),
+                       lambda: torch.arange(context.shape[1], dtype=torch.int32, device=context.device))
         body = n - n % ops.HIDDEN_ROWS
         hidden = net.hidden_hip(context[:body], ids)
         if body < n:
@@ -186,17 +185,14 @@ class ConditionalLUTransform(ConditionalTransform):
         self.default_pivot = torch.nn.Parameter(torch.arange(1, self.features + 1, dtype=torch.int32).unsqueeze(0),
                                                 requires_grad=False)
         self.scale_non_diag = torch.nn.Parameter(- 2 * torch.ones(()), requires_grad=True)
-        self._sp_cache = None
 
     def _output_dim_multiplier(self):
         return self.features
 
     def _offdiag_scale(self):
         # softplus of a 0-dim parameter: read back once per value (it only changes when trained)
-        key = ops.cache_key(self.scale_non_diag)
-        if self._sp_cache is None or self._sp_cache[0] != key:
-            self._sp_cache = (key, float(F.softplus(self.scale_non_diag.detach())))
-        return self._sp_cache[1]
+        return ops.memo(self, "offdiag_scale", ops.cache_key(self.scale_non_diag),
+                        lambda: float(F.softplus(self.scale_non_diag.detach())))
 
     def _forward_given_params(self, inputs, conditional_params):
         return ops.linear_per_sample(inputs, conditional_params, mode=ops.PER_SAMPLE_LU_FORWARD,

@@ -52,10 +52,9 @@ class OneByOneConvolution(LULinear):
         else:
             key = ops.cache_key(self.lower_entries, self.upper_entries, self.unconstrained_upper_diag,
                                 self.permutation._permutation, extra=(inverse,))
-        memo = self.__dict__.get("_conv1x1_cache")
-        if memo is not None and memo[0] == key and memo[1] is cached:
-            return memo[2], memo[3]
-        with torch.no_grad():
+
+        @torch.no_grad()
+        def fold():
             if inverse:
                 source = self._inverse64()
             else:
@@ -63,8 +62,9 @@ class OneByOneConvolution(LULinear):
                 source = lower.double() @ upper.double()
             matrix = self._fold(source, inverse).float()
             lad = self.logabsdet() if cached is None else self.cache.logabsdet
-        self.__dict__["_conv1x1_cache"] = (key, cached, matrix, lad)
-        return matrix, lad
+            return matrix, lad, cached       # (the entry keeps alive what its key names by id)
+
+        return ops.memo(self, "conv1x1", (key, id(cached)), fold)[:2]
 
     def _lu_forward_inverse(self, inputs, inverse=False):
         """The reference's composition on rows (conv.py), for channel counts the kernel does not take."""

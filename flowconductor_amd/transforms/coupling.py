@@ -66,7 +66,6 @@ class CouplingTransform(Transform):
             self.unconditional_transform = None
         else:
             self.unconditional_transform = unconditional_transform(features=self.num_identity_features)
-        self._cols_cache = None
 
     @property
     def num_identity_features(self):
@@ -78,19 +77,13 @@ class CouplingTransform(Transform):
 
     def _cols(self, device):
         """int32 copy of ``transform_features`` on ``device`` (what the kernel indexes with)."""
-        c = self._cols_cache
-        if c is None or c.device != device or c.numel() != self.num_transform_features:
-            c = self.transform_features.to(device=device, dtype=torch.int32).contiguous()
-            self._cols_cache = c
-        return c
+        return ops.memo(self, "cols", (self.num_transform_features, device),
+                        lambda: self.transform_features.to(device=device, dtype=torch.int32).contiguous())
 
     def _id_cols(self, device):
         """int32 copy of ``identity_features`` on ``device``."""
-        c = getattr(self, "_id_cols_cache", None)
-        if c is None or c.device != device or c.numel() != self.num_identity_features:
-            c = self.identity_features.to(device=device, dtype=torch.int32).contiguous()
-            self._id_cols_cache = c
-        return c
+        return ops.memo(self, "id_cols", (self.num_identity_features, device),
+                        lambda: self.identity_features.to(device=device, dtype=torch.int32).contiguous())
 
     def _check(self, inputs):
         if inputs.dim() not in [2, 4]:
@@ -221,7 +214,7 @@ class AffineCouplingTransform(CouplingTransform):
                     and net.hip_hidden_supported(inputs.shape[1], None)
                     and all(ops.activation_code(b.activation)[0] == ops.ACT_RELU for b in net.blocks))
 
-        return (ops.static_memo(self, "_fc_static_ok", (inputs.shape[1], id(self.unconditional_transform)) + ops.structure_key(net),
+        return (ops.static_memo(self, "static_ok", (inputs.shape[1], id(self.unconditional_transform)) + ops.structure_key(net),
                                 structure_ok)
                 and not ops.has_hooks(net)
                 and not (torch.is_grad_enabled()
@@ -229,13 +222,13 @@ class AffineCouplingTransform(CouplingTransform):
 
     def _one_kernel(self, inputs, inverse, total):
         net = self.transform_net
-        plan = ops.device_plan(self, "_tail_image", net._storage_key(), lambda: ops.device_pack_affine_coupling(
+        pack, image = ops.device_plan(self, "tail_image", net._storage_key(), lambda: ops.device_pack_affine_coupling(
             net, self.num_transform_features, self._activation_code() == ops.AFFINE_ADDITIVE))
-        plan[1].refresh()
+        pack.refresh()
         n = inputs.shape[0]
         body = n - n % ops.HIDDEN_ROWS
         dev = inputs.device
-        args = (self._id_cols(dev), self._cols(dev), plan[2], net.initial_layer.in_features, len(net.blocks),
+        args = (self._id_cols(dev), self._cols(dev), image, net.initial_layer.in_features, len(net.blocks),
                 self._activation_code())
         if body == n:
             return ops.affine_coupling_resnet(inputs, *args, inverse=inverse, logabsdet_accum=total)
@@ -400,7 +393,7 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
         lin = net.final_layer
         hidden_pack = None
         if getattr(net, "hip_hidden_backward_supported", None) is not None and net.hip_hidden_backward_supported():
-            hidden_pack = net.hidden_backward_plan()[1]        # rebuilt by the net when ITS storages moved
+            hidden_pack = net.hidden_backward_plan()[0]        # rebuilt by the net when ITS storages moved
 
         def build():
             pack, chunks = ops.device_pack_final_layer(lin.weight.detach(), lin.bias.detach(), self.num_bins, self.tails,
@@ -411,9 +404,9 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
 
         # also rebuilt when lin.weight is a new Parameter object or the hidden pack it merged is a different one
         where = (id(lin.weight), lin.weight.data_ptr(), lin.bias.data_ptr(), device, id(hidden_pack))
-        plan = ops.device_plan(self, "_train_pack", where, build)
-        plan[1].refresh()
-        return plan[2]
+        plan = ops.device_plan(self, "train_pack", where, build)
+        plan[0].refresh()
+        return plan[1]
 
     def _apply_accumulate(self, inputs, context, inverse, total):
         """CompositeTransform fast path: the fused kernel adds this layer's logabsdet onto ``total`` itself."""

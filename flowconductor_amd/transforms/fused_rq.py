@@ -21,15 +21,12 @@ def fused_mode(n, d, d_t, hidden, num_bins, tails, general_hidden):
 
 
 def packed_chunks(owner, lin, mode, num_bins, tails, spec):
-    """The final Linear ``lin`` in the layout of ``mode``, cached on ``owner._packed`` as ``(cache_key of the parameters,
-    {mode: chunks})``: one ``(w_pad, bias_pad, cols)`` ("k8") or ``(w_frag, w_unscale, bias_pad, cols)`` ("general") per
+    """The final Linear ``lin`` in the layout of ``mode``, cached on ``owner`` as ``{mode: chunks}`` per ``cache_key`` of
+    the parameters: one ``(w_pad, bias_pad, cols)`` ("k8") or ``(w_frag, w_unscale, bias_pad, cols)`` ("general") per
     group of transformed dims.  Only a miss asks the layer what to pack: ``spec()`` -> ``(weight, hidden_pad, [(row slice
     of the weight, cols)])`` -- ``lin.weight`` or a MADE's ``weight * mask``, the hidden width "general" zero-pads to."""
-    key = ops.cache_key(lin.weight, lin.bias)
-    cache = getattr(owner, "_packed", None)
-    if cache is None or cache[0] != key:
-        cache = owner._packed = (key, {})
-    packed = cache[1].get(mode)
+    by_mode = ops.memo(owner, "packed", ops.cache_key(lin.weight, lin.bias), dict)
+    packed = by_mode.get(mode)
     if packed is None:
         weight, hidden_pad, groups = spec()
         packed = []
@@ -39,7 +36,7 @@ def packed_chunks(owner, lin, mode, num_bins, tails, spec):
             else:
                 images = ops.pack_final_layer_general(weight[rows], lin.bias[rows], num_bins, tails, hidden_pad)
             packed.append(tuple(images) + (cols,))
-        cache[1][mode] = packed
+        by_mode[mode] = packed
     return packed
 
 

@@ -160,10 +160,10 @@ class iResBlock(Transform):
             return None
         if any(p.dtype != torch.float32 or p.device != inputs.device for p in params) or ops.has_hooks(self.nnet):
             return None
-        # has_hooks keeps the net's module list: a sub-module in training mode (net.bn.train()) means the composition
-        if any(m.training for m in self.nnet.__dict__["_fc_module_list"][2]):
+        # a sub-module in training mode (net.bn.train()) means the composition
+        if any(m.training for m in ops.module_list(self.nnet)):
             return None
-        plan = ops.static_memo(self, "_fc_static_ok", (id(self.nnet), id(self.nnet.activation)), self._kernel_plan)
+        plan = ops.static_memo(self, "static_ok", (id(self.nnet), id(self.nnet.activation)), self._kernel_plan)
         if plan is None:
             return None
         if (plan[3] > 0 or plan[4]) != (context is not None):
@@ -172,15 +172,6 @@ class iResBlock(Transform):
                                         and context.shape[0] == inputs.shape[0]):
             return None
         return plan
-
-    def _buffer_list(self):
-        """The net's buffers (power-method vectors, running statistics), memoised like ``ops.param_list``: valid while
-        the cache epoch stands and every slot still holds the same tensor."""
-        memo = self.__dict__.get("_ires_buffers")
-        if memo is None or memo[0] != ops.cache_epoch() or not all(m._buffers.get(n) is t for m, n, t in memo[1]):
-            slots = tuple((m, n, t) for m in self.nnet.modules() for n, t in m._buffers.items() if t is not None)
-            memo = self.__dict__["_ires_buffers"] = (ops.cache_epoch(), slots, tuple(t for _, _, t in slots))
-        return memo[2]
 
     def _image_constants(self):
         """The plain Python numbers that end up in the image (they have no version counter to watch)."""
@@ -195,10 +186,11 @@ class iResBlock(Transform):
     def _image(self, plan):
         """The packed, normalised net on the device, once per parameter version (no host sync)."""
         net = self.nnet
-        key = ops.cache_key(*ops.param_list(self), *self._buffer_list(), extra=self._image_constants())
-        memo = self.__dict__.get("_ires_image")
-        if memo is not None and memo[0] == key:
-            return memo[1]
+        key = ops.cache_key(*ops.param_list(self), *ops.buffer_list(net), extra=self._image_constants())
+        return ops.memo(self, "ires_image", key, lambda: self._pack_image(plan))
+
+    def _pack_image(self, plan):
+        net = self.nnet
         act_id = plan[0]
         with torch.no_grad():
             # the constants of the eval-mode net (normalised weights, eta1 / eta2, activation scalars) are evaluated by
@@ -233,7 +225,6 @@ class iResBlock(Transform):
             image = torch.cat(pieces).float().contiguous()
         expected = ops.iresnet_image_floats(net.dimension, plan[3], net.densenet_depth, net.densenet_growth, act_id)
         assert image.numel() == expected, (image.numel(), expected)
-        self.__dict__["_ires_image"] = (key, image)
         return image
 
     def _extras(self, plan, context):
@@ -257,7 +248,7 @@ class iResBlock(Transform):
     def inverse_iterations(self):
         """Largest per-row iteration count of the last kernel ``inverse`` call (reads a device word: a host sync; for
         tools and tests).  None before the first such call."""
-        word = self.__dict__.get("_ires_iters")
+        word = ops.cached(self, "ires_iters")
         return None if word is None else int(word.item())
 
     # ---- the two directions -----------------------------------------------------------------------------------------
@@ -277,9 +268,8 @@ class iResBlock(Transform):
         if plan is not None:
             extra, scale = self._extras(plan, context)
             image, shape = self._image(plan), self._shape_args(plan)
-            word = self.__dict__.get("_ires_iters")
-            if word is None or word.device != inputs.device:
-                word = self.__dict__["_ires_iters"] = torch.zeros(1, dtype=torch.int32, device=inputs.device)
+            word = ops.memo(self, "ires_iters", inputs.device,
+                            lambda: torch.zeros(1, dtype=torch.int32, device=inputs.device))
             x = ops.iresnet_inverse(inputs, image, *shape, extra=extra, scale=scale, iterations_out=word)
             _, lad = ops.iresnet_forward(x, image, *shape, extra=extra, scale=scale)
             return x, -lad

@@ -118,7 +118,7 @@ class MaskedResidualBlock(nn.Module):
         return inputs + h
 
 
-class MADE(ops.RuntimeCaches, nn.Module):
+class MADE(nn.Module):
     """Masked autoencoder: masked initial layer, ``num_blocks`` masked blocks, masked output layer
     producing ``output_multiplier`` values per input feature (feature-major)."""
 
@@ -203,8 +203,8 @@ class MADE(ops.RuntimeCaches, nn.Module):
 
         layers = [self.initial_layer] + [lin for block in self.blocks for lin in block.linear_layers]
         ctx_layers = ([self.context_layer] + [block.context_layer for block in self.blocks]) if context is not None else []
-        key = ops.cache_key(*[t for lin in layers + ctx_layers for t in (lin.weight, lin.bias)])
-        if getattr(self, "_hip_packed", None) is None or self._hip_packed[0] != key:
+
+        def pack():
             hw = ops.FUSED_HIDDEN
             masked = [ops._pad_to((lin.weight * lin.mask).detach(), (hw, lin.in_features if i == 0 else hw))
                       for i, lin in enumerate(layers)]
@@ -216,8 +216,11 @@ class MADE(ops.RuntimeCaches, nn.Module):
                 wc = torch.stack([ops._pad_to(cl.weight.detach(), (hw, cl.in_features)) for cl in ctx_layers]).contiguous()
                 bc = torch.stack([ops._pad_to(cl.bias.detach(), (hw,)) for cl in ctx_layers]).contiguous()
             ids = torch.arange(self.initial_layer.in_features, dtype=torch.int32, device=rows.device)
-            self._hip_packed = (key, (masked[0], biases[0].contiguous(), wb, bb, wc, bc), ids)
-        return ops.resnet_hidden(rows, self._hip_packed[2], self._hip_packed[1], self.initial_layer.in_features,
+            return ids, (masked[0], biases[0].contiguous(), wb, bb, wc, bc)
+
+        key = ops.cache_key(*[t for lin in layers + ctx_layers for t in (lin.weight, lin.bias)])
+        ids, packed = ops.memo(self, "hip_packed", key, pack)
+        return ops.resnet_hidden(rows, ids, packed, self.initial_layer.in_features,
                                  len(self.blocks), context, ops.activation_code(self.activation),
                                  ops.CONTEXT_ADDITIVE)
 
@@ -228,11 +231,35 @@ class MADE(ops.RuntimeCaches, nn.Module):
         width = lin.in_features if width is None else width
         from flowconductor_amd import ops
 
-        key = ops.cache_key(lin.weight, extra=(width,))
-        cache = getattr(self, "_masked_final", None)
-        if cache is None or cache[0] != key:
+        def masked():
             w = (lin.weight * lin.mask).detach()
             if width != lin.in_features:
                 w = F.pad(w, (0, width - lin.in_features))
-            self._masked_final = cache = (key, w.contiguous())
-        return cache[1], lin.bias
+            return w.contiguous()
+
+        return ops.memo(self, "masked_final", ops.cache_key(lin.weight, extra=(width,)), masked), lin.bias
+
+    def inverse_packs(self, per_dim, with_context):
+        """``(pack_made_inverse, pack_made_inverse_context or None)`` of this net with ``per_dim`` outputs per feature: the
+        weight images of the one-kernel device loops (autoregressive inverse, mixture sampling), re-packed when a weight
+        or bias of the layers they are made from changed."""
+        from flowconductor_amd import ops
+
+        features = self.initial_layer.in_features
+        layers = [self.initial_layer, self.final_layer] + [lin for block in self.blocks for lin in block.linear_layers]
+        key = ops.cache_key(*[t for lin in layers for t in (lin.weight, lin.bias)], extra=(per_dim,))
+        pack = ops.memo(self, "made_inverse_pack", key, lambda: ops.pack_made_inverse(self, features, per_dim))
+        if not with_context:
+            return pack, None
+        ctx_layers = [self.context_layer] + [block.context_layer for block in self.blocks]
+        ctx_key = ops.cache_key(*[t for lin in ctx_layers for t in (lin.weight, lin.bias)], extra=(per_dim,))
+        return pack, ops.memo(self, "made_inverse_context_pack", ctx_key,
+                              lambda: ops.pack_made_inverse_context(self, features, per_dim))
+
+
+def pad_rows(t):
+    """``t`` [N, ...] detached, contiguous and zero-padded to the next multiple of ``ops.HIDDEN_ROWS`` rows (what the device
+    loops take; the caller cuts the results back to N rows)."""
+    t = t.detach().contiguous()
+    pad = -t.shape[0] % ops.HIDDEN_ROWS
+    return t if pad == 0 else F.pad(t, (0, 0, 0, pad))

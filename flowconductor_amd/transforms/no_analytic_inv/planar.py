@@ -93,10 +93,8 @@ class SylvesterTransform(Transform):
         """(W1, W2, r_diag_prod) for the matrix-core kernel, recomputed only when a parameter changed."""
         params = (self.Q_orth.q_vectors, self.upper_entries1, self.log_upper_diag1, self.upper_entries2,
                   self.log_upper_diag2)
-        key = ops.cache_key(*params)
-        if getattr(self, "_mm_cache", None) is None or self._mm_cache[0] != key:
-            self._mm_cache = (key, ops.pack_sylvester(self.Q_orth.q_vectors, self._create_R1(), self._create_R2()))
-        return self._mm_cache[1]
+        return ops.memo(self, "mm_weights", ops.cache_key(*params),
+                        lambda: ops.pack_sylvester(self.Q_orth.q_vectors, self._create_R1(), self._create_R2()))
 
     _HIP_AUTOGRAD = True
 

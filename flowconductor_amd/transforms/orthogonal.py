@@ -48,10 +48,7 @@ class HouseholderSequence(Transform):
                 and options.get("sylvester_mm")
                 and not (torch.is_grad_enabled() and (inputs.requires_grad or self.q_vectors.requires_grad))):
             return None
-        key = ops.cache_key(self.q_vectors)
-        if getattr(self, "_dense_cache", None) is None or self._dense_cache[0] != key:
-            self._dense_cache = (key, {})
-        mats = self._dense_cache[1]
+        mats = ops.memo(self, "dense", ops.cache_key(self.q_vectors), dict)
         if reverse not in mats:
             # householder(v, q, reverse) == v @ M  ->  as a column map the weight is M^T
             mats[reverse] = ops.householder_matrix(self.q_vectors, reverse=reverse).T.float().contiguous()

@@ -44,11 +44,8 @@ class Permutation(Transform):
     def _index32(self, device):
         """The permutation as the int32 device vector the kernel takes, converted once per buffer version."""
         perm = self._permutation
-        key = ops.cache_key(perm, extra=(device,))
-        memo = self.__dict__.get("_cols_cache")
-        if memo is None or memo[0] != key:
-            memo = self.__dict__["_cols_cache"] = (key, perm.to(device=device, dtype=torch.int32).contiguous())
-        return memo[1]
+        return ops.memo(self, "index32", ops.cache_key(perm, extra=(device,)),
+                        lambda: perm.to(device=device, dtype=torch.int32).contiguous())
 
     def _apply_accumulate(self, inputs, context, inverse, total):
         """CompositeTransform fast path: logabsdet is identically zero -- nothing to allocate or add (two tiny launches per

@@ -34,10 +34,7 @@ def folded_mm(module, inputs, inverse, fold, tail):
     """``fc_dense_mm`` with the module's weight (or inverse weight) folded once in float64 -- ``fold(inverse)``, cached per
     parameter version -- over the rows that fill whole tiles; ``tail(rows)`` maps the remaining rows.  The inverse
     subtracts the bias inside the kernel, before the product."""
-    key = ops.cache_key(*module.parameters())
-    if getattr(module, "_dense_cache", None) is None or module._dense_cache[0] != key:
-        module._dense_cache = (key, {})
-    mats = module._dense_cache[1]
+    mats = ops.memo(module, "dense", ops.cache_key(*module.parameters()), dict)
     if inverse not in mats:
         mats[inverse] = fold(inverse).float().contiguous()
     n = inputs.shape[0]

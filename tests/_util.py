@@ -33,6 +33,23 @@ def build_case(name, g=None):
     return t, spec
 
 
+def warm_modules(root):
+    """The sub-modules of ``root`` (itself included) whose run-time cache store holds anything."""
+    return [m for m in root.modules() if m.__dict__.get("_fc_cache")]
+
+
+def copies(module):
+    """``module`` through ``copy.deepcopy``, ``pickle`` and ``torch.save`` + ``torch.load``."""
+    import copy
+    import io
+    import pickle
+
+    buf = io.BytesIO()
+    torch.save(module, buf)
+    buf.seek(0)
+    return copy.deepcopy(module), pickle.loads(pickle.dumps(module)), torch.load(buf, weights_only=False)
+
+
 def maxdiff(a, b):
     a = a.detach().cpu().double().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float64)
     b = b.detach().cpu().double().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, dtype=np.float64)

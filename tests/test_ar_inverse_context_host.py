@@ -2,14 +2,13 @@
 the reference's statement that the context never reaches column 0 of an autoregressive inverse."""
 import copy
 import ctypes
-import io
 import os
-import pickle
 import re
 
 import pytest
 import torch
 
+from _util import copies, warm_modules
 from flowconductor_amd import _hip, ops
 from flowconductor_amd import transforms as T
 from oracle import torch_oracle as O
@@ -101,24 +100,46 @@ def test_context_lds_budget():
 
 
 def test_device_loop_caches_do_not_travel():
-    names = ("_fc_made_inverse_pack", "_fc_made_inverse_context_pack", "_fc_device_loop_ok", "_fc_device_loop_context_ok")
-    for name in names:
-        assert name in ops.RUNTIME_CACHE_ATTRS
     t = build("maf", 6, 32, 3, 2)
     net = t.autoregressive_net
-    t.__dict__["_fc_made_inverse_pack"] = ((1,), ops.pack_made_inverse(net, 6, 2))
-    t.__dict__["_fc_made_inverse_context_pack"] = ((1,), ops.pack_made_inverse_context(net, 6, 2))
-    t.__dict__["_fc_device_loop_ok"] = ((0,), True)
-    t.__dict__["_fc_device_loop_context_ok"] = ((0,), True)
-    for other in (copy.deepcopy(t), pickle.loads(pickle.dumps(t))):
-        assert all(other.__dict__.get(name) is None for name in names)
-    buf = io.BytesIO()
-    torch.save(t, buf)
-    buf.seek(0)
-    loaded = torch.load(buf, weights_only=False)
-    assert all(loaded.__dict__.get(name) is None for name in names)
+    pack, context_pack = net.inverse_packs(2, True)
+    ops.static_memo(t, "device_loop_ok", (0,), lambda: True)
+    ops.static_memo(t, "device_loop_context_ok", (0,), lambda: True)
+    deep, pickled, loaded = copies(t)
+    for other in (deep, pickled, loaded):
+        assert warm_modules(other) == []
+        assert all(ops.cached(other, name) is None for name in ("device_loop_ok", "device_loop_context_ok"))
+        assert all(ops.cached(other.autoregressive_net, name) is None
+                   for name in ("made_inverse_pack", "made_inverse_context_pack"))
     assert all(torch.equal(a, b) for a, b in zip(loaded.state_dict().values(), t.state_dict().values()))
-    assert t.__dict__["_fc_made_inverse_context_pack"] is not None            # the original keeps its packs
+    assert ops.cached(net, "made_inverse_context_pack") is context_pack       # the original keeps its packs
+    assert ops.cached(net, "made_inverse_pack") is pack and ops.cached(t, "device_loop_ok") is True
+
+
+def test_inverse_packs_are_kept_per_output_width_and_follow_the_weights(monkeypatch):
+    """MADE.inverse_packs: unchanged weights give the very same tensors, an in-place update re-packs what was made from
+    the changed layer; a caller asking for another ``per_dim`` is never handed the pack of the first (a real net has one
+    output width, so the packers are stubbed for that part)."""
+    net = build("maf", 6, 32, 3, 2).autoregressive_net
+    pack, context_pack = net.inverse_packs(2, True)
+    again, context_again = net.inverse_packs(2, True)
+    assert all(a is b for a, b in zip(pack + context_pack, again + context_again))
+    assert net.inverse_packs(2, False) == (pack, None)
+    assert all(torch.equal(a, b) for a, b in zip(pack, ops.pack_made_inverse(net, 6, 2)))
+    assert all(torch.equal(a, b) for a, b in zip(context_pack, ops.pack_made_inverse_context(net, 6, 2)))
+    with torch.no_grad():
+        net.blocks[0].linear_layers[0].weight.mul_(2.0)
+    fresh, context_same = net.inverse_packs(2, True)
+    assert fresh is not pack and context_same is context_pack          # (no context layer changed)
+    assert all(torch.equal(a, b) for a, b in zip(fresh, ops.pack_made_inverse(net, 6, 2)))
+    assert not all(torch.equal(a, b) for a, b in zip(fresh, pack))
+    with torch.no_grad():
+        net.context_layer.bias.add_(0.5)
+    assert net.inverse_packs(2, True)[1] is not context_pack
+    monkeypatch.setattr(ops, "pack_made_inverse", lambda made, features, per_dim: ("pack", features, per_dim))
+    monkeypatch.setattr(ops, "pack_made_inverse_context", lambda made, features, per_dim: ("context", features, per_dim))
+    for per_dim in (23, 12, 23):
+        assert net.inverse_packs(per_dim, True) == (("pack", 6, per_dim), ("context", 6, per_dim))
 
 
 @pytest.mark.parametrize("kind,features,hidden,context_features,blocks,n", SHAPES)

@@ -237,7 +237,8 @@ def test_caches_follow_the_context_layers(device):
     with torch.no_grad():
         y0, lad0 = _device_inverse(t, xd, cd)
         twin = copy.deepcopy(t)
-        assert twin.__dict__.get("_fc_made_inverse_context_pack") is None and twin.__dict__.get("_fc_made_inverse_pack") is None
+        assert ops.cached(t.autoregressive_net, "made_inverse_context_pack") is not None
+        assert [m for m in twin.modules() if m.__dict__.get("_fc_cache")] == []      # the copy starts cold
         y_twin, lad_twin = _device_inverse(twin, xd, cd)
         assert torch.equal(y_twin, y0) and torch.equal(lad_twin, lad0)
         t.autoregressive_net.blocks[1].context_layer.bias.add_(0.5)

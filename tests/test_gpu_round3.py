@@ -7,7 +7,10 @@ import numpy as np
 import pytest
 import torch
 
-from _util import GOLDEN_DIR, Lib, build_case, golden  # noqa: F401
+import _mog_util as M
+from _util import GOLDEN_DIR, Lib, build_case, golden, maxdiff, warm_modules  # noqa: F401
+from flowconductor_amd import ops
+from oracle import torch_oracle as O
 
 pytestmark = pytest.mark.gpu
 T, nets, utils = Lib.transforms, Lib.nets, Lib.utils
@@ -28,15 +31,20 @@ def test_deepcopy_and_torch_save_after_forward_and_backward(device):
     flow = _nsf().to(device)
     x = torch.randn(256, 64, device=device)
     flow.train()
-    (-flow.log_prob(x).mean()).backward()             # builds the training plans (_train_pack, _hip_packed_bwd)
+    (-flow.log_prob(x).mean()).backward()             # builds the training plans (train_pack, hip_packed_bwd)
     flow.eval()
     with torch.no_grad():
-        ref = flow.log_prob(x)                         # builds the inference images (_hip_image)
+        ref = flow.log_prob(x)                         # builds the inference images (hip_image)
     snap = copy.deepcopy(flow)
     buf = io.BytesIO()
     torch.save(flow, buf)
     buf.seek(0)
     loaded = torch.load(buf, weights_only=False)
+    # every layer and every conditioner took a fast path and keeps what it packed; no copy inherits any of it
+    warm = warm_modules(flow)
+    for layer in flow._transform._transforms:
+        assert any(m is layer for m in warm) and any(m is layer.transform_net for m in warm)
+    assert warm_modules(snap) == [] and warm_modules(loaded) == []
     with torch.no_grad():
         assert torch.equal(snap.log_prob(x), ref)
         assert torch.equal(loaded.log_prob(x), ref)
@@ -45,6 +53,58 @@ def test_deepcopy_and_torch_save_after_forward_and_backward(device):
             p.mul_(1.5)
         assert torch.equal(snap.log_prob(x), ref)
         assert not torch.equal(flow.log_prob(x), ref)
+
+
+def test_device_loop_packs_live_on_the_net_and_follow_copies_and_updates(device):
+    """The one-kernel autoregressive inverse and the one-kernel mixture sampler take their weight images from
+    ``MADE.inverse_packs`` of their own nets: a deep copy starts cold and gives the same bits, an in-place change of a
+    hidden layer's weight reaches the kernel.  Bounds: those of tests/test_gpu_ar_inverse_context.py (inverse) and of
+    tests/test_gpu_mog.py::test_routing (sampler)."""
+    torch.manual_seed(3)
+    t = T.MaskedPiecewiseRationalQuadraticAutoregressiveTransform(6, 32, num_bins=8, tails="linear", tail_bound=3.0,
+                                                                  num_blocks=2).eval()
+    with torch.no_grad():
+        for p in t.parameters():
+            p.mul_(1.5)
+    dist = M.build(6, 32, 4, None, 2)
+    x = torch.randn(64, 6, generator=torch.Generator().manual_seed(5)) * 1.2
+    normal, uniform, _ = M.noise(64, 6, None, 7)
+
+    def inverse64(layer):
+        with torch.no_grad():
+            y32, _ = O.transform_apply(layer, x.clone(), None, inverse=True)
+            y64, _ = O.transform_apply(copy.deepcopy(layer).double(), x.double(), None, inverse=True)
+        return y64, 1e-4 * max(1.0, float(y32.abs().max())) + 4 * maxdiff(y32, y64)
+
+    def run(layer, mixture):
+        with torch.no_grad(), ops.KernelTimer("fc_made_inverse") as inverse_timer, \
+                ops.KernelTimer("fc_made_mog_sample") as sample_timer:
+            y, _ = layer.inverse(x.to(device))
+            draws = mixture._sample_from_noise(normal.to(device), uniform.to(device))
+        assert len(inverse_timer.pairs) == 1 and len(sample_timer.pairs) == 1
+        return y, draws
+
+    t, dist = t.to(device), dist.to(device)
+    y0, draws0 = run(t, dist)
+    assert ops.cached(t.autoregressive_net, "made_inverse_pack") is not None
+    assert ops.cached(dist._made, "made_inverse_pack") is not None
+    t_twin, dist_twin = copy.deepcopy(t), copy.deepcopy(dist)
+    assert warm_modules(t_twin) == [] and warm_modules(dist_twin) == []
+    y_twin, draws_twin = run(t_twin, dist_twin)
+    assert torch.equal(y_twin, y0) and torch.equal(draws_twin, draws0)
+    with torch.no_grad():
+        t.autoregressive_net.initial_layer.weight.add_(0.5)
+        dist._made.initial_layer.weight.add_(0.5)
+    y1, draws1 = run(t, dist)
+    y64, tol_y = inverse64(copy.deepcopy(t).cpu())
+    assert maxdiff(y1, y0) > 10 * tol_y, "the changed weight did not reach fc_made_inverse"
+    assert maxdiff(y1, y64) <= tol_y
+    draws64, keep, _ = M.sample64(dist, normal, uniform, None)
+    tol_draws = 1e-4 * max(1.0, float(draws64.abs().max()))
+    assert maxdiff(draws1, draws0) > 10 * tol_draws, "the changed weight did not reach fc_made_mog_sample"
+    assert float((draws1.cpu().double() - draws64)[keep].abs().max()) <= tol_draws
+    y_twin, draws_twin = run(t_twin, dist_twin)           # the copies packed from THEIR weights
+    assert torch.equal(y_twin, y0) and torch.equal(draws_twin, draws0)
 
 
 def test_fused_backward_refuses_weights_changed_after_forward(device):

@@ -441,36 +441,98 @@ def test_runtime_caches_do_not_travel_with_deepcopy_or_pickle():
     pickle / torch.save of a module that has run must succeed and start cold (EMA snapshots, whole-module
     checkpoints -- the reference supports both)."""
     import copy
-    import io
     import pickle
 
+    from _util import copies, warm_modules
     from flowconductor_amd import _hip
 
     t = T.PiecewiseRationalQuadraticCouplingTransform(utils.create_alternating_binary_mask(8), _net, num_bins=4)
+    net = t.transform_net
     pack = ops.DevicePack(torch.device("cpu"))
     pack.prepare.append(lambda: None)                  # a local closure, as the real plans hold
-    t._train_pack = [0, pack, [], t.transform_net.final_layer.weight, None]
-    t._tail_image = [0, pack, (torch.zeros(3),)]
-    t.transform_net._hip_image = [0, _hip.PackJob(), (torch.zeros(3),)]
-    t.transform_net._hip_packed = ((1, 2), torch.zeros(5))
-    for name in ("_train_pack", "_tail_image"):
-        assert name in ops.RUNTIME_CACHE_ATTRS
+    train_pack = ops.device_plan(t, "train_pack", 0, lambda: (pack, [], net.final_layer.weight, None))
+    ops.device_plan(t, "tail_image", 0, lambda: (pack, (torch.zeros(3),)))
+    ops.device_plan(net, "hip_image", 0, lambda: (_hip.PackJob(), (torch.zeros(3),)))
+    ops.memo(net, "hip_packed", (1, 2), lambda: torch.zeros(5))
     with pytest.raises(Exception):
-        pickle.dumps(t._train_pack)                    # what used to break deepcopy of the whole module
-    t2 = copy.deepcopy(t)
-    assert t2._train_pack is None and t2._tail_image is None
-    assert t2.transform_net._hip_image is None and t2.transform_net._hip_packed is None
-    assert t._train_pack is not None and t.transform_net._hip_image is not None    # the original keeps its plans
-    assert t2.transform_net.final_layer.weight.data_ptr() != t.transform_net.final_layer.weight.data_ptr()
-    buf = io.BytesIO()
-    torch.save(t, buf)
-    buf.seek(0)
-    t3 = torch.load(buf, weights_only=False)
-    assert t3._train_pack is None and t3.transform_net._hip_image is None
+        pickle.dumps(train_pack)                       # what used to break deepcopy of the whole module
+    t2, t_pickled, t3 = copies(t)
+    for other in (t2, t_pickled, t3):                  # every slot of every module starts cold
+        assert warm_modules(other) == []
+        assert ops.cached(other, "train_pack") is None and ops.cached(other, "tail_image") is None
+        assert ops.cached(other.transform_net, "hip_image") is None and ops.cached(other.transform_net, "hip_packed") is None
+    assert ops.cached(t, "train_pack") is train_pack and ops.cached(net, "hip_image") is not None    # the original keeps its plans
+    assert warm_modules(t) == [t, net]
+    assert t2.transform_net.final_layer.weight.data_ptr() != net.final_layer.weight.data_ptr()
     assert all(torch.equal(a, b) for a, b in zip(t3.state_dict().values(), t.state_dict().values()))
     made = T.made.MADE(features=4, hidden_features=8)
-    made._hip_packed = (0, _hip.PackJob())
-    assert copy.deepcopy(made)._hip_packed is None
+    ops.memo(made, "hip_packed", 0, _hip.PackJob)
+    assert ops.cached(made, "hip_packed") is not None and warm_modules(copy.deepcopy(made)) == []
+
+
+def test_memo_recomputes_on_another_key_and_plans_outlive_the_epoch(monkeypatch):
+    """ops.memo: an equal key is a hit, any other key a miss; the cache epoch is part of a static_memo key and of no
+    device_plan key -- a plan's DevicePack follows the epoch on its own, in refresh()."""
+    owner = torch.nn.Linear(2, 2)
+    calls = []
+
+    def compute():
+        calls.append(1)
+        return object()
+
+    first = ops.memo(owner, "slot", (1, "a"), compute)
+    assert ops.memo(owner, "slot", (1, "a"), compute) is first and len(calls) == 1
+    assert ops.cached(owner, "slot") is first and ops.cached(owner, "other") is None
+    assert ops.memo(owner, "slot", (2, "a"), compute) is not first and len(calls) == 2
+    static = ops.static_memo(owner, "static", (3,), compute)
+    assert ops.static_memo(owner, "static", (3,), compute) is static and len(calls) == 3
+    launches = []
+    monkeypatch.setattr(ops.DevicePack, "run", lambda self: launches.append(len(self.root().all_jobs())))
+
+    def build():
+        pack = ops.DevicePack(torch.device("cpu"))
+        pack.add(ops.PACK_HIDDEN, owner.weight, None, torch.empty(64, dtype=torch.float16), torch.empty(1), nks=1, nt=1)
+        return pack, ()
+
+    plan = ops.device_plan(owner, "plan", (owner.weight.data_ptr(),), build)
+    plan[0].refresh()
+    plan[0].refresh()
+    assert launches == [1]
+    ops.invalidate_hip_caches()
+    assert ops.static_memo(owner, "static", (3,), compute) is not static and len(calls) == 4
+    assert ops.device_plan(owner, "plan", (owner.weight.data_ptr(),), build) is plan
+    plan[0].refresh()
+    assert launches == [1, 1]
+
+
+def test_plain_modules_keep_their_memos_in_the_same_store():
+    """ops.has_hooks / ops.param_list write onto whatever nn.Module they are given (a Lipschitz dense net, an
+    nn.Sequential): those memos do not travel either, and a copy answers for its own modules.  torch refuses to pickle
+    a parametrized module (the dense net's spectral normalisation) whatever it holds: that one is copied by deepcopy."""
+    import copy
+    import pickle
+
+    from _util import copies, warm_modules
+
+    torch.manual_seed(0)
+    dense = nets.DenseNet(dimension=4, densenet_depth=2, densenet_growth=8)
+    with pytest.raises(RuntimeError, match="parametrized modules"):
+        pickle.dumps(dense)
+    plain = torch.nn.Sequential(torch.nn.Linear(3, 4), torch.nn.Tanh(), torch.nn.Linear(4, 2))
+    for net, copy_all in ((dense, lambda m: (copy.deepcopy(m),)), (plain, copies)):
+        assert not ops.has_hooks(net) and len(ops.param_list(net)) == len(list(net.parameters()))
+        assert warm_modules(net) == [net]
+        for other in copy_all(net):
+            assert warm_modules(other) == []
+            leaf = [m for m in other.modules() if not m._modules][0]
+            handle = leaf.register_forward_pre_hook(lambda m, i: None)
+            assert ops.has_hooks(other) and not ops.has_hooks(net)
+            handle.remove()
+            handle = net.register_forward_hook(lambda m, i, o: None)
+            assert ops.has_hooks(net) and not ops.has_hooks(other)
+            handle.remove()
+            assert all(a is b for a, b in zip(ops.param_list(other), other.parameters()))
+        assert warm_modules(net) == [net]                 # the original keeps its entries
 
 
 def test_param_list_memo_sees_replaced_parameter_objects():

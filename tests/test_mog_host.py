@@ -147,4 +147,11 @@ def test_sampler_law_of_column_zero():
 
 
 def test_sampler_cache_does_not_travel():
-    assert "_fc_mog_sample_ok" in ops.RUNTIME_CACHE_ATTRS
+    from _util import copies, warm_modules
+
+    made = M.build(6, 32, 4, None, 2)._made
+    ops.static_memo(made, "mog_sample_ok", (6, None), lambda: True)
+    pack, _ = made.inverse_packs(12, False)
+    for other in copies(made):
+        assert warm_modules(other) == [] and ops.cached(other, "mog_sample_ok") is None
+    assert ops.cached(made, "mog_sample_ok") is True and ops.cached(made, "made_inverse_pack") is pack
