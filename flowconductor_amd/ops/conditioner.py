@@ -1,0 +1,255 @@
+"""Conditioner drivers: the hidden stack of a ResidualNet / MADE (64-wide, wide, backward), the one-kernel affine coupling
+layer and the one-kernel autoregressive inverse.
+"""
+import torch
+
+from flowconductor_amd import _hip
+from ._core import _aligned16, _as_cols, _call, _err_word, _finish, _logabsdet_target, _prep_2d
+from .rq import DEFAULT_MIN_BIN_HEIGHT, DEFAULT_MIN_BIN_WIDTH, DEFAULT_MIN_DERIVATIVE, _rq_config
+from .affine import AFFINE_ADDITIVE, AFFINE_MAF_SOFTPLUS, AFFINE_SIGMOID_PLUS2, AFFINE_SOFTPLUS_CLAMP3
+
+
+HIDDEN_ROWS = 16
+
+ACT_RELU, ACT_TANH, ACT_SILU, ACT_ELU, ACT_LEAKY_RELU, ACT_SIGMOID = range(6)
+
+
+def activation_code(fn):
+    """``(FC_ACT_* code, parameter)`` of an activation callable / module the hidden-layer kernel knows, else None."""
+    import torch.nn as nn
+    from torch.nn import functional as F
+
+    if isinstance(fn, nn.ReLU) or fn in (F.relu, torch.relu):
+        return ACT_RELU, 0.0
+    if isinstance(fn, nn.Tanh) or fn in (torch.tanh, F.tanh):
+        return ACT_TANH, 0.0
+    if isinstance(fn, nn.SiLU) or fn is F.silu:
+        return ACT_SILU, 0.0
+    if isinstance(fn, nn.ELU):
+        return ACT_ELU, float(fn.alpha)
+    if fn is F.elu:
+        return ACT_ELU, 1.0
+    if isinstance(fn, nn.LeakyReLU):
+        return ACT_LEAKY_RELU, float(fn.negative_slope)
+    if fn is F.leaky_relu:
+        return ACT_LEAKY_RELU, 0.01
+    if isinstance(fn, nn.Sigmoid) or fn in (torch.sigmoid, F.sigmoid):
+        return ACT_SIGMOID, 0.0
+    return None
+
+
+CONTEXT_GLU, CONTEXT_ADDITIVE = 1, 2
+
+WIDE_ROWS = 64
+
+HIDDEN_BWD_ROWS = 128
+
+MADE_AFFINE, MADE_RQ = 0, 1
+
+
+def made_inverse_context_fits(features, num_blocks, per_dim):
+    """LDS budget of ``fc_made_inverse_context`` (fc_made_inverse.h ``mi_lds_bytes`` + ``mi_ctx_lds_bytes``, one 16-row
+    block per wave): the hidden stack's image, the context layers' images and the waves' parameter strips in 160 KB."""
+    k0s = 1 if features <= 32 else 2
+    pt = -(-per_dim // 16)
+    image = (k0s * 8 + 2 * num_blocks * 16) * 1024 + (1 + 2 * num_blocks) * 256 + 64 + 8 * 16 * (16 * pt + 4) * 4
+    context = (1 + num_blocks) * (8 * 1024 + 256) + 64
+    return num_blocks <= 3 and features <= 64 and per_dim <= 48 and image + context <= 160 * 1024
+
+
+def made_inverse(inputs, packed, num_blocks, per_dim, kind, rq=None, logabsdet_accum=None, context=None,
+                 context_pack=None):
+    """The D passes of an autoregressive inverse in ONE kernel (``fc_made_inverse``): ``inputs`` [N, D <= 64] (rows a
+    multiple of 16), ``packed`` from ``pack_made_inverse``; ``kind`` ``MADE_AFFINE`` or ``MADE_RQ`` (``rq``: keyword
+    arguments of the spline as for ``rq_spline``).  With ``context`` [N, C <= 32] and ``context_pack`` from
+    ``pack_made_inverse_context`` the conditional form (``fc_made_inverse_context``).  Returns ``(outputs, logabsdet)``."""
+    lib = _hip.load()
+    z = _prep_2d(inputs)
+    _hip.require_no_grad(inputs)
+    n, d = z.shape
+    if n % HIDDEN_ROWS != 0 or d > 64:
+        raise ValueError("fc_made_inverse: rows must be a multiple of %d, D <= 64" % HIDDEN_ROWS)
+    if (context is None) != (context_pack is None):
+        raise ValueError("made_inverse: context and context_pack go together")
+    if context is not None:
+        _hip.require_no_grad(context)
+        if (not torch.is_tensor(context) or context.dtype != torch.float32 or context.dim() != 2 or context.shape[0] != n
+                or not 1 <= context.shape[1] <= 32 or not context.is_contiguous() or context.device != z.device):
+            raise ValueError("made_inverse: context must be a contiguous float32 [N, C <= 32] tensor on the inputs' device")
+        if not made_inverse_context_fits(d, num_blocks, per_dim):
+            raise ValueError("fc_made_inverse_context has no instantiation for D = %d, %d blocks, %d parameters per dim"
+                             % (d, num_blocks, per_dim))
+        cf, cu, cb = context_pack
+        if cf.numel() != (1 + num_blocks) * 4096 or cu.numel() != 1 + num_blocks or cb.numel() != (1 + num_blocks) * 64:
+            raise ValueError("made_inverse: context_pack does not match num_blocks = %d" % num_blocks)
+    cfg = None
+    if kind == MADE_RQ:
+        rq = dict(rq)
+        cfg = _rq_config(rq.pop("num_bins"), rq.pop("tails"), rq.pop("tail_bound", 1.0),
+                         (rq.pop("left", 0.0), rq.pop("right", 1.0), rq.pop("bottom", 0.0), rq.pop("top", 1.0)),
+                         rq.pop("min_bin_width", DEFAULT_MIN_BIN_WIDTH), rq.pop("min_bin_height", DEFAULT_MIN_BIN_HEIGHT),
+                         rq.pop("min_derivative", DEFAULT_MIN_DERIVATIVE), rq.pop("enable_identity_init", False),
+                         rq.pop("wh_divisor", 1.0), True)
+        if rq:
+            raise TypeError("made_inverse: unknown spline arguments %s" % sorted(rq))
+    y = torch.empty_like(z)
+    lad, flags = _logabsdet_target(logabsdet_accum, n, z.device)
+    if flags:
+        if cfg is None:
+            cfg = _hip.RQConfig()          # affine form: only the flags are read
+        cfg.flags = flags
+    err = _err_word(z.device, True)
+    hf, hu, hb, ff, fu, fb, need = packed
+    if need.dtype != torch.int32 or need.numel() != d:
+        raise ValueError("made_inverse: units_needed must hold one int32 per dim")
+    if context is not None:
+        _call("fc_made_inverse_context", lib.fc_made_inverse_context, z.device, _hip.ptr(z), _hip.ptr(context), _hip.ptr(y),
+              _hip.ptr(lad), _hip.ptr(hf), _hip.ptr(hu), _hip.ptr(hb), _hip.ptr(cf), _hip.ptr(cu), _hip.ptr(cb), _hip.ptr(ff),
+              _hip.ptr(fu), _hip.ptr(fb), _hip.ptr(need), _hip.ptr(err), n, d, context.shape[1], num_blocks, per_dim, kind, cfg,
+              _hip.stream_ptr(z.device))
+        _finish(True)
+        return y, lad
+    _call("fc_made_inverse", lib.fc_made_inverse, z.device, _hip.ptr(z), _hip.ptr(y), _hip.ptr(lad), _hip.ptr(hf),
+          _hip.ptr(hu), _hip.ptr(hb), _hip.ptr(ff), _hip.ptr(fu), _hip.ptr(fb), _hip.ptr(need), _hip.ptr(err), n, d, num_blocks, per_dim,
+          kind, cfg, _hip.stream_ptr(z.device))
+    _finish(True)
+    return y, lad
+
+
+def affine_tail_fits(in_features, num_blocks, d):
+    """LDS budget of ``fc_affine_coupling_resnet``: the weight image (initial layer, 2 per block, the final Linear) + one
+    [16, D | 1] float tile per wave next to it, 160 KB per CU; D <= 128, <= 3 blocks."""
+    k0s = 1 if in_features <= 32 else 2
+    layers = 2 + 2 * num_blocks
+    image = (k0s * 8 + (2 * num_blocks + 1) * 16) * 1024 + layers * 64 * 4 + 64 + 32 * k0s * 4 + 512
+    return d <= 128 and num_blocks <= 3 and image + 16 + 8 * 16 * (d | 1) * 4 <= 160 * 1024
+
+
+def affine_tail_activation(code):
+    """Scale activations ``fc_affine_coupling_resnet`` evaluates itself."""
+    return code in (AFFINE_SIGMOID_PLUS2, AFFINE_SOFTPLUS_CLAMP3, AFFINE_ADDITIVE, AFFINE_MAF_SOFTPLUS)
+
+
+def affine_coupling_resnet(inputs, id_cols, tr_cols, packed, in_features, num_blocks, activation, inverse=False,
+                           logabsdet_accum=None):
+    """One affine / additive coupling layer with a ResidualNet(hidden <= 64, <= 3 ReLU blocks) conditioner in ONE kernel
+    (``fc_affine_coupling_resnet``); rows a multiple of 16.  Returns ``(outputs, logabsdet)``; with ``logabsdet_accum`` the
+    layer's logabsdet is added onto that tensor, which is returned."""
+    lib = _hip.load()
+    x = _prep_2d(inputs, align16=True)        # the kernel moves whole 16-row chunks with 16-byte loads
+    _hip.require_no_grad(inputs)
+    n, d = x.shape
+    if n % HIDDEN_ROWS != 0 or not affine_tail_activation(activation):
+        raise ValueError("fc_affine_coupling_resnet: unsupported rows / activation")
+    w_frag, w_un, bias_acc = packed
+    ids, cols = _as_cols(id_cols, x.device), _as_cols(tr_cols, x.device)
+    y = torch.empty_like(x)
+    lad, accumulate = _logabsdet_target(logabsdet_accum, n, x.device)
+    _call("fc_affine_coupling_resnet", lib.fc_affine_coupling_resnet, x.device, _hip.ptr(x), _hip.ptr(y), _hip.ptr(ids),
+          _hip.ptr(cols), _hip.ptr(w_frag), _hip.ptr(w_un), _hip.ptr(bias_acc), _hip.ptr(lad), n, d, in_features,
+          cols.numel(), 64, num_blocks, int(activation), 1 if inverse else 0, accumulate, _hip.stream_ptr(x.device))
+    return y, lad
+
+
+def resnet_hidden_packed(inputs, id_cols, packed, in_features, num_blocks, activation=(ACT_RELU, 0.0)):
+    """``resnet_hidden`` (no context) from a ready-made weight image (``device_pack_resnet_hidden_forward``)."""
+    lib = _hip.load()
+    x = _prep_2d(inputs)
+    _hip.require_no_grad(inputs)
+    n, d = x.shape
+    if n % HIDDEN_ROWS != 0:
+        raise ValueError("fc_resnet_hidden needs a multiple of %d rows" % HIDDEN_ROWS)
+    w_frag, w_un, bias_acc = packed
+    k0s = 1 if in_features <= 32 else 2
+    if w_frag.numel() != (k0s + 4 * num_blocks) * 4096 or w_un.numel() != 1 + 2 * num_blocks:
+        raise ValueError("weight image does not match in_features = %d, num_blocks = %d" % (in_features, num_blocks))
+    ids = _as_cols(id_cols, x.device)
+    h = torch.empty(n, 64, dtype=torch.float32, device=x.device)
+    # (timed and reported under the name of the kernel it launches: fc_resnet_hidden with a ready-made image)
+    _call("fc_resnet_hidden", lib.fc_resnet_hidden_packed, x.device, _hip.ptr(x), _hip.ptr(h), _hip.ptr(ids),
+          _hip.ptr(w_frag), _hip.ptr(w_un), _hip.ptr(bias_acc), n, d, in_features, 64, num_blocks, int(activation[0]),
+          float(activation[1]), _hip.stream_ptr(x.device))
+    return h
+
+
+def resnet_hidden_backward(inputs, grad_hidden, id_cols, packed, in_features, num_blocks, grad_inputs_accum=None):
+    """Backward of ``resnet_hidden`` (hidden 64, <= 2 ReLU blocks, no context; rows a multiple of 128): returns
+    ``(grad_x_id [N, in_features], grad_w0 [64, in_features], grad_wb [2 blocks, 64, 64], grad_b [L, 64])`` with the
+    activations recomputed from ``inputs``.  With ``grad_inputs_accum`` [N, D] the gradient wrt the identity columns is
+    added into it in place (``fc_resnet_hidden_backward_accum``) and the first result is None."""
+    lib = _hip.load()
+    x = _prep_2d(inputs.detach())
+    gh = _aligned16(_hip.dev_f32(grad_hidden, "grad_hidden"))
+    n, d = x.shape
+    if n % HIDDEN_BWD_ROWS != 0 or gh.shape != (n, 64) or not 0 <= num_blocks <= 2:
+        raise ValueError("fc_resnet_hidden_backward: unsupported shapes")
+    w_frag, wt_frag, w_un, bias_acc, k0s = packed
+    ids = _as_cols(id_cols, x.device)
+    layers = 1 + 2 * num_blocks
+    if grad_inputs_accum is not None and (grad_inputs_accum.shape != x.shape or not grad_inputs_accum.is_contiguous()
+                                          or grad_inputs_accum.dtype != torch.float32):
+        raise ValueError("grad_inputs_accum must be a contiguous float32 [N, D] tensor")
+    gxid = None if grad_inputs_accum is not None else torch.empty(n, 32 * k0s, dtype=torch.float32, device=x.device)
+    nb2 = max(1, 2 * num_blocks)
+    acc = torch.zeros(64 * 32 * k0s + nb2 * 4096 + layers * 64, dtype=torch.float32, device=x.device)   # one memset
+    gw0 = acc[:64 * 32 * k0s].view(64, 32 * k0s)
+    gwb = acc[64 * 32 * k0s:64 * 32 * k0s + nb2 * 4096].view(nb2, 64, 64)
+    gb = acc[64 * 32 * k0s + nb2 * 4096:].view(layers, 64)
+    fn = lib.fc_resnet_hidden_backward if gxid is not None else lib.fc_resnet_hidden_backward_accum
+    _call("fc_resnet_hidden_backward", fn, x.device, _hip.ptr(x), _hip.ptr(gh), _hip.ptr(ids),
+          _hip.ptr(w_frag), _hip.ptr(wt_frag), _hip.ptr(w_un), _hip.ptr(bias_acc),
+          _hip.ptr(gxid if gxid is not None else grad_inputs_accum), _hip.ptr(gw0),
+          _hip.ptr(gwb), _hip.ptr(gb), n, d, in_features, 64, num_blocks, ACT_RELU, _hip.stream_ptr(x.device))
+    return (None if gxid is None else gxid[:, :in_features]), gw0[:, :in_features], gwb, gb
+
+
+def resnet_hidden_wide(inputs, id_cols, packed, in_features, num_blocks, width, activation=(ACT_RELU, 0.0)):
+    """Hidden layers of a wide conditioner on the rows of ``inputs`` (multiple of 64 rows) -> h [N, width]."""
+    lib = _hip.load()
+    x = _prep_2d(inputs)
+    _hip.require_no_grad(inputs)
+    n, d = x.shape
+    if n % WIDE_ROWS != 0 or width not in (128, 256):
+        raise ValueError("fc_resnet_hidden_wide needs a multiple of %d rows and a width of 128 or 256" % WIDE_ROWS)
+    w_frag, w_un, bias = packed
+    ids = _as_cols(id_cols, x.device)
+    h = torch.empty(n, width, dtype=torch.float32, device=x.device)
+    _call("fc_resnet_hidden_wide", lib.fc_resnet_hidden_wide, x.device, _hip.ptr(x), _hip.ptr(h), _hip.ptr(ids),
+          _hip.ptr(w_frag), _hip.ptr(w_un), _hip.ptr(bias), n, d, in_features, width, num_blocks, int(activation[0]),
+          float(activation[1]), _hip.stream_ptr(x.device))
+    return h
+
+
+def resnet_hidden(inputs, id_cols, packed, in_features, num_blocks, context=None, activation=(ACT_RELU, 0.0),
+                  context_mode=CONTEXT_GLU):
+    """Hidden layers of the conditioner on the rows of ``inputs`` (multiple of 16 rows) -> h [N, 64].
+    ``activation``: ``activation_code`` of the blocks' activation.  ``context_mode``: ``CONTEXT_GLU`` (ResidualNet:
+    concatenated into the initial layer, GLU gate per block) or ``CONTEXT_ADDITIVE`` (MADE: added after the initial
+    layer through the activation and inside every block; ``packed`` then carries ``blocks + 1`` context layers).
+    ``in_features`` = number of identity columns read from ``inputs``; ``context`` [N, C] (C <= 32,
+    in_features + C <= 64) enters the initial layer after them and gates every block (``packed`` then carries
+    the context layers)."""
+    lib = _hip.load()
+    x = _prep_2d(inputs)
+    _hip.require_no_grad(inputs)
+    n, d = x.shape
+    if n % HIDDEN_ROWS != 0:
+        raise ValueError("fc_resnet_hidden needs a multiple of %d rows" % HIDDEN_ROWS)
+    w0, b0, wb, bb = packed[:4]
+    ids = _as_cols(id_cols, x.device)
+    h = torch.empty(n, 64, dtype=torch.float32, device=x.device)
+    if context is None:
+        _call("fc_resnet_hidden", lib.fc_resnet_hidden, x.device, _hip.ptr(x), _hip.ptr(h), _hip.ptr(ids),
+              _hip.ptr(w0), _hip.ptr(b0), _hip.ptr(wb), _hip.ptr(bb), n, d, in_features, 64, num_blocks,
+              int(activation[0]), float(activation[1]), _hip.stream_ptr(x.device))
+        return h
+    wc, bc = packed[4:6]
+    c = _prep_2d(context)
+    _hip.require_no_grad(context)
+    if c.shape[0] != n or w0.shape[1] != in_features + (c.shape[1] if context_mode == CONTEXT_GLU else 0):
+        raise ValueError("context rows / width do not match the inputs / the initial layer")
+    _call("fc_resnet_hidden_context", lib.fc_resnet_hidden_context, x.device, _hip.ptr(x), _hip.ptr(c), _hip.ptr(h),
+          _hip.ptr(ids), _hip.ptr(w0), _hip.ptr(b0), _hip.ptr(wb), _hip.ptr(bb), _hip.ptr(wc), _hip.ptr(bc), n, d,
+          in_features, c.shape[1], 64, num_blocks, int(context_mode), int(activation[0]), float(activation[1]),
+          _hip.stream_ptr(x.device))
+    return h

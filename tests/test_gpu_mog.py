@@ -173,13 +173,13 @@ def test_one_kernel_sampler_against_float64_restatement(case, device):
 
 def _spy(monkeypatch):
     names = []
-    real = ops._call
+    real = ops.mog._call
 
     def call(name, *args):
         names.append(name)
         return real(name, *args)
 
-    monkeypatch.setattr(ops, "_call", call)
+    monkeypatch.setattr(ops.mog, "_call", call)
     return names
 
 

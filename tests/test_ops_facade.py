@@ -1,0 +1,115 @@
+"""The ``ops`` package is a facade over one module per kernel family: every name the single ``ops.py`` exposed still resolves
+on ``flowconductor_amd.ops``, the shared state exists once, ``ops/__init__.py`` holds imports only and every family module
+imports on its own.  Runs off the GPU and without loading the HIP library."""
+import ast
+import inspect
+import os
+import pkgutil
+import subprocess
+import sys
+
+from flowconductor_amd import ops
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# every non-module name of the single-file ``ops`` module, frozen when it was split:
+# sorted(n for n, v in vars(ops).items() if not n.startswith("__") and not isinstance(v, types.ModuleType))
+NAMES = [
+    "ACT_ELU", "ACT_LEAKY_RELU", "ACT_RELU", "ACT_SIGMOID", "ACT_SILU", "ACT_TANH", "AFFINE_ADDITIVE",
+    "AFFINE_MAF_SOFTPLUS", "AFFINE_SCALE_GIVEN", "AFFINE_SCALE_SOFTPLUS", "AFFINE_SHIFT_TANH2", "AFFINE_SIGMOID_PLUS2",
+    "AFFINE_SOFTPLUS_CLAMP3", "CONTEXT_ADDITIVE", "CONTEXT_GLU", "CONV1X1_MAX_CHANNELS", "DEFAULT_MIN_BIN_HEIGHT",
+    "DEFAULT_MIN_BIN_WIDTH", "DEFAULT_MIN_DERIVATIVE", "DevicePack", "EW_CAUCHY_CDF", "EW_EXP", "EW_EXTENDED_SOFTPLUS",
+    "EW_GLU", "EW_LEAKY_RELU", "EW_LOGTANH", "EW_SIGMOID", "EW_SOFTPLUS", "EW_TANH", "FRAG_ELEMS", "FRAG_KSTEP",
+    "FUSED_BINS", "FUSED_DT", "FUSED_HIDDEN", "FUSED_ROWS", "GENERAL_BINS", "GENERAL_HIDDEN", "HDH_MAX_REFLECTIONS",
+    "HIDDEN_BWD_ROWS", "HIDDEN_ROWS", "IRES_ACT_CLIPSWISH", "IRES_ACT_CSIN", "IRES_ACT_ELU", "IRES_ACT_LEAKY_LSWISH",
+    "IRES_ACT_LIPSWISH", "IRES_ACT_RELU", "IRES_ACT_SIN", "IRES_ACT_SWISH", "IRES_ACT_TANH", "IRES_CONCAT_ACTS",
+    "IRES_MAX_DEPTH", "IRES_MAX_DIM", "IRES_MAX_WIDTH", "InputOutsideDomain", "InverseNotAvailable", "KernelTimer",
+    "LAD_ACCUMULATE", "LAD_ACCUMULATE_NEG", "LAD_STORE", "LAD_STORE_NEG", "LINEAR_DENSE", "LINEAR_DENSE_SHIFTED",
+    "LINEAR_LU_FORWARD", "LINEAR_LU_INVERSE", "MADE_AFFINE", "MADE_RQ", "MAX_ROW_FEATURES", "MOG_MAX_COMPONENTS",
+    "MSG_CHOLESKY_FAILED", "MSG_DIAGONAL_NONPOSITIVE", "MSG_NOT_LOWER_TRIANGULAR", "MSG_NOT_POSITIVE_DEFINITE",
+    "MSG_NOT_SQUARE", "MSG_NOT_SYMMETRIC", "PACK_FINAL", "PACK_FINAL_T", "PACK_HIDDEN", "PACK_HIDDEN_T",
+    "PACK_HIDDEN_T0", "PER_SAMPLE_DENSE", "PER_SAMPLE_DENSE_T", "PER_SAMPLE_LU_FORWARD", "PER_SAMPLE_LU_INVERSE",
+    "SPD_MAX_DIM", "SPLINE_CUBIC", "SPLINE_LINEAR", "SPLINE_QUADRATIC", "SYLVESTER_MM_ROWS", "WIDE_ROWS",
+    "_AffineFunction", "_CholeskyOuterFunction", "_Conv1x1Function", "_DeepSigmoidFunction", "_DiagExtractFunction",
+    "_DiagReplaceFunction", "_HDHLinearFunction", "_HouseholderFunction", "_LULinearFunction", "_MoGLogProbFunction",
+    "_PermuteFunction", "_PiecewiseSplineFunction", "_PlanarFunction", "_PointwiseAffineFunction", "_RQSplineFunction",
+    "_SoSFunction", "_SqueezeFunction", "_StdNormalLogProbFunction", "_SylvesterFunction", "_TrilPackFunction",
+    "_UpperLinearFunction", "_a_fragments", "_add_hidden_jobs", "_affine_coupling_nograd", "_aligned16", "_as_cols",
+    "_bias_accumulator_order", "_call", "_check_now", "_cholesky_outer_nograd", "_conv1x1_nograd", "_conv1x1_operand",
+    "_diag_extract_nograd", "_diag_replace_nograd", "_err_word", "_exact_pow2", "_finish", "_flag_for", "_flags",
+    "_hb_perm", "_hdh_operands", "_hidden_image", "_hidden_image_fragments", "_hidden_layer_fragments",
+    "_hidden_linears", "_householder_backward", "_inverse_through_forward", "_ires_operands", "_item_vector",
+    "_logabsdet_target", "_made_pass_prefix", "_matrices", "_mog_log_prob_nograd", "_mog_operands", "_pad4", "_pad_to",
+    "_param", "_permute_nograd", "_pow2_scale", "_prep_2d", "_raise_for", "_rows", "_rq_config", "_spline_config",
+    "_squeeze_nograd", "_standard_normal_log_prob_nograd", "_state", "_tril_pack_nograd", "activation_code",
+    "affine_coupling", "affine_coupling_resnet", "affine_tail_activation", "affine_tail_fits", "batchnorm_eval",
+    "buffer_list", "cache_key", "cached", "capture_mode", "check_errors", "cholesky", "cholesky_outer", "conv1x1",
+    "deep_sigmoid", "deep_sigmoid_autograd", "deep_sigmoid_bound", "deep_sigmoid_fits", "deferred_errors", "dense_mm",
+    "device_pack_affine_coupling", "device_pack_final_layer", "device_pack_made_affine",
+    "device_pack_resnet_hidden_backward", "device_pack_resnet_hidden_forward", "device_plan", "drop_param_list",
+    "elementwise", "fill_triangular", "fused_backward_supported", "fused_general_supported", "fused_linear_supported",
+    "general_hidden_width", "has_hooks", "hdh_linear", "hdh_linear_autograd", "householder", "householder_autograd",
+    "householder_matrix", "invalidate_hip_caches", "iresnet_forward", "iresnet_image_floats", "iresnet_inverse",
+    "iresnet_supported", "linear", "linear_per_sample", "lu_linear_autograd", "made_inverse",
+    "made_inverse_context_fits", "made_mog_sample", "matrix_diagonal", "matrix_replace_diagonal", "memo", "module_list",
+    "mog_log_prob", "mog_log_prob_backward", "pack_final_layer", "pack_final_layer_general",
+    "pack_final_layer_transposed", "pack_made_inverse", "pack_made_inverse_context", "pack_resnet_hidden",
+    "pack_resnet_hidden_backward", "pack_resnet_hidden_wide", "pack_sylvester", "param_list", "permute",
+    "piecewise_spline", "piecewise_spline_autograd", "piecewise_spline_backward_supported", "planar", "planar_autograd",
+    "pointwise_affine", "pointwise_affine_autograd", "resnet_hidden", "resnet_hidden_backward", "resnet_hidden_packed",
+    "resnet_hidden_wide", "rq_fused_linear_backward", "rq_param_count", "rq_spline", "rq_spline_autograd",
+    "rq_spline_backward", "rq_spline_fused_general", "rq_spline_fused_linear", "spline_multiplier", "squeeze",
+    "standard_normal_log_prob", "static_memo", "structure_key", "sum_of_sigmoids", "sum_of_sigmoids_autograd",
+    "sylvester", "sylvester_autograd", "sylvester_mm", "sylvester_mm_supported", "tril_gather", "upper_linear",
+    "upper_linear_autograd"]
+
+MODULES = [m.name for m in pkgutil.iter_modules(ops.__path__)]
+
+
+def test_every_name_resolves():
+    assert len(NAMES) == 256 and sum(n.startswith("_") for n in NAMES) == 68
+    assert [n for n in NAMES if not hasattr(ops, n)] == []
+
+
+def test_definitions_live_in_the_package():
+    homes = {n: getattr(ops, n).__module__ for n in NAMES
+             if inspect.isfunction(getattr(ops, n)) or inspect.isclass(getattr(ops, n))}
+    assert len(homes) >= 133 + 25 + 12          # functions, classes, the run-time cache's re-exports when it was split
+    assert {n: m for n, m in homes.items()
+            if not (m.startswith("flowconductor_amd.ops.") or m == "flowconductor_amd.runtime_cache")} == {}
+
+
+def test_state_exists_once():
+    assert ops._state is ops._core._state
+    assert ops.KernelTimer is ops._core.KernelTimer and ops.KernelTimer._active is ops._core.KernelTimer._active
+    for name in MODULES:
+        module = getattr(ops, name)
+        assert getattr(module, "_state", ops._state) is ops._state
+        assert getattr(module, "_call", ops._call) is ops._core._call
+
+
+def test_init_holds_imports_only():
+    with open(os.path.join(ROOT, "flowconductor_amd", "ops", "__init__.py")) as f:
+        body = ast.parse(f.read()).body
+    assert isinstance(body[0], ast.Expr) and isinstance(body[0].value, ast.Constant) and isinstance(body[0].value.value, str)
+    assert [type(node).__name__ for node in body[1:]] == ["ImportFrom"] * (len(body) - 1)
+    imported = [alias.name for node in body[1:] for alias in node.names]
+    assert all(node.level == 1 and node.module in MODULES for node in body[1:])
+    assert "*" not in imported and len(set(imported)) == len(imported) and set(NAMES) <= set(imported)
+
+
+def test_each_module_imports_alone():
+    """One interpreter that forgets the package between imports: no module needs another one to have been imported first,
+    and none of them loads the HIP library."""
+    script = (
+        "import importlib, sys\n"
+        "for name in sys.argv[1:]:\n"
+        "    for key in [k for k in sys.modules if k.split('.')[0] == 'flowconductor_amd']:\n"
+        "        del sys.modules[key]\n"
+        "    importlib.import_module('flowconductor_amd.ops.' + name)\n"
+        "    assert sys.modules['flowconductor_amd._hip']._lib is None, name\n"
+        "print('imported', len(sys.argv) - 1)\n")
+    assert {"_core", "packing", "rq", "mog", "fused_rq"} <= set(MODULES)
+    done = subprocess.run([sys.executable, "-c", script] + MODULES, cwd=ROOT, capture_output=True, text=True)
+    assert done.returncode == 0, done.stderr
+    assert done.stdout.strip() == "imported %d" % len(MODULES)
