@@ -158,6 +158,7 @@ SIGNATURES = {
     "fc_conv1x1": [_P, _P, _P, _P, _P, _I64, _I32, _I64, _P],
     "fc_iresnet_forward": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "fc_iresnet_inverse": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _P],
+    "fc_umnn": [_P] * 7 + [_I64, _I32, _I32, _I32, _I32, _I32, _I32, _P],
 }
 
 _lib = None

@@ -8,6 +8,7 @@ from flowconductor_amd.transforms.autoregressive import (  # noqa: F401
     MaskedPiecewiseRationalQuadraticAutoregressiveTransform,
     MaskedShiftAutoregressiveTransform,
     MaskedSumOfSigmoidsTransform,
+    MaskedUMNNAutoregressiveTransform,
 )
 from flowconductor_amd.transforms.base import (  # noqa: F401
     CompositeTransform,
@@ -30,6 +31,7 @@ from flowconductor_amd.transforms.conditional import (  # noqa: F401
     ConditionalSVDTransform,
     ConditionalSylvesterTransform,
     ConditionalTransform,
+    ConditionalUMNNTransform,
     PiecewiseLinearConditionalTransform,
 )
 from flowconductor_amd.transforms.coupling import (  # noqa: F401
@@ -40,6 +42,7 @@ from flowconductor_amd.transforms.coupling import (  # noqa: F401
     PiecewiseLinearCouplingTransform,
     PiecewiseQuadraticCouplingTransform,
     PiecewiseRationalQuadraticCouplingTransform,
+    UMNNCouplingTransform,
 )
 from flowconductor_amd.transforms.adaptive_sigmoids import DeepSigmoid, SumOfSigmoids  # noqa: F401
 from flowconductor_amd.transforms.linear import Linear, ScalarScale, ScalarShift  # noqa: F401

@@ -13,6 +13,7 @@ from flowconductor_amd import ops, options
 from flowconductor_amd.transforms import fused_rq
 from flowconductor_amd.transforms import made as made_module
 from flowconductor_amd.transforms.adaptive_sigmoids import DeepSigmoidModule
+from flowconductor_amd.transforms.UMNN import MonotonicNormalizer
 from flowconductor_amd.transforms.base import Transform
 
 
@@ -496,6 +497,45 @@ class MaskedDeepSigmoidTransform(AutoregressiveTransform):
 
     def _elementwise_inverse(self, inputs, autoregressive_params):
         return self._elementwise(inputs, autoregressive_params, inverse=True)
+
+
+class MaskedUMNNAutoregressiveTransform(AutoregressiveTransform):
+    """Unconstrained-monotonic-neural-network AR layer (autoregressive.py:199-261; Wehenkel & Louppe, NeurIPS 2019): the
+    MADE emits ``cond_size`` values per feature, the embedding ``h`` of ``transformer`` (a ``MonotonicNormalizer``):
+    z = h_0 + int_0^x f(t, h) dt, logabsdet = sum log f(x, h).
+
+    integrand_net_layers: hidden widths of the integrand network; cond_size: embedding size per feature; nb_steps:
+    Clenshaw-Curtis steps; solver: "CC" or "CCParallel" (the same arithmetic here).  The inverse runs the host loops
+    (full passes or column at a time); the one-kernel MADE inverse does not take this layer."""
+
+    def __init__(self, features, hidden_features, context_features=None, num_blocks=2, use_residual_blocks=True,
+                 random_mask=False, activation=F.relu, dropout_probability=0.0, use_batch_norm=False,
+                 integrand_net_layers=[50, 50, 50], cond_size=20, nb_steps=20, solver="CCParallel"):
+        self.features = features
+        self.cond_size = cond_size
+        made = _made(self, features, hidden_features, context_features, num_blocks, use_residual_blocks,
+                     random_mask, activation, dropout_probability, use_batch_norm)
+        self._epsilon = 1e-3
+        super().__init__(made)
+        self.transformer = MonotonicNormalizer(integrand_net_layers, cond_size, nb_steps, solver)
+
+    def _output_dim_multiplier(self):
+        return self.cond_size
+
+    def _needs_grad(self, inputs):
+        return super()._needs_grad(inputs) or (torch.is_grad_enabled()
+                                               and any(p.requires_grad for p in self.transformer.parameters()))
+
+    def _embedding(self, inputs, autoregressive_params):
+        # (the column-at-a-time inverse hands over one column and its cond_size parameters)
+        return autoregressive_params.reshape(inputs.shape[0], inputs.shape[1], -1)
+
+    def _elementwise_forward(self, inputs, autoregressive_params):
+        return self.transformer.apply_with_logabsdet(inputs, self._embedding(inputs, autoregressive_params))
+
+    def _elementwise_inverse(self, inputs, autoregressive_params):
+        return self.transformer.apply_with_logabsdet(inputs, self._embedding(inputs, autoregressive_params),
+                                                     inverse=True)
 
 
 def _ar_divisor(net):

@@ -15,6 +15,7 @@ from flowconductor_amd.transforms import fused_rq
 from flowconductor_amd.transforms.coupling import _is_plain_resnet
 from flowconductor_amd.transforms.base import Transform
 from flowconductor_amd.transforms.orthogonal import ParametrizedHouseHolder
+from flowconductor_amd.transforms.UMNN import MonotonicNormalizer
 
 
 class ConditionalTransform(Transform):
@@ -321,6 +322,31 @@ class ConditionalSVDTransform(ConditionalTransform):
         else:
             s = torch.exp(s_raw) + self.eps
         return q_u.contiguous(), q_v.contiguous(), s.contiguous(), bias
+
+
+class ConditionalUMNNTransform(ConditionalTransform):
+    """Unconstrained monotonic neural network whose embedding comes from the context (conditional.py:546-603):
+    ``conditional_net(context)`` emits ``cond_size`` values per feature for ``transformer`` (a ``MonotonicNormalizer``)."""
+
+    def __init__(self, features, hidden_features, context_features=None, num_blocks=2, use_residual_blocks=True,
+                 activation=F.relu, dropout_probability=0.0, use_batch_norm=False, integrand_net_layers=[50, 50, 50],
+                 cond_size=20, nb_steps=20, solver="CCParallel"):
+        self.cond_size = cond_size
+        super().__init__(features=features, hidden_features=hidden_features, context_features=context_features,
+                         num_blocks=num_blocks, use_residual_blocks=use_residual_blocks, activation=activation,
+                         dropout_probability=dropout_probability, use_batch_norm=use_batch_norm)
+        self.transformer = MonotonicNormalizer(integrand_net_layers, cond_size, nb_steps, solver)
+
+    def _output_dim_multiplier(self):
+        return self.cond_size
+
+    def _forward_given_params(self, inputs, conditional_params):
+        return self.transformer.apply_with_logabsdet(
+            inputs, conditional_params.reshape(inputs.shape[0], inputs.shape[1], -1))
+
+    def _inverse_given_params(self, inputs, conditional_params):
+        return self.transformer.apply_with_logabsdet(
+            inputs, conditional_params.reshape(inputs.shape[0], inputs.shape[1], -1), inverse=True)
 
 
 class PiecewiseLinearConditionalTransform(ConditionalTransform):

@@ -15,6 +15,7 @@ import torch
 from flowconductor_amd import ops, options
 from flowconductor_amd.transforms import fused_rq
 from flowconductor_amd.transforms.base import Transform
+from flowconductor_amd.transforms.UMNN import MonotonicNormalizer
 
 
 def _is_plain_resnet(net):
@@ -161,6 +162,51 @@ class CouplingTransform(Transform):
     def _param_rows_nchw(self, transform_params, shape):
         """Conditioner output [B, d_t*mult, H, W] -> per-pixel rows in the 2-D layout."""
         raise NotImplementedError()
+
+
+class UMNNCouplingTransform(CouplingTransform):
+    """Unconstrained-monotonic-neural-network coupling layer (coupling.py:145-209; Wehenkel & Louppe, NeurIPS 2019): the
+    conditioner emits ``cond_size`` values per transformed feature, the embedding of ``transformer`` (a
+    ``MonotonicNormalizer``).  4-D inputs follow the reference's pixel layout (one embedding row [1, C_t cond_size] per
+    pixel, read channel-minor) on the torch composition.
+
+    ``apply_unconditional_transform`` builds the reference's sub-module (a ``MonotonicNormalizer`` with ``cond_size`` 0)
+    so that its ``state_dict`` loads; the reference cannot run that path (it calls the normalizer with the context as
+    ``h``), and neither can this class."""
+
+    def __init__(self, mask, transform_net_create_fn, integrand_net_layers=[50, 50, 50], cond_size=20, nb_steps=20,
+                 solver="CCParallel", apply_unconditional_transform=False):
+        if apply_unconditional_transform:
+            def unconditional_transform(features):
+                return MonotonicNormalizer(integrand_net_layers, 0, nb_steps, solver)
+        else:
+            unconditional_transform = None
+        self.cond_size = cond_size
+        super().__init__(mask, transform_net_create_fn, unconditional_transform=unconditional_transform)
+        self.transformer = MonotonicNormalizer(integrand_net_layers, cond_size, nb_steps, solver)
+
+    def _transform_dim_multiplier(self):
+        return self.cond_size
+
+    def _coupling_kernel(self, inputs, transform_params, inverse):
+        split = inputs[:, self.transform_features]
+        out, logabsdet = self.transformer.apply_with_logabsdet(
+            split, transform_params.reshape(split.shape[0], split.shape[1], -1), inverse=inverse)
+        outputs = inputs.clone()
+        outputs[:, self.transform_features] = out
+        return outputs, logabsdet
+
+    def _run(self, inputs, context, inverse):
+        if inputs.dim() != 4 or self.unconditional_transform is not None:
+            return super()._run(inputs, context, inverse)
+        self._check(inputs)
+        transform_params = self._conditioner(inputs, None, context)
+        rows, shape = _rows_from_nchw(inputs[:, self.transform_features])
+        h = transform_params.permute(0, 2, 3, 1).reshape(rows.shape[0], 1, transform_params.shape[1])
+        out_rows, lad_rows = self.transformer.apply_with_logabsdet(rows, h, inverse=inverse)
+        outputs = inputs.clone()
+        outputs[:, self.transform_features] = _nchw_from_rows(out_rows, shape)
+        return outputs, lad_rows.reshape(shape[0], -1).sum(dim=1)
 
 
 class AffineCouplingTransform(CouplingTransform):

@@ -47,7 +47,8 @@ extern "C" {
  * holds for the invertible-residual-block entries fc_iresnet_forward / fc_iresnet_inverse, for the conditional
  * device loop fc_made_inverse_context and for the mixture-of-Gaussians entries fc_mog_log_prob(_backward) /
  * fc_made_mog_sample(_context), for the Householder-diagonal-Householder entries fc_hdh_linear(_backward) and for the
- * deep-sigmoidal-flow entries fc_deep_sigmoid / fc_deep_sigmoid_backward(_rows)). */
+ * deep-sigmoidal-flow entries fc_deep_sigmoid / fc_deep_sigmoid_backward(_rows) and for the monotonic-integral entry
+ * fc_umnn). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -592,6 +593,36 @@ int fc_deep_sigmoid_backward(const float* x, const float* raw, const float* grad
 /* Workspace rows of the shared-row mode above (a count, not an error code); 0: the row does not fit the reduction's
  * LDS plan, expand it to per-sample rows instead. */
 int fc_deep_sigmoid_backward_rows(int64_t n, int32_t d, int32_t n_sigmoids);
+
+/* ---- unconstrained monotonic neural networks (Clenshaw-Curtis integral of an MLP) --------------- */
+/* z[n, j] = h[n, j, 0] + int_0^x f(t, h[n, j, :]) dt with f = ELU(MLP(t, h)) + 1 and the quadrature
+ *   z = h_0 + (x / 2) sum_i w_i f((x / 2)(s_i + 1), h),  s_i = cos(i pi / nb_steps), i = 0..nb_steps,
+ * jac[n, j] = f(x, h) at the x of the element, logabsdet[n] = sum_j log jac[n, j].  One matrix-core kernel: no
+ * intermediate of size n * d * nb_steps exists.  Replaces MonotonicNormalizer.forward / inverse_transform
+ * (transforms/UMNN/MonotonicNormalizer.py:51-82) with the third-party NeuralIntegral restated, and the jac.log().sum(1)
+ * of its three callers (autoregressive.py:251-261, coupling.py:187-203, conditional.py:593-603).
+ *   x       [n, d]; h [n, d, cond_size], 1 <= cond_size <= FC_UMNN_MAX_COND, all of it (element 0 included) feeds f
+ *   MLP     Linear(1 + cond_size -> w_1) ReLU ... Linear(w_L -> 1), L = hidden_layers in 1..FC_UMNN_MAX_HIDDEN_LAYERS,
+ *           widths <= 64 (zero-padded to 64), given as an image in two parts:
+ *   w_frag  f16, 16-byte aligned: v_mfma_f32_16x16x32_f16 A fragments [layer][k-step][tile][piece (hi, lo)][lane][8] of
+ *           the first layer (64 x 32, one k-step: column 0 -- the weight of t -- ZEROED, columns 1..cond_size the
+ *           embedding) and of the L - 1 hidden 64 x 64 layers (two k-steps); each layer scaled by a power of two that
+ *           lifts its largest entry into [2^14, 2^15); tile t, row 4 g + r holds unit 32 (t >> 1) + 8 g + 4 (t & 1) + r
+ *   aux     f32 [64 L + 128 + 4 + 2 FC_UMNN_POINTS]: biases of the L fragment layers, [g][4 t + r] order; the first
+ *           layer's t column and the last layer's row in the same order; the L inverse scales (padded to 3) and the last
+ *           bias; the tables (s_i + 1) / 2 continued with 1 and w_i continued with 0
+ * inverse != 0: x is the target z; per element a Newton search with f as the slope inside [0, 20] or [-20, 0] (F(0) = h_0
+ * picks the side), stopping at a step below 2^-23 max(|x|, 1, 4 max(|z|, |h_0|) / f); a target beyond F(+-20) returns +-20 (the reference:
+ * 25 bisections of [-20, 20], MonotonicNormalizer.py:67-82); y = the root, jac = f there, logabsdet = -sum log jac.
+ * lad_mode as above, applied to that sign; logabsdet may be NULL.  x != y.  A row's results do not depend on its position
+ * in the batch.  hipErrorInvalidValue for shapes outside the limits. */
+#define FC_UMNN_MAX_COND 31
+#define FC_UMNN_MAX_HIDDEN_LAYERS 3
+#define FC_UMNN_MAX_STEPS 63
+#define FC_UMNN_POINTS 68
+int fc_umnn(const float* x, const float* h, const void* w_frag, const float* aux, float* y, float* jac,
+            float* logabsdet, int64_t n, int32_t d, int32_t cond_size, int32_t hidden_layers, int32_t nb_steps,
+            int32_t inverse, int32_t lad_mode, void* stream);
 
 /* ---- row-per-wavefront bijectors with dense parameters (d <= 512) ------------------------------ */
 /* K Householder reflections out -= (out.q_k)(2/|q_k|^2) q_k, k = 0..K-1 (reverse != 0: K-1..0).
