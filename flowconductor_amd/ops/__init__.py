@@ -47,11 +47,14 @@ from .pointwise import (  # noqa: F401
 from .rowwave import (  # noqa: F401
     HDH_MAX_REFLECTIONS, LINEAR_DENSE, LINEAR_DENSE_SHIFTED, LINEAR_LU_FORWARD, LINEAR_LU_INVERSE, MAX_ROW_FEATURES,
     PER_SAMPLE_DENSE, PER_SAMPLE_DENSE_T, PER_SAMPLE_LU_FORWARD, PER_SAMPLE_LU_INVERSE, SYLVESTER_MM_ROWS,
-    _HDHLinearFunction, _HouseholderFunction, _LULinearFunction, _PlanarFunction, _SylvesterFunction,
-    _UpperLinearFunction, _hdh_operands, _householder_backward, _param, _rows, dense_mm, hdh_linear,
+    _DenseLinearFunction, _HDHLinearFunction, _HouseholderFunction, _LULinearFunction, _PlanarFunction, _SylvesterFunction,
+    _UpperLinearFunction, _hdh_operands, _householder_backward, _param, _rows, dense_linear_autograd, dense_mm, hdh_linear,
     hdh_linear_autograd, householder, householder_autograd, linear, linear_per_sample, lu_linear_autograd, planar,
     planar_autograd, sylvester, sylvester_autograd, sylvester_mm, sylvester_mm_supported, upper_linear,
     upper_linear_autograd)
+from .rownorm import (  # noqa: F401
+    _RadialFunction, _UnitVectorFunction, _radial_inverse_through_forward, radial, radial_autograd, unit_vector,
+    unit_vector_autograd)
 from .sigmoids import (  # noqa: F401
     _DeepSigmoidFunction, _SoSFunction, deep_sigmoid, deep_sigmoid_autograd, deep_sigmoid_bound, deep_sigmoid_fits,
     sum_of_sigmoids, sum_of_sigmoids_autograd)

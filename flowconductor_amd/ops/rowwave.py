@@ -38,6 +38,38 @@ def lu_linear_autograd(inputs, lower, upper, bias, inverse=False):
     return _LULinearFunction.apply(_prep_2d(inputs), lower, upper, bias, inverse)
 
 
+class _DenseLinearFunction(torch.autograd.Function):
+    """``y = W x + b`` / ``y = W^-1 (x - b)`` by the ``fc_linear`` kernel; gradients by library GEMMs on the device
+    (``NaiveLinear`` under autograd, linear.py:159-190).  The inverse direction is handed ``W^-1`` (no graph of its own): with
+    ``gz = gy W^-1`` the gradients are ``gx = gz``, ``dW = -gz^T y``, ``db = -sum gz``."""
+
+    @staticmethod
+    def forward(ctx, inputs, weight, bias, weight_inverse):
+        ctx.inverse = weight_inverse is not None
+        with torch.no_grad():
+            if ctx.inverse:
+                outputs = linear(inputs, weight_inverse, bias=bias, mode=LINEAR_DENSE_SHIFTED)
+                ctx.save_for_backward(outputs, weight_inverse)
+            else:
+                outputs = linear(inputs, weight, bias=bias, mode=LINEAR_DENSE)
+                ctx.save_for_backward(inputs, weight)
+        return outputs
+
+    @staticmethod
+    def backward(ctx, gy):
+        saved, matrix = ctx.saved_tensors
+        if not ctx.inverse:
+            return gy @ matrix, gy.T @ saved, gy.sum(0), None
+        gz = gy @ matrix
+        return gz, -(gz.T @ saved), -gz.sum(0), None
+
+
+def dense_linear_autograd(inputs, weight, bias, weight_inverse=None):
+    """Dense linear map with an autograd node (training / differentiable sampling); with ``weight_inverse`` (``W^-1`` as a
+    tensor without a graph) the inverse direction, whose gradients still reach ``weight`` and ``bias``."""
+    return _DenseLinearFunction.apply(_prep_2d(inputs), weight, bias, weight_inverse)
+
+
 class _UpperLinearFunction(torch.autograd.Function):
     """``y = R x`` / ``y = R^-1 x`` with an upper-triangular ``R`` by the ``fc_linear`` kernel (the inverse is its back
     substitution: ``LINEAR_LU_INVERSE`` with a unit lower factor); gradients by library GEMMs and one triangular solve

@@ -45,13 +45,14 @@ from flowconductor_amd.transforms.coupling import (  # noqa: F401
     UMNNCouplingTransform,
 )
 from flowconductor_amd.transforms.adaptive_sigmoids import DeepSigmoid, SumOfSigmoids  # noqa: F401
-from flowconductor_amd.transforms.linear import Linear, ScalarScale, ScalarShift  # noqa: F401
+from flowconductor_amd.transforms.linear import Linear, NaiveLinear, ScalarScale, ScalarShift  # noqa: F401
 from flowconductor_amd.transforms.lu import LULinear  # noqa: F401
 from flowconductor_amd.transforms.qr import QRLinear  # noqa: F401
 from flowconductor_amd.transforms.svd import SVDLinear  # noqa: F401
 from flowconductor_amd.transforms.no_analytic_inv import (  # noqa: F401
     MonotonicTransform,
     PlanarTransform,
+    RadialTransform,
     SylvesterTransform,
 )
 from flowconductor_amd.transforms.nonlinearities import (  # noqa: F401
@@ -95,3 +96,4 @@ from flowconductor_amd.transforms.matrix import (  # noqa: F401
 from flowconductor_amd.transforms.conv import OneByOneConvolution  # noqa: F401
 from flowconductor_amd.transforms.reshape import SqueezeTransform  # noqa: F401
 from flowconductor_amd.transforms.lipschitz import iResBlock  # noqa: F401
+from flowconductor_amd.transforms.unitvector import UnitVector  # noqa: F401

@@ -1,7 +1,9 @@
-"""Planar and Sylvester flows (API of flowcon/transforms/no_analytic_inv/planar.py:13-169).
+"""Planar, Sylvester and radial flows (API of flowcon/transforms/no_analytic_inv/planar.py:13-214).
 
-Forward direction only, like the reference.  Each is one fused row-per-wavefront HIP kernel.
+Planar and Sylvester: forward direction only, like the reference.  Radial: forward as the reference, plus a closed-form
+inverse the reference does not have.  Each is one fused row-per-wavefront HIP kernel.
 """
+import math
 
 import numpy as np
 import torch
@@ -119,3 +121,55 @@ class SylvesterTransform(Transform):
 
     def inverse(self, inputs, context=None):
         raise ops.InverseNotAvailable()
+
+
+class RadialTransform(Transform):
+    """f(z) = z + beta_hat / (|alpha| + r) (z - z_0), r = |z - z_0|, beta_hat = softplus(beta) - |alpha| >= -|alpha|
+    (https://arxiv.org/abs/1505.05770; parameters ``beta`` [1], ``alpha`` [1], ``z_0`` and the int64 buffer ``d`` as in the
+    reference, whose checkpoints load).  One ``fc_radial`` launch per direction.
+
+    Deliberate differences from the reference: ``inverse`` exists (the reference raises) -- r is the non-negative root of
+    ``r^2 + (|alpha| + beta_hat - rho) r - |alpha| rho = 0`` for ``rho = |y - z_0|``; and a ``z_0`` must carry a leading
+    batch dimension of 1 (``[1, D]``, or ``[1, ...]`` for a norm over all non-batch dimensions, flattened to rows of at most
+    ``ops.MAX_ROW_FEATURES`` values) -- without it the reference's ``vector_norm(dim=[])`` is an accident, here a
+    ``ValueError``."""
+
+    _HIP_AUTOGRAD = True
+
+    def __init__(self, features: int = 2, z_0=None):
+        super().__init__()
+        self.features = features
+        self.register_buffer("d", torch.tensor(self.features))
+        lim = 1.0 / self.features
+        self.beta = nn.Parameter(torch.empty(1))
+        init.uniform_(self.beta, -lim - 1.0, lim - 1.0)
+        self.alpha = nn.Parameter(torch.empty(1))
+        init.uniform_(self.alpha, -lim, lim)
+        if z_0 is not None:
+            if z_0.dim() < 2 or z_0.shape[0] != 1:
+                raise ValueError("RadialTransform: z_0 must have shape [1, ...], got %s" % (tuple(z_0.shape),))
+            if math.prod(z_0.shape[1:]) != features:      # the log-determinant's (d - 1) is the norm's dimension
+                raise ValueError("RadialTransform: z_0 of shape %s does not hold %d features" % (tuple(z_0.shape), features))
+            if math.prod(z_0.shape[1:]) > ops.MAX_ROW_FEATURES:
+                raise ValueError("RadialTransform: z_0 with %d values per sample exceeds the %d supported by the row kernels"
+                                 % (math.prod(z_0.shape[1:]), ops.MAX_ROW_FEATURES))
+            self.z_0 = nn.Parameter(z_0)
+        else:
+            self.z_0 = nn.Parameter(torch.randn(self.features)[None])
+
+    def _map(self, inputs, inverse):
+        if inputs.shape[1:] != self.z_0.shape[1:]:
+            raise ValueError("RadialTransform: inputs of shape %s do not match z_0 of shape %s"
+                             % (tuple(inputs.shape), tuple(self.z_0.shape)))
+        a = torch.abs(self.alpha)
+        b = torch.log(1 + torch.exp(self.beta)) - a
+        if inputs.dim() == 2:
+            return ops.radial_autograd(inputs, self.z_0.reshape(-1), a, b, inverse=inverse)
+        outputs, logabsdet = ops.radial_autograd(inputs.reshape(inputs.shape[0], -1), self.z_0.reshape(-1), a, b, inverse=inverse)
+        return outputs.reshape(inputs.shape), logabsdet
+
+    def forward(self, inputs, context=None):
+        return self._map(inputs, False)
+
+    def inverse(self, inputs, context=None):
+        return self._map(inputs, True)

@@ -1,4 +1,5 @@
 from flowconductor_amd.utils.torchutils import (  # noqa: F401
+    batch_JTJ_logabsdet,
     batch_jacobian,
     cbrt,
     create_alternating_binary_mask,

@@ -90,6 +90,13 @@ def batch_jacobian(g, x):
     return torch.cat(rows, 1)
 
 
+def batch_JTJ_logabsdet(inputs, outputs):
+    """0.5 log det(J^T J) per row for the [B, n_out, n_in] Jacobian of ``outputs`` w.r.t. ``inputs``: the volume change of
+    a map between spaces of different dimension (R^d -> S^d embedded in R^(d+1))."""
+    jacs = batch_jacobian(outputs, inputs)
+    return 0.5 * torch.linalg.slogdet(torch.bmm(torch.transpose(jacs, -2, -1), jacs))[1]
+
+
 def logabsdet(x):
     """log|det x| of a square matrix."""
     return torch.linalg.slogdet(x)[1]

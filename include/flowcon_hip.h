@@ -47,8 +47,8 @@ extern "C" {
  * holds for the invertible-residual-block entries fc_iresnet_forward / fc_iresnet_inverse, for the conditional
  * device loop fc_made_inverse_context and for the mixture-of-Gaussians entries fc_mog_log_prob(_backward) /
  * fc_made_mog_sample(_context), for the Householder-diagonal-Householder entries fc_hdh_linear(_backward) and for the
- * deep-sigmoidal-flow entries fc_deep_sigmoid / fc_deep_sigmoid_backward(_rows) and for the monotonic-integral entry
- * fc_umnn). */
+ * deep-sigmoidal-flow entries fc_deep_sigmoid / fc_deep_sigmoid_backward(_rows), for the monotonic-integral entry
+ * fc_umnn and for the row-norm entries fc_radial(_backward) / fc_unit_vector(_backward)). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -673,6 +673,38 @@ int fc_hdh_linear_backward(const float* y, const float* grad_y, const float* q_a
                            const float* post, float* grad_x, float* grad_q_a, float* grad_q_b, float* grad_scale,
                            float* grad_pre, float* grad_post, int64_t n, int32_t d, int32_t ka, int32_t kb,
                            int32_t reverse_a, int32_t reverse_b, void* stream);
+
+/* ---- row-norm bijectors: radial flow and the stereographic unit-vector map (row width <= 512) --- */
+/* Radial flow (no_analytic_inv/planar.py:199-211), z0 [d] shared, a and b DEVICE scalars (a = |alpha|,
+ * b = softplus(beta) - |alpha|: host-side torch expressions on the parameters, b >= -a).  inverse == 0:
+ *   dz = x - z0, r = |dz|, h = b / (a + r), k = -b r / (a + r)^2;  y = x + h dz;
+ *   logabsdet = (d - 1) log(1 + h) + log(1 + h + k).
+ * inverse != 0 (the reference has none): rho = |y - z0|, r the non-negative root of r^2 + (a + b - rho) r - a rho = 0 --
+ * with q = a + b - rho: 2 a rho / (q + sqrt(q^2 + 4 a rho)) for q > 0, (-q + sqrt(q^2 + 4 a rho)) / 2 otherwise --,
+ * x = z0 + (y - z0) / (1 + b / (a + r)), logabsdet = minus the forward's at that r.  logabsdet may be NULL.  x != y. */
+int fc_radial(const float* x, float* y, float* logabsdet, const float* z0, const float* a, const float* b, int64_t n,
+              int32_t d, int32_t inverse, void* stream);
+
+/* Backward of fc_radial's forward direction: grad_x [n, d] is written, grad_z0 [d], grad_a [1] and grad_b [1] are
+ * ACCUMULATED (atomic adds of per-wave partial sums: zero them first).  grad_logabsdet may be NULL (zeros).  A row exactly
+ * on z0 (r = 0): the reference's autograd yields NaN through the norm's gradient; here the norm's subgradient is taken as
+ * 0 and every gradient stays finite. */
+int fc_radial_backward(const float* x, const float* grad_y, const float* grad_logabsdet, const float* z0, const float* a,
+                       const float* b, float* grad_x, float* grad_z0, float* grad_a, float* grad_b, int64_t n, int32_t d,
+                       void* stream);
+
+/* Stereographic map R^d -> S^d (unitvector.py:18-53); d is the R^d side, d + 1 <= 512.  inverse == 0: x [n, d],
+ * s = |x|^2, y [n, d + 1] = (2 x, s - 1) / (s + 1), logabsdet = d (log 2 - log1p(s)).  inverse != 0: x [n, d + 1] on the
+ * sphere, y [n, d] = x[:d] / (1 - x[d]), logabsdet = -d (log 2 - log1p(|y|^2)); EVERY row with | |x|^2 - 1 | > 1e-4 ORs
+ * FC_ERR_OUTSIDE_DOMAIN into err_flag (the reference tests the batch maximum only).  logabsdet and err_flag may be NULL.
+ * x != y. */
+int fc_unit_vector(const float* x, float* y, float* logabsdet, uint32_t* err_flag, int64_t n, int32_t d, int32_t inverse,
+                   void* stream);
+
+/* Backward of fc_unit_vector in either direction: x_or_y is that direction's INPUT ([n, d] forward, [n, d + 1] inverse),
+ * grad_out the gradient of its output, grad_logabsdet [n] or NULL (zeros); grad_in (the input's shape) is written. */
+int fc_unit_vector_backward(const float* x_or_y, const float* grad_out, const float* grad_logabsdet, float* grad_in,
+                            int64_t n, int32_t d, int32_t inverse, void* stream);
 
 /* Element-wise middle of the backward of fc_sylvester with batch-shared parameters (no_analytic_inv/planar.py:144-166):
  * pre [n, d] = R1 Q^T z + b (recomputed by the caller), grad_act_inout [n, d] = gradient wrt tanh(pre) coming from the
