@@ -163,6 +163,10 @@ SIGNATURES = {
     "fc_radial_backward": [_P] * 10 + [_I64, _I32, _P],
     "fc_unit_vector": [_P] * 4 + [_I64, _I32, _I32, _P],
     "fc_unit_vector_backward": [_P] * 4 + [_I64, _I32, _I32, _P],
+    "fc_bernoulli_log_prob": [_P] * 4 + [_I64, _I32, _P],
+    "fc_bernoulli_log_prob_backward": [_P] * 5 + [_I64, _I32, _P],
+    "fc_bernoulli_sample": [_P] * 3 + [_I64, _I32, _I32, _P],
+    "fc_box_log_prob": [_P] * 4 + [_I64, _I32, _P],
 }
 
 _lib = None

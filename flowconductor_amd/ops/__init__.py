@@ -55,6 +55,8 @@ from .rowwave import (  # noqa: F401
 from .rownorm import (  # noqa: F401
     _RadialFunction, _UnitVectorFunction, _radial_inverse_through_forward, radial, radial_autograd, unit_vector,
     unit_vector_autograd)
+from .discrete import (  # noqa: F401
+    _BernoulliLogProbFunction, bernoulli_log_prob, bernoulli_sample, box_log_prob)
 from .sigmoids import (  # noqa: F401
     _DeepSigmoidFunction, _SoSFunction, deep_sigmoid, deep_sigmoid_autograd, deep_sigmoid_bound, deep_sigmoid_fits,
     sum_of_sigmoids, sum_of_sigmoids_autograd)

@@ -48,7 +48,8 @@ extern "C" {
  * device loop fc_made_inverse_context and for the mixture-of-Gaussians entries fc_mog_log_prob(_backward) /
  * fc_made_mog_sample(_context), for the Householder-diagonal-Householder entries fc_hdh_linear(_backward) and for the
  * deep-sigmoidal-flow entries fc_deep_sigmoid / fc_deep_sigmoid_backward(_rows), for the monotonic-integral entry
- * fc_umnn and for the row-norm entries fc_radial(_backward) / fc_unit_vector(_backward)). */
+ * fc_umnn, for the row-norm entries fc_radial(_backward) / fc_unit_vector(_backward) and for the discrete / uniform base
+ * entries fc_bernoulli_log_prob(_backward), fc_bernoulli_sample and fc_box_log_prob). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -407,6 +408,30 @@ int fc_affine(const float* x, float* y, const float* params, const int32_t* cols
  * Flow._log_prob (flows/base.py:48). */
 int fc_standard_normal_log_prob(const float* z, const float* add, float* out, int64_t n,
                                 int32_t d, float log_z, void* stream);
+
+/* ---- discrete and uniform bases (any d >= 1: the lanes loop over their row) ------------------ */
+/* out[i] = sum_j ( inputs[i,j] * logits[i,j] - softplus(logits[i,j]) ) (+ add[i] when add != NULL), with
+ * softplus(l) = max(l, 0) + log1p(exp(-|l|)): ConditionalIndependentBernoulli._log_prob (distributions/discrete.py:41-56,
+ * -x softplus(-l) - (1 - x) softplus(l) summed over the event) for every real x, not only 0 / 1. */
+int fc_bernoulli_log_prob(const float* inputs, const float* logits, const float* add, float* out, int64_t n, int32_t d,
+                          void* stream);
+
+/* Backward of fc_bernoulli_log_prob from the row gradient grad_out [n]: grad_logits [n, d] = g (x - sigmoid(l)),
+ * grad_inputs [n, d] = g l.  Either output may be NULL (inputs may be NULL when grad_logits is); the gradient of add is
+ * grad_out itself. */
+int fc_bernoulli_log_prob_backward(const float* inputs, const float* logits, const float* grad_out, float* grad_logits,
+                                   float* grad_inputs, int64_t n, int32_t d, void* stream);
+
+/* out[r, j] = noise[r, j] < sigmoid(logits[r / num_samples, j]) ? 1 : 0 for logits [contexts, d] and noise / out
+ * [contexts * num_samples, d] (distributions/discrete.py:58-68 without the repeated probability rows). */
+int fc_bernoulli_sample(const float* logits, const float* noise, float* out, int64_t contexts, int32_t num_samples,
+                        int32_t d, void* stream);
+
+/* out[i] = -sum_j log(high[j] - low[j]) when low[j] <= inputs[i,j] < high[j] for every j, -inf otherwise (a NaN input
+ * fails both comparisons): torch.distributions.Uniform.log_prob summed over the event dimension, as BoxUniform
+ * (distributions/uniform.py:7-29) evaluates it.  low and high are [d]. */
+int fc_box_log_prob(const float* inputs, const float* low, const float* high, float* out, int64_t n, int32_t d,
+                    void* stream);
 
 /* ---- permutation ------------------------------------------------------------------------- */
 /* y[o, j, i] = x[o, perm[j], i] for a tensor viewed as [outer, d, inner]; bit-exact.  x != y.
