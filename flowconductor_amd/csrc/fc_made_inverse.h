@@ -551,16 +551,8 @@ inline hipError_t made_inverse_prepare(const void* z, const void* y, const void*
   if ((((uintptr_t)hidden_frag | (uintptr_t)final_frag | (uintptr_t)final_bias) & 15u) != 0) return hipErrorInvalidValue;
   if (kind == 1) {
     RQParams& q = op.q;
-    q.K = cfg->num_bins; q.tails = cfg->tails ? 1 : 0; q.inverse = 1;
+    q = rq_params_from_config(*cfg, 1);
     if (q.K < 1 || q.K > 16 || params_per_dim != (q.tails ? 3 * q.K - 1 : 3 * q.K + 1)) return hipErrorInvalidValue;
-    q.left = cfg->left; q.right = cfg->right; q.bottom = cfg->bottom; q.top = cfg->top;
-    q.min_w = (float)cfg->min_bin_width; q.min_h = (float)cfg->min_bin_height; q.min_d = (float)cfg->min_derivative;
-    q.cw = (float)(1.0 - cfg->min_bin_width * q.K);
-    q.ch = (float)(1.0 - cfg->min_bin_height * q.K);
-    rq_finish_params(q);
-    q.wh_div = cfg->wh_divisor > 0.f ? cfg->wh_divisor : 1.f;
-    q.beta = cfg->softplus_beta;
-    q.tail_const = cfg->tail_constant;
     op.inv_div = 1.f / q.wh_div;
     op.inv_beta = 1.f / q.beta;
   }

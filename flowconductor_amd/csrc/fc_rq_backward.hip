@@ -210,20 +210,7 @@ extern "C" int fc_rq_spline_backward(const float* x, const float* params, const 
   if (cfg->inverse) return hipErrorInvalidValue;   // gradients of the forward direction only
   if (n == 0) return hipSuccess;
   if (!x || !params || !grad_y || !grad_x || !grad_params) return hipErrorInvalidValue;
-  fc::RQParams q;
-  q.K = cfg->num_bins;
-  q.tails = cfg->tails;
-  q.inverse = 0;
-  q.left = cfg->left; q.right = cfg->right; q.bottom = cfg->bottom; q.top = cfg->top;
-  q.min_w = (float)cfg->min_bin_width;
-  q.min_h = (float)cfg->min_bin_height;
-  q.min_d = (float)cfg->min_derivative;
-  q.cw = (float)(1.0 - cfg->min_bin_width * q.K);
-  q.ch = (float)(1.0 - cfg->min_bin_height * q.K);
-  fc::rq_finish_params(q);
-  q.wh_div = cfg->wh_divisor > 0.f ? cfg->wh_divisor : 1.f;
-  q.beta = cfg->softplus_beta;
-  q.tail_const = cfg->tail_constant;
+  const fc::RQParams q = fc::rq_params_from_config(*cfg, 0);
   fc::RQBackwardArgs a{x, params, cols, grad_y, grad_logabsdet, grad_x, grad_params, n, d, d_t};
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (q.K) {

@@ -38,18 +38,9 @@ extern "C" int fc_rq_spline_fused_linear(const float* x, float* y, const float* 
   if ((((uintptr_t)h | (uintptr_t)x | (uintptr_t)y) & 15u) != 0) return hipErrorInvalidValue;
 
   fc::RQOp<fc::kK> op;
-  fc::RQParams& q = op.q;
-  q.K = cfg->num_bins; q.tails = 1; q.inverse = cfg->inverse;
-  q.left = cfg->left; q.right = cfg->right; q.bottom = cfg->bottom; q.top = cfg->top;
-  q.min_w = (float)cfg->min_bin_width; q.min_h = (float)cfg->min_bin_height; q.min_d = (float)cfg->min_derivative;
-  q.cw = (float)(1.0 - cfg->min_bin_width * q.K);
-  q.ch = (float)(1.0 - cfg->min_bin_height * q.K);
-  fc::rq_finish_params(q);
-  q.wh_div = cfg->wh_divisor > 0.f ? cfg->wh_divisor : 1.f;
-  q.beta = cfg->softplus_beta;
-  q.tail_const = cfg->tail_constant;
-  op.inv_div = 1.f / q.wh_div;
-  op.inv_beta = 1.f / q.beta;
+  op.q = fc::rq_params_from_config(*cfg, cfg->inverse);
+  op.inv_div = 1.f / op.q.wh_div;
+  op.inv_beta = 1.f / op.q.beta;
 
   const int acc = (cfg->flags & FC_RQ_ACCUMULATE_LOGABSDET) ? 1 : 0;
   const int wrows = (cfg->flags & FC_RQ_RAW_WEIGHTS) ? fc::kPP - 1 : fc::kPP;

@@ -27,14 +27,15 @@
 // One 512-thread workgroup per CU walks 32-row tiles.  Wave w owns transformed dims 4w..4w+3 for the whole
 // kernel: both weight pieces stay in 96 VGPRs.  Per 16-sample block a wave issues 36 MFMAs for the NEXT
 // block and evaluates one element per lane of the CURRENT block, hand-interleaved: the evaluation is
-// generated straight-line code with 36 hook points (tools/gen_fused_eval.py), hook n issues MFMA n and pins
-// it with a sched_barrier.
+// straight-line code (fc_rq_eval_straight.inc) with 36 hook points spread evenly over it (fc_rq_eval_plan.h), hook n
+// issues MFMA n and pins it with a sched_barrier.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
 #include "fc_tile.h"
 #include "fc_math.h"
 #include "fc_rq_op.h"
+#include "fc_rq_eval_plan.h"
 #include "fc_rq_fused.h"
 #include "fc_split.h"
 #include "fc_lane.h"
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(512) void rq_fused_linear_kernel3(RQOp<kK> op, Fuse
     };
     bw[t] = f32x4{bias_of(4 * t), bias_of(4 * t + 1), bias_of(4 * t + 2), bias_of(4 * t + 3)};
   }
-  // Knot constants of fc_rq_fused3_eval.inc (x: widths axis, y: heights axis), formed in double once per kernel:
+  // Knot constants of fc_rq_eval_straight.inc (x: widths axis, y: heights axis), formed in double once per kernel:
   // knot_{i+1} = kc_i + (sum of the first i + 1 softmax numerators) * (sc1 / their total) for the lower half, and
   // kc_i - (sum of the last K - 1 - i numerators) * (sc1 / total) for the upper half.
   const double span_x = (double)op.q.right - (double)op.q.left, span_y = (double)op.q.top - (double)op.q.bottom;
@@ -195,11 +196,10 @@ __global__ __launch_bounds__(512) void rq_fused_linear_kernel3(RQOp<kK> op, Fuse
     return f2{(float)((double)op.q.right - span_x * (double)op.q.min_w * (double)(kK - 1 - i)),
               (float)((double)op.q.top - span_y * (double)op.q.min_h * (double)(kK - 1 - i))};
   };
-  const f2 kc0 = knot_const(0), kc1 = knot_const(1), kc2 = knot_const(2), kc3 = knot_const(3), kc4 = knot_const(4),
-           kc5 = knot_const(5), kc6 = knot_const(6);
-  static_assert(kK == 8, "kc0 .. kc6: the generated evaluation is for 8 bins");
+  f2 kc[kK - 1];
+  static_for([&](auto I) { kc[I] = knot_const(I); }, std::make_integer_sequence<int, kK - 1>{});
 
-  // Lane-private bin tables (fc_rq_fused3_eval.inc): slots 0 and K are the interval ends / the linear-tail
+  // Lane-private bin tables (fc_rq_eval_straight.inc): slots 0 and K are the interval ends / the linear-tail
   // derivative constant (rational_quadratic.py:33-36) and never change; slots 1..K-1 are rewritten per element.
   // [slot][lane] layout: every access of a wave is conflict-free whatever the lanes' bin indices are.
   float* ktab = tabs + wave * (kKnotFloats + kDerFloats) + lane * 2;
@@ -344,6 +344,10 @@ __global__ __launch_bounds__(512) void rq_fused_linear_kernel3(RQOp<kK> op, Fuse
         __builtin_amdgcn_s_setprio(3 - ((n + 1) % FC_PRIO_PERIOD) / (FC_PRIO_PERIOD / 4));
       __builtin_amdgcn_sched_barrier(FC_HOOK_MASK);
     };
+    // what fc_rq_eval_straight.inc reads from its scope: two accumulator sets, so hooks sit among the parameter reads too
+    constexpr int K = kK;
+    constexpr bool kTails = true;
+    using Plan = EvalPlan<kK, 6 * kCt3, true, false>;
     const RQParams& q = op.q;
     const float inv_beta = op.inv_beta;   // softplus(x, beta) = log1p(exp(beta x)) * (1 / beta): exact at beta = 1
     float y, lad;
@@ -367,7 +371,7 @@ __global__ __launch_bounds__(512) void rq_fused_linear_kernel3(RQOp<kK> op, Fuse
     y = x + (FC_WH(0) + FC_WH(5) + FC_WH(10) + FC_WH(15) + FC_UD(0) + FC_UD(5)) * 0.f + q.left * 0.f;
     lad = 0.f;
 #else
-#include "fc_rq_fused3_eval.inc"
+#include "fc_rq_eval_straight.inc"
 #endif
 #undef FC_COUNT_GE
 #undef FC_DER_LD

@@ -1,6 +1,6 @@
 // Fused final-Linear + RQ-spline kernel, fourth structure: kernel 3 (fc_rq_fused3.hip) for bin counts other than 8,
 // written once and compiled per shape (one translation unit per bin count and tail mode, fc_rq_fused4_k<K>[_box].hip, which
-// defines FC_F4_K, FC_F4_TAILS, FC_F4_NAME and FC_F4_EVAL_INC before including this file).  hidden_features = 64, linear
+// defines FC_F4_K, FC_F4_TAILS and FC_F4_NAME before including this file).  hidden_features = 64, linear
 // tails or none (coupling.py:543-547: 3K - 1 or 3K + 1 parameters per dim), up to 32 transformed dims.  gfx950.
 //
 //   params[n, :] = W h[n, :] + b        (flowcon/nn/nets/resnet.py:91,99; num_bins defaults to 10, coupling.py:507)
@@ -11,7 +11,7 @@
 //   * ONE accumulator set.  The evaluation reads every raw parameter in its first tenth (the 2K width / height logits
 //     into the softmax registers, the K - 1 derivative logits into the lane's LDS table); from there on the
 //     accumulators are dead, and the 6 CT MFMAs of the NEXT block are issued into them, hooked into the rest of the
-//     evaluation (tools/gen_fused_eval.py --bins K places the hooks after the last read).
+//     evaluation (EvalPlan<.., kHookReads = false>, fc_rq_eval_plan.h, places the hooks after the last read).
 //   * the bias lives in LDS ([wave][g][slot], pre-multiplied like kernel 3's), read back as CT 16-byte loads per element;
 //   * the weights are not split in the kernel: the resident fragments are loaded from the packed image the general
 //     kernel streams (fc_pack_fragments FC_PACK_FINAL: scaled by a power of two per group of 4 dims, two f16 pieces),
@@ -29,6 +29,7 @@
 #include "fc_device.h"
 #include "fc_lane.h"
 #include "fc_math.h"
+#include "fc_rq_eval_plan.h"
 #include "fc_rq_fused_general.h"
 #include "fc_rq_op.h"
 #include "fc_split.h"
@@ -47,6 +48,7 @@ constexpr int P = kTails ? 3 * K - 1 : 3 * K + 1;   // parameters per dim
 constexpr int CT = (P + 3) / 4;         // 16-feature tiles per wave: 4 dims x 4 CT padded parameters
 constexpr int PP = 4 * CT;
 constexpr int NM = 6 * CT;              // MFMAs per 16-sample block: 3 split terms x 2 k-steps x CT tiles
+using Plan = EvalPlan<K, NM, false, !kTails>;   // where the evaluation issues them
 constexpr int R = 32;                   // rows per tile
 constexpr int kHB = 64 + 16;            // f16 per h row in LDS: 160 B (conflict-free ds_read_b128, see fc_rq_fused3.hip)
 constexpr int kBiasRow = 36;            // floats per (wave, g) bias row: 144 B apart, the four rows a wave reads share no bank
@@ -62,11 +64,6 @@ static_assert(PP <= 32 && K <= 11 && K >= 4, "accumulator slots / knot constants
 
 constexpr size_t lds_bytes(int d) {
   return (size_t)kHbufBytes + kLpartBytes + kHscaleBytes + kTabBytes + kBiasBytes + (size_t)3 * R * (d + 4) * 4 + 32 * 4;
-}
-
-template <class F, int... I>
-__device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
 }
 
 // XV: float4 of the x tile per thread; kFull: 32 transformed dims (every wave has spline work); kPadX: D % 4 == 0
@@ -126,13 +123,11 @@ __global__ __launch_bounds__(512) void rq_fused_linear_kernel4(RQOp<K> op, GenAr
   }
   const f32x4* bwp = reinterpret_cast<const f32x4*>(bias_lds + (grp * 4 + g) * kBiasRow);
 
-  // knot constants of the generated evaluation (formed in double on the host, fc_rq_op.h rq_finish_params)
+  // knot constants of the evaluation (formed in double on the host, fc_rq_op.h rq_finish_params)
   const RQParams& q = op.q;
   const f2 sc1 = {q.sc1x, q.sc1y};
-  const f2 kc0 = {q.kcx[0], q.kcy[0]}, kc1 = {q.kcx[1], q.kcy[1]}, kc2 = {q.kcx[2], q.kcy[2]}, kc3 = {q.kcx[3], q.kcy[3]},
-           kc4 = {q.kcx[4], q.kcy[4]}, kc5 = {q.kcx[5], q.kcy[5]}, kc6 = {q.kcx[6], q.kcy[6]}, kc7 = {q.kcx[7], q.kcy[7]},
-           kc8 = {q.kcx[8], q.kcy[8]}, kc9 = {q.kcx[9], q.kcy[9]};
-  (void)kc0; (void)kc1; (void)kc2; (void)kc3; (void)kc4; (void)kc5; (void)kc6; (void)kc7; (void)kc8; (void)kc9;
+  f2 kc[K - 1];
+  static_for([&](auto I) { kc[I] = f2{q.kcx[I], q.kcy[I]}; }, std::make_integer_sequence<int, K - 1>{});
 
   // Lane-private bin tables: knot slots 0 and K are the interval ends and never change, slots 1..K-1 are rewritten per
   // element; derivative slots 0 and K hold the linear-tail constant (rational_quadratic.py:33-36) -- without tails all
@@ -239,7 +234,6 @@ __global__ __launch_bounds__(512) void rq_fused_linear_kernel4(RQOp<K> op, GenAr
     float y, lad;
     __builtin_amdgcn_s_setprio(3);
     __builtin_amdgcn_sched_barrier(0);
-#define FC_HOOK(n) hook(std::integral_constant<int, n>{});
 #define FC_WH_SLOT(i) ((i) < K ? 2 * (i) : 2 * ((i) - K) + 1)
 #define FC_WH(i) __builtin_fmaf(acc[FC_WH_SLOT(i) >> 2][FC_WH_SLOT(i) & 3], c_wh, bw[FC_WH_SLOT(i) >> 2][FC_WH_SLOT(i) & 3])
 #define FC_UD(j) __builtin_fmaf(acc[((j) + 2 * K) >> 2][((j) + 2 * K) & 3], c_ud, bw[((j) + 2 * K) >> 2][((j) + 2 * K) & 3])
@@ -252,7 +246,7 @@ __global__ __launch_bounds__(512) void rq_fused_linear_kernel4(RQOp<K> op, GenAr
     const float fc_b_ = (b);                                                                  \
     asm("v_cmp_ge_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, 0, %0, vcc" : "+v"(count) : "v"(a), "v"(fc_b_) : "vcc"); \
   } while (0)
-#include FC_F4_EVAL_INC
+#include "fc_rq_eval_straight.inc"
 #undef FC_COUNT_GE
 #undef FC_DER_LD
 #undef FC_DER_ST
@@ -261,7 +255,6 @@ __global__ __launch_bounds__(512) void rq_fused_linear_kernel4(RQOp<K> op, GenAr
 #undef FC_UD
 #undef FC_WH
 #undef FC_WH_SLOT
-#undef FC_HOOK
     if (dim_ok) *xr = y;
     lad_out = dim_ok ? lad : 0.f;
   };

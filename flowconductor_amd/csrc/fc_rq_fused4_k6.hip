@@ -1,6 +1,5 @@
-// K = 6, linear tails: instance of the K-generic resident-weight fused kernel (fc_rq_fused4_body.h).
+// K = 6, linear tails: instance of the K-generic resident-weight fused kernel (fc_rq_fused4_body.h), listed in FC_F4_INSTANCES (fc_rq_fused4.hip).
 #define FC_F4_K 6
 #define FC_F4_TAILS 1
 #define FC_F4_NAME k6
-#define FC_F4_EVAL_INC "fc_rq_fused4_eval_k6.inc"
 #include "fc_rq_fused4_body.h"

@@ -16,16 +16,7 @@ extern "C" int fc_rq_fused_linear_backward(int32_t role, const float* x, const f
         (uintptr_t)grad_x | (uintptr_t)grad_h) & 15u) != 0)
     return hipErrorInvalidValue;
 
-  fc::RQParams q;
-  q.K = cfg->num_bins; q.tails = cfg->tails ? 1 : 0; q.inverse = 0;
-  q.left = cfg->left; q.right = cfg->right; q.bottom = cfg->bottom; q.top = cfg->top;
-  q.min_w = (float)cfg->min_bin_width; q.min_h = (float)cfg->min_bin_height; q.min_d = (float)cfg->min_derivative;
-  q.cw = (float)(1.0 - cfg->min_bin_width * q.K);
-  q.ch = (float)(1.0 - cfg->min_bin_height * q.K);
-  fc::rq_finish_params(q);
-  q.wh_div = cfg->wh_divisor > 0.f ? cfg->wh_divisor : 1.f;
-  q.beta = cfg->softplus_beta;
-  q.tail_const = cfg->tail_constant;
+  const fc::RQParams q = fc::rq_params_from_config(*cfg, 0);
 
   fc::BwdArgs a{x, h, grad_y, grad_logabsdet, static_cast<const fc::f16x8*>(w_frag), w_unscale, bias_pad,
                 static_cast<const fc::f16x8*>(wt_frag), cols, grad_x, grad_h, grad_bias_pad, grad_w_pad,

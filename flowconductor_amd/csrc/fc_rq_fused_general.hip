@@ -12,16 +12,7 @@ extern "C" int fc_rq_spline_fused_general(const float* x, float* y, const float*
   if (!x || !y || !h || !w_frag || !w_unscale || !bias_pad || !cols || !logabsdet) return hipErrorInvalidValue;
   if ((((uintptr_t)h | (uintptr_t)x | (uintptr_t)y | (uintptr_t)w_frag) & 15u) != 0) return hipErrorInvalidValue;
 
-  fc::RQParams q;
-  q.K = cfg->num_bins; q.tails = cfg->tails ? 1 : 0; q.inverse = cfg->inverse;
-  q.left = cfg->left; q.right = cfg->right; q.bottom = cfg->bottom; q.top = cfg->top;
-  q.min_w = (float)cfg->min_bin_width; q.min_h = (float)cfg->min_bin_height; q.min_d = (float)cfg->min_derivative;
-  q.cw = (float)(1.0 - cfg->min_bin_width * q.K);
-  q.ch = (float)(1.0 - cfg->min_bin_height * q.K);
-  fc::rq_finish_params(q);
-  q.wh_div = cfg->wh_divisor > 0.f ? cfg->wh_divisor : 1.f;
-  q.beta = cfg->softplus_beta;
-  q.tail_const = cfg->tail_constant;
+  const fc::RQParams q = fc::rq_params_from_config(*cfg, cfg->inverse);
 
   fc::GenArgs a{x, y, h, static_cast<const fc::f16x8*>(w_frag), w_unscale, bias_pad, cols, logabsdet, err_flag,
                 n / fc::kGenRows, d, hidden, d_t, (cfg->flags & FC_RQ_ACCUMULATE_LOGABSDET) ? 1 : 0};

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include "fc_tile.h"
 #include "fc_math.h"
+#include "../../include/flowcon_hip.h"
 
 namespace fc {
 
@@ -43,6 +44,22 @@ inline void rq_finish_params(RQParams& q) {
       q.kcy[i] = (float)((double)q.top - sy * (double)q.min_h * (double)(K - 1 - i));
     }
   }
+}
+
+// host: the C ABI's spline configuration as the kernels' parameter block (`inverse`: the entry's direction -- cfg->inverse,
+// or fixed by the entry).  Every consumer reads `tails` as a truth value.
+inline RQParams rq_params_from_config(const fc_rq_config& cfg, int inverse) {
+  RQParams q;
+  q.K = cfg.num_bins; q.tails = cfg.tails ? 1 : 0; q.inverse = inverse;
+  q.left = cfg.left; q.right = cfg.right; q.bottom = cfg.bottom; q.top = cfg.top;
+  q.min_w = (float)cfg.min_bin_width; q.min_h = (float)cfg.min_bin_height; q.min_d = (float)cfg.min_derivative;
+  q.cw = (float)(1.0 - cfg.min_bin_width * q.K);
+  q.ch = (float)(1.0 - cfg.min_bin_height * q.K);
+  rq_finish_params(q);
+  q.wh_div = cfg.wh_divisor > 0.f ? cfg.wh_divisor : 1.f;
+  q.beta = cfg.softplus_beta;
+  q.tail_const = cfg.tail_constant;
+  return q;
 }
 
 // Walk the K bins of one cumulative axis. u -> LDS pointer to K unnormalised values.
@@ -220,8 +237,8 @@ struct RQOp {
 
   // Branch-free evaluation for linear tails: no early return for out-of-interval inputs (evaluated on a
   // clamped copy, selected away at the end), select-form softplus, direction fixed at compile time.  This is
-  // the readable form of what the fused kernel executes: fc_rq_fused3_eval.inc is this function written out
-  // statement by statement (tools/gen_fused_eval.py) with MFMA hook points in between and the parameters
+  // the readable form of what the fused kernels execute: fc_rq_eval_straight.inc is this function written out
+  // statement by statement with MFMA hook points in between (fc_rq_eval_plan.h) and the parameters
   // taken from accumulator registers instead of `p`.
   template <bool kInverse>
   __device__ __forceinline__ void eval_tails_straight(const float* __restrict__ p, float x, float& y, float& lad,

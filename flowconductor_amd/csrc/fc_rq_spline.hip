@@ -137,20 +137,7 @@ extern "C" int fc_rq_spline(const float* x, float* y, const float* params, const
                             const fc_rq_config* cfg, void* stream) {
   if (!cfg || n < 0 || d <= 0 || d_t <= 0 || d_t > d || cfg->num_bins <= 0) return hipErrorInvalidValue;
   if (n > 0 && (!x || !y || !params)) return hipErrorInvalidValue;
-  fc::RQParams q;
-  q.K = cfg->num_bins;
-  q.tails = cfg->tails;
-  q.inverse = cfg->inverse;
-  q.left = cfg->left; q.right = cfg->right; q.bottom = cfg->bottom; q.top = cfg->top;
-  q.min_w = (float)cfg->min_bin_width;
-  q.min_h = (float)cfg->min_bin_height;
-  q.min_d = (float)cfg->min_derivative;
-  q.cw = (float)(1.0 - cfg->min_bin_width * q.K);
-  q.ch = (float)(1.0 - cfg->min_bin_height * q.K);
-  fc::rq_finish_params(q);
-  q.wh_div = cfg->wh_divisor > 0.f ? cfg->wh_divisor : 1.f;
-  q.beta = cfg->softplus_beta;
-  q.tail_const = cfg->tail_constant;
+  const fc::RQParams q = fc::rq_params_from_config(*cfg, cfg->inverse);
 
   fc::TileArgs a{};
   a.x = x; a.y = y; a.params = params; a.cols = cols; a.logabsdet = logabsdet; a.err = err_flag;

@@ -1,5 +1,5 @@
 """In-kernel clock of the K = 10 resident-weight fused kernel: needs a probe build with FC_F4_STAMP
-(tools/probe/build_f4_variants.sh stamp "-DFC_F4_STAMP" X=1; python tools/probe/fused4_clock.py --lib tools/probe/build/libf4_stamp.so)."""
+(tools/probe/build_f4_variants.sh stamp "-DFC_F4_STAMP"; python tools/probe/fused4_clock.py --lib tools/probe/build/libf4_stamp.so)."""
 import os
 import sys
 import time
