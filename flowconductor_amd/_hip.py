@@ -159,6 +159,8 @@ SIGNATURES = {
     "fc_iresnet_forward": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "fc_iresnet_inverse": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _P],
     "fc_umnn": [_P] * 7 + [_I64, _I32, _I32, _I32, _I32, _I32, _I32, _P],
+    "fc_umnn_backward": [_P] * 11 + [_I64, _I32, _I32, _I32, _I32, _I32, _P],
+    "fc_umnn_backward_workspace": [_I64, _I32, _I32],
     "fc_radial": [_P] * 6 + [_I64, _I32, _I32, _P],
     "fc_radial_backward": [_P] * 10 + [_I64, _I32, _P],
     "fc_unit_vector": [_P] * 4 + [_I64, _I32, _I32, _P],

@@ -75,5 +75,6 @@ from .iresnet import (  # noqa: F401
     IRES_ACT_SIN, IRES_ACT_SWISH, IRES_ACT_TANH, IRES_CONCAT_ACTS, IRES_MAX_DEPTH, IRES_MAX_DIM, IRES_MAX_WIDTH,
     _ires_operands, _pad4, iresnet_forward, iresnet_image_floats, iresnet_inverse, iresnet_supported)
 from .umnn import (  # noqa: F401
-    UMNN_MAX_COND, UMNN_MAX_HIDDEN_LAYERS, UMNN_MAX_STEPS, UMNN_MAX_WIDTH, UMNN_POINTS, pack_umnn, umnn, umnn_fits,
-    umnn_image, umnn_image_floats)
+    UMNN_DOUBLE_BACKWARD_MSG, UMNN_MAX_COND, UMNN_MAX_HIDDEN_LAYERS, UMNN_MAX_STEPS, UMNN_MAX_WIDTH, UMNN_POINTS,
+    _UMNNFunction, pack_umnn, pack_umnn_backward, umnn, umnn_autograd, umnn_backward, umnn_backward_image, umnn_fits,
+    umnn_grad_floats, umnn_image, umnn_image_floats, umnn_unpack_grads)

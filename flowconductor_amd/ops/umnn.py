@@ -103,3 +103,136 @@ def umnn(inputs, h, image, cond_size, nb_steps, inverse=False, lad_mode=LAD_STOR
           _hip.ptr(jac), _hip.ptr(lad), n, d, cond_size, hidden_layers, nb_steps, 1 if inverse else 0, int(lad_mode),
           _hip.stream_ptr(x.device))
     return y, lad, jac
+
+
+# ---- training: fc_umnn_backward ------------------------------------------------------------------------------------------
+UMNN_DOUBLE_BACKWARD_MSG = (
+    "flowconductor_amd: the UMNN kernel route (options 'umnn_training') is once differentiable; for a gradient of a "
+    "gradient (create_graph=True) run the layer with options.override(umnn_training=False), the torch composition")
+
+
+def umnn_grad_floats(hidden_layers):
+    """float32 entries of ``fc_umnn_backward``'s gradient image (layout: include/flowcon_hip.h)."""
+    return 64 * 32 + (hidden_layers - 1) * 64 * 64 + 64 * hidden_layers + 64 + 4
+
+
+def pack_umnn_backward(linears, device):
+    """The transposed image of ``fc_umnn_backward``: ``_hidden_layer_fragments`` of W_l^T for the hidden 64 x 64 layers,
+    then of W1[:, 1:]^T (32 x 64, slot 0 -- t's -- zero), each with the power-of-two scale ``pack_umnn`` gave its layer
+    (the largest entry of a matrix is that of its transpose), rows in accumulator order."""
+    with torch.no_grad():
+        perm = _hb_perm().to(device)
+        mfma = linears[:-1]
+        frags = []
+        for lin in mfma[1:]:
+            w = _pad_to(lin.weight.detach().to(device=device, dtype=torch.float32), (64, 64))
+            sc, _ = _pow2_scale(w.abs().amax().reshape(1))
+            frags.append(_hidden_layer_fragments(w.t().contiguous() * sc, perm))
+        w = _pad_to(mfma[0].weight.detach().to(device=device, dtype=torch.float32), (64, 32)).clone()
+        w[:, 0] = 0
+        sc, _ = _pow2_scale(w.abs().amax().reshape(1))
+        frags.append(_hidden_layer_fragments(w.t().contiguous() * sc, perm[:32]))
+        fragt = torch.cat(frags).contiguous()
+    assert fragt.numel() == (16 * (len(mfma) - 1) + 8) * 512
+    return fragt
+
+
+def umnn_backward_image(owner, linears, device):
+    """``pack_umnn_backward`` of ``owner``'s integrand in the owner's run-time store, keyed as ``umnn_image``."""
+    params = [t for lin in linears for t in (lin.weight, lin.bias)]
+    key = cache_key(*params, extra=(device,))
+    return memo(owner, "umnn_backward_image", key, lambda: pack_umnn_backward(linears, device))
+
+
+def umnn_backward(x, h, image, image_t, grad_out, grad_jac, cond_size, nb_steps, inverse=False):
+    """The raw ``fc_umnn_backward``: ``(grad_in [N, D], grad_h [N, D, cond_size], grad_params [umnn_grad_floats])`` for
+    ``x`` the forward call's input (``inverse``: the root it returned), ``grad_out`` the gradient of the call's output and
+    ``grad_jac`` that of ``jac`` with logabsdet's folded in."""
+    lib = _hip.load()
+    x = _prep_2d(x)
+    emb = _hip.dev_f32(h, "h")
+    go = _hip.dev_f32(grad_out, "grad_out")
+    gj = _hip.dev_f32(grad_jac, "grad_jac")
+    frag, aux = image
+    n, d = x.shape
+    hidden_layers = (frag.numel() // 512 - 8) // 16 + 1
+    if emb.numel() != n * d * cond_size or go.shape != x.shape or gj.shape != x.shape:
+        raise ValueError("flowconductor_amd: umnn_backward: the shapes of h / grad_out / grad_jac do not belong to x")
+    if (frag.device != x.device or aux.device != x.device or image_t.device != x.device
+            or aux.numel() != umnn_image_floats(hidden_layers) or image_t.numel() != (16 * (hidden_layers - 1) + 8) * 512):
+        raise ValueError("flowconductor_amd: the integrand images do not belong to these inputs")
+    gin = torch.empty_like(x)
+    gh = torch.empty((n, d, cond_size), dtype=torch.float32, device=x.device)
+    gp = torch.empty(umnn_grad_floats(hidden_layers), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        floats = lib.fc_umnn_backward_workspace(n, d, hidden_layers)
+    if floats < 0:
+        raise ValueError("flowconductor_amd: umnn_backward: outside the kernel's limits")
+    ws = torch.empty(max(floats, 1), dtype=torch.float32, device=x.device)
+    _call("fc_umnn_backward", lib.fc_umnn_backward, x.device, _hip.ptr(x), _hip.ptr(emb), _hip.ptr(frag), _hip.ptr(aux),
+          _hip.ptr(image_t), _hip.ptr(go), _hip.ptr(gj), _hip.ptr(gin), _hip.ptr(gh), _hip.ptr(gp), _hip.ptr(ws), n, d,
+          cond_size, hidden_layers, nb_steps, 1 if inverse else 0, _hip.stream_ptr(x.device))
+    return gin, gh, gp
+
+
+def umnn_unpack_grads(grad_params, linears):
+    """The padded gradient image as tensors of the shapes of ``linears``' ``weight`` / ``bias``, in that order."""
+    nl = len(linears) - 1
+    o_wh = 64 * 32
+    o_b = o_wh + (nl - 1) * 4096
+    o_wl = o_b + 64 * nl
+    out = []
+    for i, lin in enumerate(linears[:-1]):
+        rows, cols = lin.weight.shape
+        if i == 0:
+            w = grad_params[:o_wh].view(64, 32)
+        else:
+            w = grad_params[o_wh + (i - 1) * 4096:o_wh + i * 4096].view(64, 64)
+        out += [w[:rows, :cols].contiguous(), grad_params[o_b + 64 * i:o_b + 64 * i + rows].clone()]
+    last = linears[-1]
+    out += [grad_params[o_wl:o_wl + last.weight.shape[1]].reshape(last.weight.shape).clone(),
+            grad_params[o_wl + 64:o_wl + 65].reshape(last.bias.shape).clone()]
+    return out
+
+
+class _UMNNFunction(torch.autograd.Function):
+    """``fc_umnn`` with ``fc_umnn_backward``: saves the input (or the root), ``h`` and ``jac`` -- nothing of size
+    N D points exists in either pass."""
+
+    @staticmethod
+    def forward(ctx, inputs, h, owner, linears, cond_size, nb_steps, inverse, *params):
+        device = inputs.device
+        image = umnn_image(owner, linears, nb_steps, device)
+        out, lad, jac = umnn(inputs, h, image, cond_size, nb_steps, inverse=inverse)
+        ctx.image = image
+        ctx.image_t = umnn_backward_image(owner, linears, device)
+        ctx.linears = linears
+        ctx.meta = (cond_size, nb_steps, bool(inverse), tuple(h.shape))
+        ctx.save_for_backward(out if inverse else _prep_2d(inputs), h, jac)
+        return out, lad, jac
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_lad, grad_jac):
+        if torch.is_grad_enabled():
+            raise RuntimeError(UMNN_DOUBLE_BACKWARD_MSG)
+        return _UMNNFunction._backward_once(ctx, grad_out, grad_lad, grad_jac)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _backward_once(ctx, grad_out, grad_lad, grad_jac):
+        x, h, jac = ctx.saved_tensors
+        cond_size, nb_steps, inverse, h_shape = ctx.meta
+        fold = grad_lad.unsqueeze(1) / jac                       # logabsdet = +-sum log jac
+        gj = grad_jac - fold if inverse else grad_jac + fold
+        gin, gh, gp = umnn_backward(x, h, ctx.image, ctx.image_t, grad_out.contiguous(), gj.contiguous(), cond_size,
+                                    nb_steps, inverse=inverse)
+        need = ctx.needs_input_grad
+        grads = [g if need[7 + i] else None for i, g in enumerate(umnn_unpack_grads(gp, ctx.linears))]
+        return (gin if need[0] else None, gh.view(h_shape) if need[1] else None, None, None, None, None, None, *grads)
+
+
+def umnn_autograd(inputs, h, linears, owner, cond_size, nb_steps, inverse=False):
+    """``(outputs, logabsdet, jac)`` of ``umnn`` under autograd: gradients reach ``inputs``, ``h`` and the parameters of
+    ``linears`` through ``fc_umnn_backward`` (the images live in ``owner``'s run-time store).  Once differentiable."""
+    params = [t for lin in linears for t in (lin.weight, lin.bias)]
+    return _UMNNFunction.apply(inputs, h, owner, linears, cond_size, nb_steps, inverse, *params)

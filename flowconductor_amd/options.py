@@ -34,6 +34,9 @@ _DEFAULTS = {
     # fc_pack_fragments launch per layer, ~1 % of a cfg-3 log_prob) -- for code that edits ``.data`` of an eval-mode model
     # and cannot call ``ops.invalidate_hip_caches()`` after it.
     "paranoid_caches": False,
+    # UMNN layers: a call that needs a gradient runs fc_umnn + fc_umnn_backward (the integrand recomputed in the kernel)
+    # instead of the torch composition.  Off until a default can be moved on measured times.
+    "umnn_training": False,
 }
 
 _values = dict(_DEFAULTS)

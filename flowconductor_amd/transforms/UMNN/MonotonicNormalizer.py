@@ -10,13 +10,16 @@ third-party ``UMNN`` package; here the package owns it: Clenshaw-Curtis quadratu
 
 with Leibniz' rule for the gradient (d/dx = f(x, h); the parameters and ``h`` differentiate under the integral sign).
 ``fc_umnn`` (csrc/fc_umnn.hip) runs both directions on the matrix cores for 2-D float32 device tensors in inference;
-everything else takes the torch composition of this file.
+with ``options`` ``umnn_training`` a call that needs a gradient runs the same launch under ``ops.umnn_autograd``, whose
+backward is ``fc_umnn_backward`` (csrc/fc_umnn_backward.hip: the integrand recomputed in the kernel).  Everything else
+takes the torch composition of this file; its inverse under autograd re-attaches the root of the search by the
+implicit-function theorem, so ``x`` carries its gradient with respect to ``z``, ``h`` and the parameters.
 """
 import numpy as np
 import torch
 from torch import nn
 
-from flowconductor_amd import ops
+from flowconductor_amd import ops, options
 
 BRACKET = 20.0          # the inverse searches [-BRACKET, BRACKET] (MonotonicNormalizer.py:69-70)
 BISECTION_STEPS = 25    # (:73)
@@ -156,15 +159,34 @@ class MonotonicNormalizer(nn.Module):
                 lo = torch.where(above, lo, mid)
             return (hi + lo) / 2
 
+    def _needs_grad(self, x, h):
+        return torch.is_grad_enabled() and (x.requires_grad or h.requires_grad
+                                            or any(p.requires_grad for p in self.integrand_net.parameters()))
+
+    def _attached_inverse(self, z, h):
+        """The search's root; under autograd with the implicit-function gradient attached and the value unchanged:
+        x = x_d + (r - r.detach()) / J, r = z - F(x_d) with x_d a constant, so dx = (dz - dF|_x) / J."""
+        xd = self._compose_inverse(z, h)
+        if not self._needs_grad(z, h):
+            return xd
+        image, jac = self._compose(xd, h)
+        r = z - image
+        return xd + (r - r.detach()) / jac.detach()
+
     # ---- the kernel -------------------------------------------------------------------------------------------------
-    def _hip_ok(self, x, h):
+    def _hip_ok(self, x, h, training=False):
+        """Whether the kernel takes the call: in inference (``training`` False: nothing needs a gradient), or -- with
+        ``options`` ``umnn_training`` -- a call that does need one, under the same structural conditions and with the
+        integrand's parameters float32 on the inputs' device."""
         if not (x.dim() == 2 and h.dim() == 3 and x.is_cuda and x.dtype == torch.float32 and h.dtype == torch.float32
                 and h.device == x.device and h.shape[:2] == x.shape and h.shape[2] == self.cond_size
                 and x.numel() > 0 and self.solver in ("CC", "CCParallel")):
             return False
         net = self.integrand_net
-        if torch.is_grad_enabled() and (x.requires_grad or h.requires_grad
-                                        or any(p.requires_grad for p in net.parameters())):
+        if self._needs_grad(x, h) != training:
+            return False
+        if training and not (options.get("umnn_training")
+                             and all(p.dtype == torch.float32 and p.device == x.device for p in net.parameters())):
             return False
 
         def structure_ok():
@@ -184,6 +206,9 @@ class MonotonicNormalizer(nn.Module):
         image = ops.umnn_image(self, self.integrand_net.linears(), self.nb_steps, x.device)
         return ops.umnn(x, h, image, self.cond_size, self.nb_steps, inverse=inverse, lad_mode=lad_mode)
 
+    def _hip_autograd(self, x, h, inverse):
+        return ops.umnn_autograd(x, h, self.integrand_net.linears(), self, self.cond_size, self.nb_steps, inverse=inverse)
+
     # ---- public -----------------------------------------------------------------------------------------------------
     def forward(self, x, h, context=None):
         if self.solver not in ("CC", "CCParallel"):
@@ -191,21 +216,29 @@ class MonotonicNormalizer(nn.Module):
         if self._hip_ok(x, h):
             z, _, jac = self._hip(x, h, False)
             return z, jac
+        if self._hip_ok(x, h, training=True):
+            z, _, jac = self._hip_autograd(x, h, False)
+            return z, jac
         return self._compose(x, h)
 
     def inverse_transform(self, z, h, context=None):
         if self._hip_ok(z, h):
             return self._hip(z, h, True)[0]
-        return self._compose_inverse(z, h)
+        if self._hip_ok(z, h, training=True):
+            return self._hip_autograd(z, h, True)[0]
+        return self._attached_inverse(z, h)
 
     def apply_with_logabsdet(self, inputs, h, inverse=False):
         """What the three transform classes call: ``(outputs, logabsdet [rows])``, logabsdet = +-sum_d log f(x, h).
-        One ``fc_umnn`` launch where the kernel takes the call."""
+        One ``fc_umnn`` launch where the kernel takes the call (and one ``fc_umnn_backward`` in its backward pass)."""
         if self._hip_ok(inputs, h):
             out, lad, _ = self._hip(inputs, h, inverse)
+            return out, lad
+        if self._hip_ok(inputs, h, training=True):
+            out, lad, _ = self._hip_autograd(inputs, h, inverse)
             return out, lad
         if not inverse:
             z, jac = self._compose(inputs, h)
             return z, jac.log().sum(1)
-        x = self._compose_inverse(inputs, h)
+        x = self._attached_inverse(inputs, h)
         return x, -self._compose(x, h)[1].log().sum(1)

@@ -47,8 +47,8 @@ extern "C" {
  * holds for the invertible-residual-block entries fc_iresnet_forward / fc_iresnet_inverse, for the conditional
  * device loop fc_made_inverse_context and for the mixture-of-Gaussians entries fc_mog_log_prob(_backward) /
  * fc_made_mog_sample(_context), for the Householder-diagonal-Householder entries fc_hdh_linear(_backward) and for the
- * deep-sigmoidal-flow entries fc_deep_sigmoid / fc_deep_sigmoid_backward(_rows), for the monotonic-integral entry
- * fc_umnn, for the row-norm entries fc_radial(_backward) / fc_unit_vector(_backward) and for the discrete / uniform base
+ * deep-sigmoidal-flow entries fc_deep_sigmoid / fc_deep_sigmoid_backward(_rows), for the monotonic-integral entries
+ * fc_umnn and fc_umnn_backward(_workspace), for the row-norm entries fc_radial(_backward) / fc_unit_vector(_backward) and for the discrete / uniform base
  * entries fc_bernoulli_log_prob(_backward), fc_bernoulli_sample and fc_box_log_prob). */
 #define FC_ABI_VERSION 3
 
@@ -648,6 +648,33 @@ int fc_deep_sigmoid_backward_rows(int64_t n, int32_t d, int32_t n_sigmoids);
 int fc_umnn(const float* x, const float* h, const void* w_frag, const float* aux, float* y, float* jac,
             float* logabsdet, int64_t n, int32_t d, int32_t cond_size, int32_t hidden_layers, int32_t nb_steps,
             int32_t inverse, int32_t lad_mode, void* stream);
+
+/* Backward of fc_umnn with the integrand recomputed in the kernel (Leibniz' rule: the limits of the quadrature are
+ * constants, dz/dx = jac).  The caller folds logabsdet's gradient into jac's: grad_jac = gjac +- glad / jac.
+ *   inverse == 0: x is the forward call's input, grad_out = gz; grad_in = gx = gz jac + grad_jac df/dt(x, h)
+ *   inverse != 0: x is the ROOT the inverse call returned, grad_out = gx; grad_in = gz = (gx + grad_jac df/dt(x, h)) / jac,
+ *                 and h / the parameters receive the implicit-function gradient through F(x) = z
+ *   grad_h  [n, d, cond_size]
+ *   w_frag, aux  the image of fc_umnn
+ *   wt_frag f16, 16-byte aligned: the same fragment packing applied to the TRANSPOSED weights -- the L - 1 hidden layers
+ *           (W_l^T, 64 x 64, [k-step][tile][piece][lane][8], rows in the unit order above), then W1[:, 1:]^T with slot 0
+ *           zero (32 x 64: two tiles, tile t row 4 g + r holds input slot 8 g + 4 t + r); each shares the power-of-two
+ *           scale of its layer in w_frag
+ *   grad_params f32 [64 * 32 + (L - 1) * 64 * 64 + 64 L + 64 + 4], natural unit order, widths zero-padded to 64:
+ *           gW1 [64][32] (column 0: t, columns 1..: the embedding), gW_l [L - 1][64][64], gb [L][64], the last layer's
+ *           row [64], the last bias [1] (+ 3 of padding).  WRITTEN, not accumulated.
+ *   workspace f32, fc_umnn_backward_workspace(n, d, hidden_layers) entries: per-workgroup partial sums.
+ * Two launches: the recompute + backward, then a fixed-order sum of the workspace rows -- no atomics; grad_params are
+ * bit-identical from run to run, grad_in and grad_h of a row do not depend on its position in the batch.  Limits and
+ * errors as fc_umnn. */
+int fc_umnn_backward(const float* x, const float* h, const void* w_frag, const float* aux, const void* wt_frag,
+                     const float* grad_out, const float* grad_jac, float* grad_in, float* grad_h, float* grad_params,
+                     float* workspace, int64_t n, int32_t d, int32_t cond_size, int32_t hidden_layers, int32_t nb_steps,
+                     int32_t inverse, void* stream);
+
+/* float32 entries of fc_umnn_backward's workspace on the current device (a count, not an error code; -1: outside the
+ * limits). */
+int fc_umnn_backward_workspace(int64_t n, int32_t d, int32_t hidden_layers);
 
 /* ---- row-per-wavefront bijectors with dense parameters (d <= 512) ------------------------------ */
 /* K Householder reflections out -= (out.q_k)(2/|q_k|^2) q_k, k = 0..K-1 (reverse != 0: K-1..0).

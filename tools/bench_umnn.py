@@ -1,5 +1,8 @@
 """Time the UMNN map on the GPU: ``fc_umnn`` forward and inverse, the torch composition, and the reference-style inverse
-(25 bisections + both ends + the closing forward = 28 integrals on the composition), same device, same inputs.
+(25 bisections + both ends + the closing forward = 28 integrals on the composition), same device, same inputs; and one
+training step (forward + backward of a loss on outputs and logabsdet, gradients to x, h and the integrand's parameters) on
+the kernel route (``fc_umnn`` + ``fc_umnn_backward``, options ``umnn_training``) and on the composition in one piece, each
+with its device-event time and its peak ``torch.cuda.max_memory_allocated``.
 
     python tools/bench_umnn.py [--rows 65536] [--features 8] [--repeats 20]
 
@@ -15,7 +18,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from flowconductor_amd import ops  # noqa: E402
+from flowconductor_amd import ops, options  # noqa: E402
 from flowconductor_amd.transforms.UMNN import MonotonicNormalizer  # noqa: E402
 
 F16_DENSE_PEAK = 2.5e15      # flop/s, MI355X matrix cores, f16 dense
@@ -39,7 +42,8 @@ def main():
     ap.add_argument("--rows", type=int, default=65536)
     ap.add_argument("--features", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=20)
-    ap.add_argument("--chunk", type=int, default=8192, help="rows per call of the torch composition")
+    ap.add_argument("--chunk", type=int, default=8192, help="rows per call of the torch composition (inference rows)")
+    ap.add_argument("--train-repeats", type=int, default=3)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -82,6 +86,35 @@ def main():
                 norm.apply_with_logabsdet(x, h)
         torch.cuda.synchronize()
         res["fc_umnn_forward_entry_ms"] = min(timer.durations_ms())
+    # ---- one training step on each route -----------------------------------------------------------------------------
+    gy, gl = torch.randn(n, d, device=dev), torch.randn(n, device=dev)
+
+    def step():
+        xl, hl = x.detach().requires_grad_(True), h.detach().requires_grad_(True)
+        for p in norm.parameters():
+            p.grad = None
+        out, logabsdet = norm.apply_with_logabsdet(xl, hl)
+        ((out * gy).sum() + (logabsdet * gl).sum()).backward()
+        return xl.grad, hl.grad
+
+    grads = {}
+    for route, on in (("kernel", True), ("composition", False)):
+        with options.override(umnn_training=on):
+            step()                                                   # images, workspaces, allocator pools
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            before = torch.cuda.memory_allocated()
+            res["training_step_%s_ms" % route] = timed(step, 0, args.train_repeats)
+            res["training_step_%s_peak_bytes" % route] = torch.cuda.max_memory_allocated()
+            res["training_step_%s_peak_bytes_above_inputs" % route] = torch.cuda.max_memory_allocated() - before
+            grads[route] = [g.clone() for g in step()] + [p.grad.clone() for p in norm.parameters()]
+    res["training_max_grad_diff_kernel_vs_composition_over_largest_entry"] = max(
+        float((a - b).abs().max() / b.abs().max()) for a, b in zip(grads["kernel"], grads["composition"]))
+    with options.override(umnn_training=True), ops.KernelTimer("fc_umnn_backward") as timer:
+        for _ in range(3):
+            step()
+    torch.cuda.synchronize()
+    res["fc_umnn_backward_entry_ms"] = min(timer.durations_ms())
     flop = 3 * 2 * n * d * (22 * 2 * 64 * 64 + 64 * 32)
     res["mfma_flop_forward"] = flop
     res["split_f16_peak_fraction_forward"] = flop / (res["fc_umnn_forward_entry_ms"] * 1e-3) / F16_DENSE_PEAK
