@@ -169,6 +169,10 @@ SIGNATURES = {
     "fc_bernoulli_log_prob_backward": [_P] * 5 + [_I64, _I32, _P],
     "fc_bernoulli_sample": [_P] * 3 + [_I64, _I32, _I32, _P],
     "fc_box_log_prob": [_P] * 4 + [_I64, _I32, _P],
+    "fc_colstats_workspace": [_I32],
+    "fc_batchnorm_train": [_P] * 11 + [_I64, _I32, _F, _F, _P],
+    "fc_column_sums": [_P] * 9 + [_I64, _I32, _P],
+    "fc_batchnorm_train_backward": [_P] * 11 + [_I64, _I32, _P],
 }
 
 _lib = None

@@ -57,6 +57,9 @@ from .rownorm import (  # noqa: F401
     unit_vector_autograd)
 from .discrete import (  # noqa: F401
     _BernoulliLogProbFunction, bernoulli_log_prob, bernoulli_sample, box_log_prob)
+from .colstats import (  # noqa: F401
+    COLSTATS_MAX_PARTIALS, COLSTATS_ROWS_PER_ITERATION, _BatchNormTrainFunction, batch_statistics_route,
+    batch_statistics_supported, batchnorm_train, batchnorm_train_autograd, column_sums)
 from .sigmoids import (  # noqa: F401
     _DeepSigmoidFunction, _SoSFunction, deep_sigmoid, deep_sigmoid_autograd, deep_sigmoid_bound, deep_sigmoid_fits,
     sum_of_sigmoids, sum_of_sigmoids_autograd)

@@ -4,6 +4,7 @@ import torch
 
 from flowconductor_amd import _hip
 from ._core import _as_cols, _call, _err_word, _finish
+from .colstats import batch_statistics_route, column_sums
 
 
 class _PermuteFunction(torch.autograd.Function):
@@ -80,10 +81,23 @@ def pointwise_affine(inputs, scale, shift, inverse=False):
     return y
 
 
+_zeros = {}
+
+
+def _zero(device):
+    """A one-element zero on ``device`` (the shift of a gradient's point-wise map), allocated once."""
+    key = (device.type, device.index)
+    if key not in _zeros:
+        _zeros[key] = torch.zeros(1, dtype=torch.float32, device=device)
+    return _zeros[key]
+
+
 class _PointwiseAffineFunction(torch.autograd.Function):
-    """``pointwise_affine`` with gradients: the HIP kernel forward, broadcasting reductions backward
+    """``pointwise_affine`` with gradients: the HIP kernel forward, reductions over the batch backward
     (y = x s + b: dx = gy s, ds = sum gy x, db = sum gy; inverse y = (x - b) / s: dx = gy / s, ds = -sum gy y / s,
-    db = -sum gy / s) -- ActNorm / point-wise affine layers of a flow that is being trained."""
+    db = -sum gy / s) -- ActNorm / point-wise affine layers of a flow that is being trained.  For [N, D] float32 device
+    gradients with per-feature [D] scale and shift the two sums are one ``fc_column_sums`` and dx the point-wise kernel;
+    every other case (4-D inputs, a scalar scale or shift, a double backward) is the torch expression."""
 
     @staticmethod
     def forward(ctx, inputs, scale, shift, inverse):
@@ -96,6 +110,19 @@ class _PointwiseAffineFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         saved, scale, shift = ctx.saved_tensors
+        d = gy.shape[-1] if gy.dim() == 2 else -1
+        if (not torch.is_grad_enabled() and batch_statistics_route(gy) and saved.shape == gy.shape
+                and saved.dtype == torch.float32 and scale.shape == (d,) and shift.shape == (d,)
+                and scale.dtype == torch.float32 and scale.device == gy.device):
+            gx = None
+            if ctx.needs_input_grad[0]:
+                gx = pointwise_affine(gy, scale, _zero(gy.device), inverse=ctx.inverse)
+            if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+                return gx, None, None, None
+            s1, s2 = column_sums(gy, saved)
+            if ctx.inverse:
+                return gx, -s2 / scale, -s1 / scale, None
+            return gx, s2, s1, None
         s = scale.to(gy.dtype)
         if ctx.inverse:
             gx = gy / s

@@ -37,6 +37,10 @@ _DEFAULTS = {
     # UMNN layers: a call that needs a gradient runs fc_umnn + fc_umnn_backward (the integrand recomputed in the kernel)
     # instead of the torch composition.  Off until a default can be moved on measured times.
     "umnn_training": False,
+    # BatchNorm in training mode and the scale / shift gradients of ActNorm / PointwiseAffineTransform in the
+    # batch-axis reduction kernels (fc_batchnorm_train, fc_batchnorm_train_backward, fc_column_sums) instead of torch
+    # reductions; False selects the torch expressions for A/B measurements.
+    "batch_statistics_kernels": True,
 }
 
 _values = dict(_DEFAULTS)

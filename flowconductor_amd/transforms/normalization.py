@@ -1,8 +1,13 @@
 """Normalisation transforms (API of flowcon/transforms/normalization.py:72-218).
 
-The point-wise maps run in ``fc_pointwise_affine``; batch statistics (BatchNorm in training
-mode, ActNorm's one-off data-dependent initialisation) are cross-batch reductions outside the
-bijector hot path and use torch reductions on the device.
+The point-wise maps run in ``fc_pointwise_affine``.  BatchNorm in training mode runs in the batch-axis reduction kernels
+of ``csrc/fc_colstats.hip``: ``fc_batchnorm_train`` (batch mean and unbiased variance by pairwise-merged moments, the
+running averages, the normalised outputs and the log-determinant's variance term in one entry) and, where a gradient is
+needed, ``fc_batchnorm_train_backward``; the scale / shift gradients of ActNorm come from ``fc_column_sums``.  Those
+kernels take float32 [N, D] device tensors with 2 <= N and D <= ``ops.MAX_ROW_FEATURES`` (512).  Everything else -- CPU
+tensors, other dtypes, wider rows, a batch of one row (whose unbiased variance is the reference's NaN), a double
+backward, 4-D ActNorm gradients, or ``options.override(batch_statistics_kernels=False)`` -- is the reference's expression
+in torch ops, as is ActNorm's one-off data-dependent initialisation.
 """
 import numpy as np
 import torch
@@ -53,11 +58,26 @@ class BatchNorm(Transform):
             self.running_var.lerp_(var.detach(), self.momentum)
         return mean, var
 
+    def _train_kernels(self, inputs):
+        """Training-mode forward on the batch-axis kernels: statistics, running averages, outputs and logabsdet from
+        ``fc_batchnorm_train``; with gradients required behind an autograd node whose backward is
+        ``fc_batchnorm_train_backward`` (gradients flow through the batch statistics)."""
+        stats = (self.eps, self.running_mean, self.running_var, self.momentum)
+        if self._grad_needed(inputs):
+            return ops.batchnorm_train_autograd(inputs, self.weight, self.bias, *stats)
+        with torch.no_grad():
+            weight = self.weight
+            outputs, _, _, _, half_log_sum = ops.batchnorm_train(inputs, weight, self.bias, *stats)
+            return outputs, (torch.log(weight).sum() + half_log_sum) * inputs.new_ones(inputs.shape[0])
+
     def _map(self, inputs, inverse):
-        """Both directions, both execution modes.  With gradients required the map is plain torch arithmetic on the device
-        (training is a cross-batch reduction, SURVEY 8e: not a row-wise kernel; gradients flow through the batch statistics);
-        otherwise the point-wise kernel.  forward: y = w (x - mean) / std + b;  inverse: x = std (y - b) / w + mean."""
+        """Both directions, both execution modes.  Training mode on an input the batch-axis kernels take:
+        ``_train_kernels``.  Otherwise, with gradients required, the map is plain torch arithmetic (gradients flow through
+        the batch statistics), and without them the point-wise kernel.  forward: y = w (x - mean) / std + b;
+        inverse: x = std (y - b) / w + mean."""
         self._check(inputs)
+        if self.training and not inverse and ops.batch_statistics_route(inputs):
+            return self._train_kernels(inputs)
         differentiable = self._grad_needed(inputs)
         mean, var = self._statistics(inputs, differentiable) if not inverse else (self.running_mean, self.running_var)
         std = torch.sqrt(var + self.eps)

@@ -49,7 +49,8 @@ extern "C" {
  * fc_made_mog_sample(_context), for the Householder-diagonal-Householder entries fc_hdh_linear(_backward) and for the
  * deep-sigmoidal-flow entries fc_deep_sigmoid / fc_deep_sigmoid_backward(_rows), for the monotonic-integral entries
  * fc_umnn and fc_umnn_backward(_workspace), for the row-norm entries fc_radial(_backward) / fc_unit_vector(_backward) and for the discrete / uniform base
- * entries fc_bernoulli_log_prob(_backward), fc_bernoulli_sample and fc_box_log_prob). */
+ * entries fc_bernoulli_log_prob(_backward), fc_bernoulli_sample and fc_box_log_prob, and for the batch-statistics entries
+ * fc_batchnorm_train(_backward), fc_column_sums and fc_colstats_workspace). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -432,6 +433,42 @@ int fc_bernoulli_sample(const float* logits, const float* noise, float* out, int
  * (distributions/uniform.py:7-29) evaluates it.  low and high are [d]. */
 int fc_box_log_prob(const float* inputs, const float* low, const float* high, float* out, int64_t n, int32_t d,
                     void* stream);
+
+/* ---- batch statistics: reductions over the batch axis (fc_colstats.hip) -------------------------- */
+/* All of these take [n, d] row-major float32 rows with 2 <= n and 1 <= d <= FC_COLSTATS_MAX_FEATURES and return
+ * hipErrorInvalidValue otherwise.  Every reduction runs in two stages without atomics: at most FC_COLSTATS_MAX_PARTIALS
+ * workgroups each reduce a contiguous slice of rows into one row of `workspace` (fc_colstats_workspace(d) floats, the
+ * caller's, no alignment beyond the 16 bytes of a device allocation needed), one workgroup merges the rows in a fixed
+ * order: the bits of a result depend on (n, d) and on whether the pointers are 16-byte aligned, nothing else.  A stage-1
+ * workgroup walks its slice FC_COLSTATS_ROWS_PER_ITERATION rows at a time when d <= 4 (fewer for wider rows). */
+#define FC_COLSTATS_MAX_FEATURES 512
+#define FC_COLSTATS_MAX_PARTIALS 512
+#define FC_COLSTATS_ROWS_PER_ITERATION 2048
+
+/* Floats of workspace the entries below need for rows of d features (0 for a d out of range). */
+int fc_colstats_workspace(int32_t d);
+
+/* BatchNorm.forward in training mode (transforms/normalization.py:98-141): mean[d] and var[d] = the batch mean and the
+ * unbiased variance of every column (Chan's pairwise merge of per-lane moments, never sum x^2), invstd[d] =
+ * 1 / sqrt(var + eps), half_log_sum[1] = sum_j -0.5 log(var_j + eps), y = weight ((x - mean) invstd) + bias.  When
+ * running_mean / running_var [d] are given (both or neither) they move in place: r += momentum (stat - r). */
+int fc_batchnorm_train(const float* x, const float* weight, const float* bias, float* y, float* mean, float* var,
+                       float* invstd, float* half_log_sum, float* running_mean, float* running_var, float* workspace,
+                       int64_t n, int32_t d, float eps, float momentum, void* stream);
+
+/* s1[j] = sum_i g[i,j], s2[j] = sum_i g[i,j] vh[i,j] with vh = (v - mean) invstd, or v itself when mean and invstd are
+ * NULL (both or neither); gl_sum[1] = sum_i gl[i] when gl [n] is given. */
+int fc_column_sums(const float* g, const float* v, const float* mean, const float* invstd, const float* gl, float* s1,
+                   float* s2, float* gl_sum, float* workspace, int64_t n, int32_t d, void* stream);
+
+/* Backward of fc_batchnorm_train for upstream gradients grad_y [n, d] and grad_logabsdet [n] (or NULL) of
+ * logabsdet[i] = sum_j log weight_j - 0.5 log(var_j + eps):  s1, s2, gl_sum = fc_column_sums(grad_y, x, mean, invstd,
+ * grad_logabsdet) (so grad_bias = s1, grad_weight = s2 + gl_sum / weight), and, unless grad_x is NULL, with
+ * xh = (x - mean) invstd:
+ *   grad_x = weight invstd (grad_y - s1 / n - xh s2 / (n - 1)) - gl_sum invstd xh / (n - 1). */
+int fc_batchnorm_train_backward(const float* x, const float* grad_y, const float* grad_logabsdet, const float* mean,
+                                const float* invstd, const float* weight, float* grad_x, float* s1, float* s2,
+                                float* gl_sum, float* workspace, int64_t n, int32_t d, void* stream);
 
 /* ---- permutation ------------------------------------------------------------------------- */
 /* y[o, j, i] = x[o, perm[j], i] for a tensor viewed as [outer, d, inner]; bit-exact.  x != y.
