@@ -126,6 +126,8 @@ SIGNATURES = {
     "fc_affine_coupling_resnet": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "fc_made_inverse": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, ctypes.POINTER(RQConfig), _P],
     "fc_made_inverse_context": [_P] * 15 + [_I64, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(RQConfig), _P],
+    "fc_made_inverse_sos": [_P] * 11 + [_I64, _I32, _I32, _I32, _I32, _F, _F, _F, _I32, _P],
+    "fc_made_inverse_spline": [_P] * 11 + [_I64, _I32, _I32, ctypes.POINTER(SplineConfig), _I32, _P],
     "fc_mog_log_prob": [_P, _P, _P, _I64, _I32, _I32, _F, _I32, _P],
     "fc_mog_log_prob_backward": [_P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _P],
     "fc_made_mog_sample": [_P] * 11 + [_I64, _I32, _I32, _I32, _F, _P],

@@ -16,7 +16,8 @@
 //     initial layer of pass d + 1;
 //   * the per-column log-determinants add up in the evaluating lane; rows and logabsdet leave once, after pass D - 1.
 //
-// hidden <= 64 (zero-padded), <= 3 residual blocks, ReLU, D <= 64, P <= 48 parameters per dim.
+// hidden <= 64 (zero-padded), <= 3 residual blocks, ReLU, D <= 64, P <= 48 parameters per dim (<= 96 for the
+// sum-of-sigmoids form, whose final-layer fragments then arrive in two halves).
 //
 // A context (made.py:153-162 and the blocks' context_layer, the FC_CONTEXT_ADDITIVE form of fc_resnet_hidden_context)
 // reaches the stack only through terms that do not change from pass to pass:
@@ -36,6 +37,8 @@
 #include "fc_math.h"
 #include "fc_mog_op.h"
 #include "fc_rq_op.h"
+#include "fc_sos_op.h"
+#include "fc_spline_ops.h"
 #include "fc_split.h"
 #include "../../include/flowcon_hip.h"
 
@@ -86,6 +89,19 @@ struct MadeMogArgs : MadeInvArgs, MadeMogNoise {};
 struct MadeMogCtxArgs : MadeInvCtxArgs, MadeMogNoise {};
 constexpr int kMiMog = -1;  // kKind of the mixture column step (the host's FC_MADE_MOG)
 
+// the forms whose stand-alone kernels evaluate an element on a parameter row in LDS (fc_sos_op.h, fc_spline_ops.h: SoSOp,
+// LinearSplineOp, QuadraticSplineOp, CubicSplineOp with `inverse` set): the lane's strip row IS such a row (j = 0, d_t = 1),
+// so the column step is the op's own prepare (raw conditioner outputs -> derived values, in place; every op writes only
+// the P <= 16 PT floats it reads) followed by its eval
+template <class Op>
+struct MadeFormArgs : MadeInvArgs {
+  Op form;
+};
+constexpr int kMiForm = -2;  // kKind of that column step (the host's FC_MADE_SOS / FC_MADE_SPLINE)
+// parameter tiles whose final-layer fragments are requested before the hidden stack; beyond three tiles the rest follows
+// once the stack is through (six tiles at once are 96 registers held across the whole stack)
+constexpr int mi_first_tiles(int pt) { return pt > 3 ? (pt + 1) / 2 : pt; }
+
 // kind: 0 = affine (P = 2: unconstrained scale, shift), 1 = rational-quadratic spline with a run-time bin count (parameters read
 // from the strip as they are needed), 8 / 10 = the same with K = 8 / 10 bins fixed at compile time: the lane copies its 3K -/+ 1
 // parameters from its strip and runs the unrolled evaluation of the stand-alone kernels (RQOp<K>::eval_core, two-sided knot walk);
@@ -100,6 +116,8 @@ template <int NB, int K0S, int PT, int kKind, int BPW, class Args = MadeInvArgs>
 __global__ __launch_bounds__(kMiThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void made_inverse_kernel(Args a, RQOp<(kKind > 1 ? kKind : 0)> op) {
   constexpr bool kCtx = std::is_base_of<MadeInvCtxArgs, Args>::value;
   constexpr bool kMog = kKind == kMiMog;
+  constexpr bool kForm = kKind == kMiForm;
+  constexpr int PH = mi_first_tiles(PT);
   constexpr int kLayers = 1 + 2 * NB, kMiPS = mi_strip_row(PT);
   constexpr int kFrag0 = K0S * 4 * 2, kFragL = 2 * 4 * 2, kFrags = kFrag0 + 2 * NB * kFragL;
   extern __shared__ __attribute__((aligned(16))) unsigned char msm[];
@@ -267,13 +285,13 @@ __global__ __launch_bounds__(kMiThreads) __attribute__((amdgpu_waves_per_eu(2, 2
         }
       }
       // the final-layer fragments of dim d: requested now, used after the hidden stack
-      f16x8 fh[2][PT], fl[2][PT];
+      f16x8 fh[2][PH], fl[2][PH];
+      const f16x8* fr = a.ffrag + (size_t)d * 2 * PT * 2 * 64 + lane;
       {
-        const f16x8* fr = a.ffrag + (size_t)d * 2 * PT * 2 * 64 + lane;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-          for (int t = 0; t < PT; ++t) {
+          for (int t = 0; t < PH; ++t) {
             fh[ks][t] = fr[((ks * PT + t) * 2 + 0) * 64];
             fl[ks][t] = fr[((ks * PT + t) * 2 + 1) * 64];
           }
@@ -369,17 +387,42 @@ __global__ __launch_bounds__(kMiThreads) __attribute__((amdgpu_waves_per_eu(2, 2
           }
         }
         FC_EACH_BLOCK un[b] = make_operand(nts_c, h[b], bh[b], bl[b]);
+        // the other PT - PH tiles' fragments: requested here, multiplied after the first PH
+        [[maybe_unused]] f16x8 gh[2][PT > PH ? PT - PH : 1], gl[2][PT > PH ? PT - PH : 1];
+        if constexpr (PT > PH) {
+#pragma unroll
+          for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+            for (int t = PH; t < PT; ++t) {
+              gh[ks][t - PH] = fr[((ks * PT + t) * 2 + 0) * 64];
+              gl[ks][t - PH] = fr[((ks * PT + t) * 2 + 1) * 64];
+            }
+        }
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
 #pragma unroll
-          for (int t = 0; t < PT; ++t)
+          for (int t = 0; t < PH; ++t)
             FC_EACH_BLOCK pacc[b][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fl[ks][t], bh[b][ks], pacc[b][t], 0, 0, 0);
 #pragma unroll
-          for (int t = 0; t < PT; ++t)
+          for (int t = 0; t < PH; ++t)
             FC_EACH_BLOCK pacc[b][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh[ks][t], bl[b][ks], pacc[b][t], 0, 0, 0);
 #pragma unroll
-          for (int t = 0; t < PT; ++t)
+          for (int t = 0; t < PH; ++t)
             FC_EACH_BLOCK pacc[b][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh[ks][t], bh[b][ks], pacc[b][t], 0, 0, 0);
+        }
+        if constexpr (PT > PH) {
+#pragma unroll
+          for (int ks = 0; ks < NKS; ++ks) {
+#pragma unroll
+            for (int t = PH; t < PT; ++t)
+              FC_EACH_BLOCK pacc[b][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(gl[ks][t - PH], bh[b][ks], pacc[b][t], 0, 0, 0);
+#pragma unroll
+            for (int t = PH; t < PT; ++t)
+              FC_EACH_BLOCK pacc[b][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(gh[ks][t - PH], bl[b][ks], pacc[b][t], 0, 0, 0);
+#pragma unroll
+            for (int t = PH; t < PT; ++t)
+              FC_EACH_BLOCK pacc[b][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(gh[ks][t - PH], bh[b][ks], pacc[b][t], 0, 0, 0);
+          }
         }
       };
       switch ((units + 15) >> 4) {
@@ -425,6 +468,11 @@ __global__ __launch_bounds__(kMiThreads) __attribute__((amdgpu_waves_per_eu(2, 2
           yv = mog_draw(p, a.c, a.eps, zmine, umine);
           // (the density pass reuses the lane's strip row as scratch: the next pass rewrites it)
           ladv = mog_log_density(strip + (g * 16 + s16) * kMiPS, a.c, a.eps, yv);
+        } else if constexpr (kForm) {
+          // the lane's strip row is private to it: derived parameters in place, then the op's inverse on them
+          float* prow = strip + (g * 16 + s16) * kMiPS;
+          a.form.prepare(prow, 0, 1);
+          a.form.eval(prow, 0, 1, zmine, yv, ladv, err);
         } else {
           static_assert(kKind == 1 || PT == 2, "3K -/+ 1 parameters in two 16-row tiles");
           op.template eval_core<false>(p, zmine, yv, ladv, err);     // K static (8 / 10): the unrolled two-sided walk on the strip
@@ -480,16 +528,49 @@ constexpr size_t mi_total_lds(int nb, int k0s, int pt, int bpw) {
   return mi_lds_bytes(nb, k0s, pt, bpw) + (kMiHasContext<Args> ? mi_ctx_lds_bytes(nb) : 0);
 }
 
-// two blocks per wave need their registers: all forms without a context carry a pair; with one, see the .hip file's table
+// two blocks per wave need their registers: the affine and rational-quadratic forms without a context carry a pair; with a
+// context the table above decides, whatever the form (mi_pairs_fit_registers asks it first); see the .hip file's table
 // mixture sampler without a context: the pair spills (20-76 bytes of scratch per lane) with two k-steps of inputs (D > 32) and
 // one or two blocks at three parameter tiles, or three blocks at two (kernel-resource-usage, DESIGN.md "Mixture-of-Gaussians
 // MADE"); with a context the table above holds for it as well
 constexpr bool mi_mog_pairs_fit_registers(int nb, int k0s, int pt) {
   return !(k0s == 2 && ((nb >= 1 && pt == 3) || (nb == 3 && pt == 2)));
 }
+// sum-of-sigmoids and sibling-spline forms: every one-block instantiation is free of scratch; the pair is kept where it is
+// too, and dropped where it spills 8-100 bytes per lane (kernel-resource-usage of every candidate, DESIGN.md "Device loop:
+// sum-of-sigmoids and sibling splines"; shapes whose pair does not fit the LDS never get here)
+template <class Op>
+constexpr bool mi_form_pairs_fit_registers(int nb, int k0s, int pt);
+template <>
+constexpr bool mi_form_pairs_fit_registers<SoSOp>(int nb, int k0s, int pt) {
+  return !((pt == 3 && ((k0s == 2 && (nb == 1 || nb == 2)) || (k0s == 1 && nb == 3))) || (pt >= 5 && nb == 1 && k0s == 2) ||
+           (pt == 5 && nb == 2 && k0s == 1));
+}
+template <>
+constexpr bool mi_form_pairs_fit_registers<LinearSplineOp>(int nb, int k0s, int pt) {
+  return !(k0s == 2 && ((pt == 3 && (nb == 1 || nb == 2)) || (pt == 2 && nb == 3)));
+}
+template <>
+constexpr bool mi_form_pairs_fit_registers<QuadraticSplineOp>(int nb, int k0s, int pt) {
+  return !(nb >= 1 && ((k0s == 2 && pt >= 2) || (k0s == 1 && pt == 3 && nb >= 2)));
+}
+template <>
+constexpr bool mi_form_pairs_fit_registers<CubicSplineOp>(int nb, int k0s, int pt) {
+  return !(nb >= 1 && ((k0s == 2 && pt >= 2) || (k0s == 1 && pt == 3)));
+}
+template <class Args>
+struct MiFormOf {
+  using type = void;
+};
+template <class Op>
+struct MiFormOf<MadeFormArgs<Op>> {
+  using type = Op;
+};
 template <class Args>
 constexpr bool mi_pairs_fit_registers(int nb, int k0s, int pt, int kind) {
   if (kMiHasContext<Args>) return mi_ctx_pairs_fit_registers(nb, k0s, pt, kind);
+  using Form = typename MiFormOf<Args>::type;
+  if constexpr (!std::is_void<Form>::value) return mi_form_pairs_fit_registers<Form>(nb, k0s, pt);
   return kind != kMiMog || mi_mog_pairs_fit_registers(nb, k0s, pt);
 }
 
@@ -613,5 +694,68 @@ hipError_t dispatch_made_mog(const Args& a, int num_blocks, hipStream_t s) {
   }
 #undef FC_MM
 }
+
+// ---- sum-of-sigmoids and sibling-spline forms (fc_made_inverse_sos*.hip, fc_made_inverse_spline*.hip) ---------------------
+// argument checks both entries share (made_inverse_prepare's, with the form's own parameter limit); hipSuccess with
+// *run = false: nothing to do (n == 0)
+inline hipError_t made_form_prepare(const void* z, const void* y, const void* logabsdet, const void* hidden_frag,
+                                    const void* hidden_unscale, const void* hidden_bias, const void* final_frag,
+                                    const void* final_unscale, const void* final_bias, int64_t n, int32_t d, int32_t num_blocks,
+                                    int32_t params_per_dim, int32_t max_params, bool* run) {
+  *run = false;
+  if (n < 0 || d < 1 || d > 64 || num_blocks < 0 || num_blocks > 3) return hipErrorInvalidValue;
+  if (params_per_dim < 1 || params_per_dim > max_params) return hipErrorInvalidValue;
+  if (n % 16 != 0) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  if (!z || !y || !logabsdet || !hidden_frag || !hidden_unscale || !hidden_bias || !final_frag || !final_unscale || !final_bias)
+    return hipErrorInvalidValue;
+  if ((((uintptr_t)hidden_frag | (uintptr_t)final_frag | (uintptr_t)final_bias) & 15u) != 0) return hipErrorInvalidValue;
+  *run = true;
+  return hipSuccess;
+}
+
+template <class Op>
+MadeFormArgs<Op> made_form_args(const float* z, float* y, float* logabsdet, const void* hidden_frag, const float* hidden_unscale,
+                                const float* hidden_bias, const void* final_frag, const float* final_unscale,
+                                const float* final_bias, const int32_t* units_needed, uint32_t* err_flag, int64_t n, int32_t d,
+                                int32_t params_per_dim, int32_t lad_flags, const Op& form) {
+  return MadeFormArgs<Op>{{z, y, logabsdet, static_cast<const f16x8*>(hidden_frag), hidden_unscale, hidden_bias,
+                           static_cast<const f16x8*>(final_frag), final_unscale, final_bias, err_flag, units_needed, n / 16, d,
+                           params_per_dim, (lad_flags & FC_RQ_ACCUMULATE_LOGABSDET) ? 1 : 0},
+                          form};
+}
+
+// parameter tiles FIRST .. LAST of one form (one translation unit per form and tile range: compile time)
+template <int NB, int K0S, int FIRST, int LAST, class Args>
+hipError_t dispatch_made_form_pt(const Args& a, hipStream_t s) {
+  const RQOp<0> op{};
+  const int pt = (a.P + 15) / 16;
+  if constexpr (FIRST <= 1 && 1 <= LAST) if (pt == 1) return launch_made_inverse<NB, K0S, 1, kMiForm>(a, op, s);
+  if constexpr (FIRST <= 2 && 2 <= LAST) if (pt == 2) return launch_made_inverse<NB, K0S, 2, kMiForm>(a, op, s);
+  if constexpr (FIRST <= 3 && 3 <= LAST) if (pt == 3) return launch_made_inverse<NB, K0S, 3, kMiForm>(a, op, s);
+  if constexpr (FIRST <= 4 && 4 <= LAST) if (pt == 4) return launch_made_inverse<NB, K0S, 4, kMiForm>(a, op, s);
+  if constexpr (FIRST <= 5 && 5 <= LAST) if (pt == 5) return launch_made_inverse<NB, K0S, 5, kMiForm>(a, op, s);
+  if constexpr (FIRST <= 6 && 6 <= LAST) if (pt == 6) return launch_made_inverse<NB, K0S, 6, kMiForm>(a, op, s);
+  return hipErrorInvalidValue;
+}
+
+template <int FIRST, int LAST, class Args>
+hipError_t dispatch_made_form(const Args& a, int num_blocks, hipStream_t s) {
+  const bool wide = a.D > 32;
+#define FC_MF(NBV) \
+  case NBV:        \
+    return wide ? dispatch_made_form_pt<NBV, 2, FIRST, LAST>(a, s) : dispatch_made_form_pt<NBV, 1, FIRST, LAST>(a, s);
+  switch (num_blocks) {
+    FC_MF(0) FC_MF(1) FC_MF(2) FC_MF(3)
+    default: return hipErrorInvalidValue;
+  }
+#undef FC_MF
+}
+
+// defined in the translation units that hold the instantiations
+hipError_t dispatch_made_sos_wide(const MadeFormArgs<SoSOp>& a, int num_blocks, hipStream_t s);              // PT 4 .. 6
+hipError_t dispatch_made_spline_linear(const MadeFormArgs<LinearSplineOp>& a, int num_blocks, hipStream_t s);
+hipError_t dispatch_made_spline_quadratic(const MadeFormArgs<QuadraticSplineOp>& a, int num_blocks, hipStream_t s);
+hipError_t dispatch_made_spline_cubic(const MadeFormArgs<CubicSplineOp>& a, int num_blocks, hipStream_t s);
 
 }  // namespace fc

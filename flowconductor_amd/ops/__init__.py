@@ -34,9 +34,10 @@ from .affine import (  # noqa: F401
     _standard_normal_log_prob_nograd, affine_coupling, standard_normal_log_prob)
 from .conditioner import (  # noqa: F401
     ACT_ELU, ACT_LEAKY_RELU, ACT_RELU, ACT_SIGMOID, ACT_SILU, ACT_TANH, CONTEXT_ADDITIVE, CONTEXT_GLU, HIDDEN_BWD_ROWS,
-    HIDDEN_ROWS, MADE_AFFINE, MADE_RQ, WIDE_ROWS, activation_code, affine_coupling_resnet, affine_tail_activation,
-    affine_tail_fits, made_inverse, made_inverse_context_fits, resnet_hidden, resnet_hidden_backward,
-    resnet_hidden_packed, resnet_hidden_wide)
+    HIDDEN_ROWS, MADE_AFFINE, MADE_RQ, MADE_SOS, MADE_SPLINE, WIDE_ROWS, activation_code, affine_coupling_resnet,
+    affine_tail_activation, affine_tail_fits, made_inverse, made_inverse_context_fits, made_inverse_form_fits,
+    made_inverse_param_limit, made_inverse_row_limit, resnet_hidden, resnet_hidden_backward, resnet_hidden_packed,
+    resnet_hidden_wide)
 from .mog import (  # noqa: F401
     MOG_MAX_COMPONENTS, _MoGLogProbFunction, _mog_log_prob_nograd, _mog_operands, made_mog_sample, mog_log_prob,
     mog_log_prob_backward)

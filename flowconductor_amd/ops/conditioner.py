@@ -6,6 +6,7 @@ import torch
 from flowconductor_amd import _hip
 from ._core import _aligned16, _as_cols, _call, _err_word, _finish, _logabsdet_target, _prep_2d
 from .rq import DEFAULT_MIN_BIN_HEIGHT, DEFAULT_MIN_BIN_WIDTH, DEFAULT_MIN_DERIVATIVE, _rq_config
+from .splines import SPLINE_LINEAR, _spline_config, spline_multiplier
 from .affine import AFFINE_ADDITIVE, AFFINE_MAF_SOFTPLUS, AFFINE_SIGMOID_PLUS2, AFFINE_SOFTPLUS_CLAMP3
 
 
@@ -45,6 +46,39 @@ WIDE_ROWS = 64
 HIDDEN_BWD_ROWS = 128
 
 MADE_AFFINE, MADE_RQ = 0, 1
+# forms with entries of their own: the mixture sampler is 2 (FC_MADE_MOG, ops/mog.py)
+MADE_SOS, MADE_SPLINE = 3, 4
+
+
+def made_inverse_param_limit(kind):
+    """Parameters per dim the device loop holds for ``kind``: six 16-row tiles for the sum of sigmoids (S <= 31; the
+    reference's default S = 30 has 91), three for every other form."""
+    return 96 if kind == MADE_SOS else 48
+
+
+# Rows x sigmoids up to which ``fc_made_inverse_sos`` beats the host loop (MI355X, DESIGN.md "Device loop: sum-of-sigmoids
+# and sibling splines"): one lane per sample runs the root search, so beyond one full round of the chip (2^15 rows) the kernel
+# grows with rows x S, while the host loop's stand-alone kernel spreads the elements over all lanes.  Measured at S = 6, 15,
+# 30 and D = 8, 32, 64: ahead at every shape up to 2^16 rows x 30 sigmoids, level or behind at twice that.
+MADE_SOS_ROW_SIGMOIDS = 30 << 16
+
+
+def made_inverse_row_limit(kind, per_dim):
+    """Most rows for which the device loop of ``kind`` is the default route, or None for no limit (the affine,
+    rational-quadratic and sibling-spline forms win at every measured size)."""
+    if kind != MADE_SOS:
+        return None
+    return MADE_SOS_ROW_SIGMOIDS // max(1, (per_dim - 1) // 3)
+
+
+def made_inverse_form_fits(features, num_blocks, per_dim):
+    """LDS budget of ``fc_made_inverse_sos`` / ``fc_made_inverse_spline`` (fc_made_inverse.h ``mi_lds_bytes``, one 16-row
+    block per wave): the hidden stack's image and the waves' parameter strips in 160 KB.  Only D > 32 with three blocks and
+    six parameter tiles does not fit."""
+    k0s = 1 if features <= 32 else 2
+    pt = -(-per_dim // 16)
+    image = (k0s * 8 + 2 * num_blocks * 16) * 1024 + (1 + 2 * num_blocks) * 256 + 64 + 8 * 16 * (16 * pt + 4) * 4
+    return 0 <= num_blocks <= 3 and features <= 64 and 1 <= per_dim <= 96 and image <= 160 * 1024
 
 
 def made_inverse_context_fits(features, num_blocks, per_dim):
@@ -62,7 +96,10 @@ def made_inverse(inputs, packed, num_blocks, per_dim, kind, rq=None, logabsdet_a
     """The D passes of an autoregressive inverse in ONE kernel (``fc_made_inverse``): ``inputs`` [N, D <= 64] (rows a
     multiple of 16), ``packed`` from ``pack_made_inverse``; ``kind`` ``MADE_AFFINE`` or ``MADE_RQ`` (``rq``: keyword
     arguments of the spline as for ``rq_spline``).  With ``context`` [N, C <= 32] and ``context_pack`` from
-    ``pack_made_inverse_context`` the conditional form (``fc_made_inverse_context``).  Returns ``(outputs, logabsdet)``."""
+    ``pack_made_inverse_context`` the conditional form (``fc_made_inverse_context``).  ``MADE_SOS`` (``rq``: ``n_sigmoids``,
+    ``offset``, ``iterations``, ``lim``, ``log_scale_postact`` as for ``sum_of_sigmoids``) and ``MADE_SPLINE`` (``rq``: the
+    keyword arguments of ``piecewise_spline``) run ``fc_made_inverse_sos`` / ``fc_made_inverse_spline``, which take no
+    context.  Returns ``(outputs, logabsdet)``."""
     lib = _hip.load()
     z = _prep_2d(inputs)
     _hip.require_no_grad(inputs)
@@ -82,6 +119,10 @@ def made_inverse(inputs, packed, num_blocks, per_dim, kind, rq=None, logabsdet_a
         cf, cu, cb = context_pack
         if cf.numel() != (1 + num_blocks) * 4096 or cu.numel() != 1 + num_blocks or cb.numel() != (1 + num_blocks) * 64:
             raise ValueError("made_inverse: context_pack does not match num_blocks = %d" % num_blocks)
+    if kind in (MADE_SOS, MADE_SPLINE):
+        if context is not None:
+            raise ValueError("made_inverse: the sum-of-sigmoids and sibling-spline forms take no context")
+        return _made_inverse_form(lib, z, packed, num_blocks, per_dim, kind, dict(rq), logabsdet_accum)
     cfg = None
     if kind == MADE_RQ:
         rq = dict(rq)
@@ -112,6 +153,46 @@ def made_inverse(inputs, packed, num_blocks, per_dim, kind, rq=None, logabsdet_a
     _call("fc_made_inverse", lib.fc_made_inverse, z.device, _hip.ptr(z), _hip.ptr(y), _hip.ptr(lad), _hip.ptr(hf),
           _hip.ptr(hu), _hip.ptr(hb), _hip.ptr(ff), _hip.ptr(fu), _hip.ptr(fb), _hip.ptr(need), _hip.ptr(err), n, d, num_blocks, per_dim,
           kind, cfg, _hip.stream_ptr(z.device))
+    _finish(True)
+    return y, lad
+
+
+def _made_inverse_form(lib, z, packed, num_blocks, per_dim, kind, form, logabsdet_accum):
+    """``made_inverse`` for ``MADE_SOS`` / ``MADE_SPLINE``: launched and timed under the entries' own names."""
+    n, d = z.shape
+    if kind == MADE_SOS:
+        sigmoids = form.pop("n_sigmoids")
+        want = 3 * sigmoids + 1
+        tail = (sigmoids, int(form.pop("iterations", 50)), float(form.pop("lim", 120.0)), float(form.pop("offset", 0.0)),
+                float(form.pop("log_scale_postact", 0.0)))
+    else:
+        spline, bins, tails = form.pop("kind"), form.pop("num_bins"), form.pop("tails", None)
+        if tails not in (None, "linear"):
+            raise RuntimeError("{} tails are not implemented.".format(tails))
+        want = spline_multiplier(spline, bins, tails)
+        min_w = form.pop("min_bin_width", DEFAULT_MIN_BIN_WIDTH)
+        min_h = form.pop("min_bin_height", DEFAULT_MIN_BIN_HEIGHT)
+        if spline != SPLINE_LINEAR and (min_w * bins > 1.0 or min_h * bins > 1.0):
+            raise ValueError("Minimal bin width / height too large for the number of bins")
+        cfg = _spline_config(spline, bins, tails, form.pop("tail_bound", 1.0),
+                             (form.pop("left", 0.0), form.pop("right", 1.0), form.pop("bottom", 0.0), form.pop("top", 1.0)),
+                             min_w, min_h, form.pop("width_divisor", 1.0), form.pop("height_divisor", 1.0), True)
+        tail = (cfg,)
+    if form:
+        raise TypeError("made_inverse: unknown arguments %s" % sorted(form))
+    if per_dim != want or per_dim > made_inverse_param_limit(kind) or not made_inverse_form_fits(d, num_blocks, per_dim):
+        raise ValueError("made_inverse: no instantiation for D = %d, %d blocks, %d parameters per dim (the form has %d)"
+                         % (d, num_blocks, per_dim, want))
+    hf, hu, hb, ff, fu, fb, need = packed
+    if need.dtype != torch.int32 or need.numel() != d:
+        raise ValueError("made_inverse: units_needed must hold one int32 per dim")
+    y = torch.empty_like(z)
+    lad, flags = _logabsdet_target(logabsdet_accum, n, z.device)
+    err = _err_word(z.device, True)
+    name = "fc_made_inverse_sos" if kind == MADE_SOS else "fc_made_inverse_spline"
+    _call(name, getattr(lib, name), z.device, _hip.ptr(z), _hip.ptr(y), _hip.ptr(lad), _hip.ptr(hf), _hip.ptr(hu),
+          _hip.ptr(hb), _hip.ptr(ff), _hip.ptr(fu), _hip.ptr(fb), _hip.ptr(need), _hip.ptr(err), n, d, num_blocks, *tail,
+          flags, _hip.stream_ptr(z.device))
     _finish(True)
     return y, lad
 

@@ -104,14 +104,17 @@ class AutoregressiveTransform(Transform):
 
     # ---- the D passes on the device (round 4) -----------------------------------------------------------------------
     def _device_loop_form(self):
-        """``(kind, parameters per dim, spline keyword arguments)`` of the element-wise inverse ``fc_made_inverse`` knows,
-        or None (the other forms keep the host loop)."""
+        """``(kind, parameters per dim, keyword arguments of the form)`` of the element-wise inverse the device loop knows
+        (``fc_made_inverse``: affine, rational-quadratic; ``fc_made_inverse_sos`` / ``fc_made_inverse_spline``: sum of
+        sigmoids, piecewise linear / quadratic / cubic), or None (deep sigmoid, UMNN and shift keep the host loop)."""
         return None
 
     def _device_loop_ok(self, inputs, context):
-        """One kernel for the whole inverse (``fc_made_inverse``): a residual-block MADE with hidden <= 64, <= 3 ReLU
-        blocks, no batch norm / active dropout / hooks, D <= 64, float32 rows on the device, inference only.  A net with
-        context layers called with a context takes ``fc_made_inverse_context`` where that kernel has the shape."""
+        """One kernel for the whole inverse (``fc_made_inverse``, or the form's own entry): a residual-block MADE with
+        hidden <= 64, <= 3 ReLU blocks, no batch norm / active dropout / hooks, D <= 64, float32 rows on the device,
+        inference only, at most ``ops.made_inverse_param_limit`` parameters per dim in an image that fits the LDS
+        (``ops.made_inverse_form_fits``) and at most ``ops.made_inverse_row_limit`` rows.  A net with context layers called with a context takes
+        ``fc_made_inverse_context`` where that kernel has the shape (affine and rational-quadratic forms only)."""
         net = self.autoregressive_net
         if context is not None:
             return self._device_loop_context_ok(inputs, context)
@@ -125,11 +128,17 @@ class AutoregressiveTransform(Transform):
             code = ops.activation_code(net.activation) if isinstance(net, made_module.MADE) else None
             return (form is not None and isinstance(net, made_module.MADE) and inputs.shape[1] == net.initial_layer.in_features
                     and not hasattr(net, "context_layer") and len(net.blocks) <= 3 and net.hip_hidden_supported(None)
-                    and code is not None and code[0] == ops.ACT_RELU and form[1] <= 48
+                    and code is not None and code[0] == ops.ACT_RELU and form[1] <= ops.made_inverse_param_limit(form[0])
+                    and ops.made_inverse_form_fits(inputs.shape[1], len(net.blocks), form[1])
                     and net.final_layer.out_features == form[1] * inputs.shape[1])
 
-        return (ops.static_memo(self, "device_loop_ok", (inputs.shape[1],) + ops.structure_key(net), structure_ok)
-                and not ops.has_hooks(net))
+        if not (ops.static_memo(self, "device_loop_ok", (inputs.shape[1],) + ops.structure_key(net), structure_ok)
+                and not ops.has_hooks(net)):
+            return False
+        # (a form whose kernel falls behind the host loop on very large batches hands those back)
+        form = self._device_loop_form()
+        limit = ops.made_inverse_row_limit(form[0], form[1])
+        return limit is None or inputs.shape[0] <= limit
 
     def _device_loop_context_ok(self, inputs, context):
         """The conditional form (``fc_made_inverse_context``): everything ``_device_loop_ok`` asks without a context, a
@@ -146,6 +155,8 @@ class AutoregressiveTransform(Transform):
 
         def structure_ok():
             form = self._device_loop_form()
+            if form is not None and form[0] not in (ops.MADE_AFFINE, ops.MADE_RQ):
+                return False                # the other forms have no conditional device loop
             code = ops.activation_code(net.activation) if isinstance(net, made_module.MADE) else None
             return (form is not None and isinstance(net, made_module.MADE) and inputs.shape[1] == net.initial_layer.in_features
                     and hasattr(net, "context_layer") and all(hasattr(b, "context_layer") for b in net.blocks)
@@ -459,6 +470,11 @@ class MaskedSumOfSigmoidsTransform(AutoregressiveTransform):
     def _elementwise_inverse(self, inputs, autoregressive_params):
         return ops.sum_of_sigmoids_autograd(inputs, autoregressive_params, self.n_sigmoids, inverse=True, offset=0.5)
 
+    def _device_loop_form(self):
+        # (the constants ops.sum_of_sigmoids_autograd hands to the stand-alone kernel)
+        return (ops.MADE_SOS, self._output_dim_multiplier(),
+                dict(n_sigmoids=self.n_sigmoids, offset=0.5, iterations=50, lim=120.0, log_scale_postact=0.0))
+
 
 class MaskedDeepSigmoidTransform(AutoregressiveTransform):
     """Deep-sigmoidal-flow AR layer (autoregressive/deep_sigmoid.py): the MADE emits ``3 * n_sigmoids`` raw values per
@@ -467,8 +483,8 @@ class MaskedDeepSigmoidTransform(AutoregressiveTransform):
 
     The inverse deliberately extends the reference, whose ``_elementwise_inverse`` raises ``NotImplementedError("..")``:
     the module's numerical inverse runs per pass of the host loop (or per column of the column-at-a-time path), which
-    gives ``inverse`` and ``Flow.sample``.  The one-kernel MADE inverse does not take this layer (``3S`` parameters per
-    dim are beyond what it holds)."""
+    gives ``inverse`` and ``Flow.sample``.  The one-kernel MADE inverse does not take this layer (it has no column step
+    for the deep sigmoidal flow's numerical inverse)."""
 
     class DeepSigmoidMadeModule(DeepSigmoidModule):
         def forward(self, inputs, context=None):
@@ -561,6 +577,9 @@ class MaskedPiecewiseLinearAutoregressiveTransform(AutoregressiveTransform):
         return ops.piecewise_spline_autograd(inputs, autoregressive_params, None, kind=ops.SPLINE_LINEAR,
                                     num_bins=self.num_bins, inverse=inverse)
 
+    def _device_loop_form(self):
+        return (ops.MADE_SPLINE, self._output_dim_multiplier(), dict(kind=ops.SPLINE_LINEAR, num_bins=self.num_bins))
+
     def _elementwise_forward(self, inputs, autoregressive_params):
         return self._elementwise(inputs, autoregressive_params)
 
@@ -600,6 +619,14 @@ class MaskedPiecewiseQuadraticAutoregressiveTransform(AutoregressiveTransform):
                                     min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
                                     width_divisor=_ar_divisor(self.autoregressive_net), inverse=inverse)
 
+    def _device_loop_form(self):
+        if self.tails not in (None, "linear"):
+            return None
+        return (ops.MADE_SPLINE, self._output_dim_multiplier(),
+                dict(kind=ops.SPLINE_QUADRATIC, num_bins=self.num_bins, tails=self.tails, tail_bound=self.tail_bound,
+                     min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
+                     width_divisor=_ar_divisor(self.autoregressive_net)))
+
     def _elementwise_forward(self, inputs, autoregressive_params):
         return self._elementwise(inputs, autoregressive_params)
 
@@ -627,6 +654,11 @@ class MaskedPiecewiseCubicAutoregressiveTransform(AutoregressiveTransform):
         return ops.piecewise_spline_autograd(inputs, autoregressive_params, None, kind=ops.SPLINE_CUBIC,
                                     num_bins=self.num_bins, width_divisor=div, height_divisor=div,
                                     inverse=inverse)
+
+    def _device_loop_form(self):
+        div = _ar_divisor(self.autoregressive_net)
+        return (ops.MADE_SPLINE, self._output_dim_multiplier(),
+                dict(kind=ops.SPLINE_CUBIC, num_bins=self.num_bins, width_divisor=div, height_divisor=div))
 
     def _elementwise_forward(self, inputs, autoregressive_params):
         return self._elementwise(inputs, autoregressive_params)

@@ -50,7 +50,8 @@ extern "C" {
  * deep-sigmoidal-flow entries fc_deep_sigmoid / fc_deep_sigmoid_backward(_rows), for the monotonic-integral entries
  * fc_umnn and fc_umnn_backward(_workspace), for the row-norm entries fc_radial(_backward) / fc_unit_vector(_backward) and for the discrete / uniform base
  * entries fc_bernoulli_log_prob(_backward), fc_bernoulli_sample and fc_box_log_prob, and for the batch-statistics entries
- * fc_batchnorm_train(_backward), fc_column_sums and fc_colstats_workspace). */
+ * fc_batchnorm_train(_backward), fc_column_sums and fc_colstats_workspace), and for the device loops of the
+ * sum-of-sigmoids and sibling-spline layers fc_made_inverse_sos / fc_made_inverse_spline). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -372,6 +373,19 @@ int fc_piecewise_spline(const float* x, float* y, const float* params, const int
                         int32_t shared_params, int32_t lad_mode, const fc_spline_config* cfg,
                         void* stream);
 
+/* fc_made_inverse (above) for the sibling splines: the D passes of MaskedPiecewise{Linear,Quadratic,Cubic}
+ * AutoregressiveTransform.inverse (autoregressive.py:321-526) in ONE kernel.  z, y, logabsdet, the hidden-stack image, the
+ * final-layer fragments, units_needed, err_flag, n % 16 == 0, d <= 64 and num_blocks <= 3 mean what they mean for
+ * fc_made_inverse; the parameters per dim follow from cfg: K (linear), 2K - 1 / 2K + 1 (quadratic with / without linear
+ * tails), 2K + 2 (cubic), at most 48.  Pass c hands the raw final-layer rows of dim c to one lane per sample, which derives
+ * widths / heights in place and evaluates the inverse exactly as fc_piecewise_spline does (cfg->inverse is ignored).
+ * Without tails an input outside [bottom, top] sets FC_ERR_OUTSIDE_DOMAIN.  lad_flags: FC_RQ_ACCUMULATE_LOGABSDET or 0.
+ * Shapes out of range return hipErrorInvalidValue.  Added under ABI version 3 (it changes no existing entry). */
+int fc_made_inverse_spline(const float* z, float* y, float* logabsdet, const void* hidden_frag, const float* hidden_unscale,
+                           const float* hidden_bias, const void* final_frag, const float* final_unscale,
+                           const float* final_bias, const int32_t* units_needed, uint32_t* err_flag, int64_t n, int32_t d,
+                           int32_t num_blocks, const fc_spline_config* cfg, int32_t lad_flags, void* stream);
+
 /* Backward of fc_piecewise_spline in the forward direction (cfg->inverse == 0), per-sample rows: grad_x [n, d] (the
  * d_t transformed columns are written; the caller owns the identity columns) and grad_params [n, d_t P] from grad_y
  * [n, d] and grad_logabsdet [n] (NULL = zeros).  What torch.autograd yields for splines/linear.py:38-105,
@@ -611,6 +625,21 @@ int fc_sum_of_sigmoids(const float* x, float* y, const float* params, const int3
                        int32_t n_sigmoids, int32_t inverse, int32_t bisection_iterations,
                        float bisection_lim, float offset, float log_scale_postact,
                        int32_t shared_params, int32_t lad_mode, void* stream);
+
+/* fc_made_inverse for the sum-of-sigmoids layer: the D passes of MaskedSumOfSigmoidsTransform.inverse
+ * (autoregressive.py:266-318) in ONE kernel.  z, y, logabsdet, the hidden-stack image, the final-layer fragments,
+ * units_needed, err_flag, n % 16 == 0, d <= 64 and num_blocks <= 3 mean what they mean for fc_made_inverse, with
+ * params_per_dim = 3 n_sigmoids + 1 <= 96 (PT <= 6 parameter tiles: n_sigmoids <= 31, the reference's default is 30).  Pass c
+ * hands the raw final-layer rows of dim c to one lane per sample, which derives the parameters in place and runs the
+ * numerical inverse exactly as fc_sum_of_sigmoids does with the same bisection_iterations, bisection_lim, offset (the AR
+ * layer: 0.5) and log_scale_postact.  lad_flags: FC_RQ_ACCUMULATE_LOGABSDET or 0.  d > 32 with num_blocks == 3 and more
+ * than 80 parameters per dim exceeds the 160 KB of LDS; that and every other shape out of range return
+ * hipErrorInvalidValue.  Added under ABI version 3 (it changes no existing entry). */
+int fc_made_inverse_sos(const float* z, float* y, float* logabsdet, const void* hidden_frag, const float* hidden_unscale,
+                        const float* hidden_bias, const void* final_frag, const float* final_unscale, const float* final_bias,
+                        const int32_t* units_needed, uint32_t* err_flag, int64_t n, int32_t d, int32_t num_blocks,
+                        int32_t n_sigmoids, int32_t bisection_iterations, float bisection_lim, float offset,
+                        float log_scale_postact, int32_t lad_flags, void* stream);
 
 /* Backward of fc_sum_of_sigmoids in the forward direction, all d columns transformed, per-sample rows (what
  * torch.autograd yields for adaptive_sigmoids.py:108-142 + nonlinearities.py:519-552): grad_x [n, d] and grad_params
