@@ -596,6 +596,7 @@ hipError_t launch_made_inverse_bpw(const Args& a, const RQOp<0>& op, hipStream_t
 template <int NB, int K0S, int PT, int kKind, class Args>
 hipError_t launch_made_inverse(const Args& a, const RQOp<0>& op, hipStream_t s) {
   // two blocks per wave once every wave of the chip has a pair to carry (small batches: one block per wave fills more CUs)
+  // (the pair route is run by tests/test_gpu_ar_sampler_rows.py::test_rows_of_the_two_block_route_against_float64 at this size)
   if constexpr (mi_total_lds<Args>(NB, K0S, PT, 2) <= 160 * 1024 && mi_pairs_fit_registers<Args>(NB, K0S, PT, kKind)) {
     if (a.blocks16 >= 2 * 8 * (int64_t)device_cu_count()) return launch_made_inverse_bpw<NB, K0S, PT, kKind, 2>(a, op, s);
   }

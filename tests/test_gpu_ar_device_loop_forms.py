@@ -124,8 +124,10 @@ def test_device_loop_forms_match_the_reference_scheme(kind, k, features, hidden,
 
 
 def test_rows_do_not_depend_on_the_batch(device):
-    """S = 30: the first 77 rows of a 1000-row call equal a 77-row call bitwise (each wave works on its own 16 rows; the
-    one- and two-blocks-per-wave forms compute the same); N = 1 and N = 17 run; a call repeats itself bitwise."""
+    """S = 30: the first 77 rows of a 1000-row call equal a 77-row call bitwise (each wave works on its own 16 rows); N = 1
+    and N = 17 run; a call repeats itself bitwise.  Every call here is far below 256 rows per CU, so only the
+    one-block-per-wave form runs: the two-blocks-per-wave form against the same rows on the one-block form is
+    tests/test_gpu_ar_sampler_rows.py::test_rows_of_the_two_block_route_against_float64."""
     t = _build("sos", 30, 8, 64, 2, 72).to(device)
     x = _inputs("sos", 1000, 8).to(device)
     with torch.no_grad():
