@@ -43,8 +43,8 @@ from .mog import (  # noqa: F401
     mog_log_prob_backward)
 from .pointwise import (  # noqa: F401
     EW_CAUCHY_CDF, EW_EXP, EW_EXTENDED_SOFTPLUS, EW_GLU, EW_LEAKY_RELU, EW_LOGTANH, EW_SIGMOID, EW_SOFTPLUS, EW_TANH,
-    _PermuteFunction, _PointwiseAffineFunction, _item_vector, _permute_nograd, batchnorm_eval, elementwise, permute,
-    pointwise_affine, pointwise_affine_autograd)
+    _ElementwiseFunction, _PermuteFunction, _PointwiseAffineFunction, _item_vector, _permute_nograd, batchnorm_eval,
+    elementwise, elementwise_autograd, elementwise_expression, permute, pointwise_affine, pointwise_affine_autograd)
 from .rowwave import (  # noqa: F401
     HDH_MAX_REFLECTIONS, LINEAR_DENSE, LINEAR_DENSE_SHIFTED, LINEAR_LU_FORWARD, LINEAR_LU_INVERSE, MAX_ROW_FEATURES,
     PER_SAMPLE_DENSE, PER_SAMPLE_DENSE_T, PER_SAMPLE_LU_FORWARD, PER_SAMPLE_LU_INVERSE, SYLVESTER_MM_ROWS,

@@ -1,6 +1,9 @@
 """Permutation, batch-shared point-wise affine, eval-mode batch norm and the element-wise non-linearities."""
+import math
+
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from flowconductor_amd import _hip
 from ._core import _as_cols, _call, _err_word, _finish
@@ -190,3 +193,131 @@ def elementwise(inputs, kind, inverse=False, aux=None, p=(0.0, 0.0, 0.0, 0.0), r
           p[3], _hip.stream_ptr(x.device))
     _finish(may_raise)
     return y, (lad_el if elem_lad else lad_row)
+
+
+_LN2 = 0.6931471805599453
+_LOG_PI = 1.1447298858494002
+
+
+def _tanh_log_derivative(x):
+    """log(1 - tanh(x)^2) = 2 (ln 2 - |x| - softplus(-2|x|)): the kernel's form, no cancellation near saturation."""
+    ax = x.abs()
+    return 2.0 * (_LN2 - ax - F.softplus(-2.0 * ax))
+
+
+def _atanh_pair(x):
+    """atanh(x) and -log(1 - x^2) from log1p(x), log1p(-x)."""
+    up, down = torch.log1p(x), torch.log1p(-x)
+    return 0.5 * (up - down), -(up + down)
+
+
+def elementwise_expression(inputs, kind, inverse=False, aux=None, p=(0.0, 0.0, 0.0, 0.0)):
+    """Bijector ``kind`` as a differentiable torch expression in the dtype and on the device of ``inputs``: ``(outputs,
+    per-element log-derivative)``.  What ``_ElementwiseFunction.backward`` differentiates; the values are those of
+    ``fc_elementwise`` to rounding.  Branches are taken with ``where`` on inputs made harmless for the branch not taken,
+    so that no 0 * inf reaches a gradient."""
+    x = inputs
+    p = tuple(float(v) for v in p) + (0.0,) * (4 - len(p))
+    if kind == EW_EXP:
+        if not inverse:
+            return torch.exp(x), x
+        y = torch.log(x)
+        return y, -y
+    if kind == EW_TANH:
+        if not inverse:
+            return torch.tanh(x), _tanh_log_derivative(x)
+        return _atanh_pair(x)
+    if kind == EW_LOGTANH:
+        cut, alpha, beta, inv_cut = p
+        if not inverse:
+            mid = ~((x > cut) | (x < -cut))
+            xm, xa = torch.where(mid, x, torch.zeros_like(x)), torch.where(mid, torch.ones_like(x), x.abs())
+            y = torch.where(mid, torch.tanh(xm), torch.sign(x) * (alpha * torch.log(beta * xa)))
+            return y, torch.where(mid, _tanh_log_derivative(xm), torch.log(alpha / xa))
+        mid = ~((x > inv_cut) | (x < -inv_cut))
+        xm, xa = torch.where(mid, x, torch.zeros_like(x)), torch.where(mid, torch.zeros_like(x), x.abs())
+        y_mid, lad_mid = _atanh_pair(xm)
+        y = torch.where(mid, y_mid, torch.sign(x) * (torch.exp(xa / alpha) / beta))
+        return y, torch.where(mid, lad_mid, -math.log(alpha * beta) + xa / alpha)
+    if kind == EW_LEAKY_RELU:
+        log_slope = aux.to(x).reshape(())
+        y = torch.where(x > 0, x, x * (p[1] if inverse else p[0]))
+        lad = torch.where(x < 0, -log_slope if inverse else log_slope, torch.zeros_like(x))
+        return y, lad
+    if kind == EW_SIGMOID:
+        temp = aux.to(x).reshape(())
+        if not inverse:
+            t = temp * x
+            return torch.sigmoid(t), torch.log(temp) - F.softplus(-t) - F.softplus(t)
+        xc = torch.clamp(x, p[0], 1 - p[0])
+        y = (1 / temp) * (torch.log(xc) - torch.log1p(-xc))
+        return y, -(torch.log(temp) - F.softplus(-temp * y) - F.softplus(temp * y))
+    if kind == EW_SOFTPLUS:
+        thr, eps = p[0], p[1]
+        if not inverse:
+            return F.softplus(x, beta=1, threshold=thr) + eps, F.logsigmoid(x)
+        xi = x - eps
+        linear = xi > thr
+        y = torch.where(linear, xi, torch.log(torch.expm1(torch.where(linear, torch.ones_like(xi), xi))))
+        return y, -torch.log(-torch.expm1(-xi))
+    if kind == EW_CAUCHY_CDF:
+        if not inverse:
+            return (1 / math.pi) * torch.atan(x) + 0.5, -_LOG_PI - torch.log(1 + x ** 2)
+        y = torch.tan(math.pi * (x - 0.5))
+        return y, _LOG_PI + torch.log(1 + y ** 2)
+    if kind == EW_EXTENDED_SOFTPLUS:
+        shift = F.softplus(aux.to(x).reshape(x.shape[1:])) + 1e-1
+        y = F.softplus(x - shift) - F.softplus(-(x + shift))
+        return y, torch.logaddexp(x - torch.logaddexp(shift, x), -F.softplus(shift + x))
+    if kind == EW_GLU:
+        context = aux.to(x).reshape(x.shape)
+        gate = torch.sigmoid(context)
+        if not inverse:
+            return x * gate, F.logsigmoid(context)
+        return x / gate, -F.logsigmoid(context)
+    raise ValueError("unknown element-wise bijector kind %r" % (kind,))
+
+
+class _ElementwiseFunction(torch.autograd.Function):
+    """``elementwise`` with gradients: the HIP kernel forward; backward recomputes the bijector from the saved inputs and
+    ``aux`` as the float32 torch expression ``elementwise_expression`` on the device and lets ``torch.autograd.grad``
+    walk it with ``(grad_outputs, grad_logabsdet)`` -- no HIP backward kernel."""
+
+    @staticmethod
+    def forward(ctx, inputs, aux, kind, inverse, p, row_sum, elem_lad, may_raise):
+        with torch.no_grad():
+            outputs, logabsdet = elementwise(inputs, kind, inverse=inverse, aux=aux, p=p, row_sum=row_sum,
+                                             elem_lad=elem_lad, may_raise=may_raise)
+        ctx.save_for_backward(inputs, aux)
+        ctx.config = (kind, inverse, p, elem_lad)
+        return outputs, logabsdet
+
+    @staticmethod
+    def backward(ctx, grad_outputs, grad_logabsdet):
+        inputs, aux = ctx.saved_tensors
+        kind, inverse, p, elem_lad = ctx.config
+        with torch.enable_grad():
+            x = inputs.detach().requires_grad_(ctx.needs_input_grad[0])
+            a = None if aux is None else aux.detach().requires_grad_(ctx.needs_input_grad[1])
+            y, lad = elementwise_expression(x, kind, inverse=inverse, aux=a, p=p)
+            if not elem_lad and lad.dim() > 1:
+                lad = lad.sum(dim=list(range(1, lad.dim())))
+            wanted = [t for t, needed in ((x, ctx.needs_input_grad[0]), (a, ctx.needs_input_grad[1])) if needed]
+            # (LeakyReLU's outputs do not depend on its log-slope: only what hangs on a wanted tensor is walked)
+            walked = [(t, g) for t, g in ((y, grad_outputs), (lad, grad_logabsdet)) if t.requires_grad]
+            grads = list(torch.autograd.grad([t for t, _ in walked], wanted, [g for _, g in walked], allow_unused=True))
+        gx = grads.pop(0) if ctx.needs_input_grad[0] else None
+        ga = grads.pop(0) if ctx.needs_input_grad[1] else None
+        return gx, ga, None, None, None, None, None, None
+
+
+def elementwise_autograd(inputs, kind, inverse=False, aux=None, p=(0.0, 0.0, 0.0, 0.0), row_sum=True,
+                         elem_lad=False, may_raise=False):
+    """``elementwise``; records an autograd node when ``inputs`` or ``aux`` (temperature, log-slope, context, shift)
+    require gradients.  Without one it is ``elementwise`` itself: one launch, the same bits."""
+    if aux is not None:
+        aux = torch.as_tensor(aux)
+    if torch.is_grad_enabled() and (inputs.requires_grad or (aux is not None and aux.requires_grad)):
+        return _ElementwiseFunction.apply(inputs, aux, kind, inverse, tuple(p), row_sum, elem_lad, may_raise)
+    return elementwise(inputs, kind, inverse=inverse, aux=aux, p=p, row_sum=row_sum, elem_lad=elem_lad,
+                       may_raise=may_raise)

@@ -9,18 +9,18 @@ from flowconductor_amd.transforms.base import CompositeTransform, InverseTransfo
 
 class Exp(Transform):
     def forward(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_EXP)
+        return ops.elementwise_autograd(inputs, ops.EW_EXP)
 
     def inverse(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_EXP, inverse=True, may_raise=True)
+        return ops.elementwise_autograd(inputs, ops.EW_EXP, inverse=True, may_raise=True)
 
 
 class Tanh(Transform):
     def forward(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_TANH)
+        return ops.elementwise_autograd(inputs, ops.EW_TANH)
 
     def inverse(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_TANH, inverse=True, may_raise=True)
+        return ops.elementwise_autograd(inputs, ops.EW_TANH, inverse=True, may_raise=True)
 
 
 class LogTanh(Transform):
@@ -40,13 +40,15 @@ class LogTanh(Transform):
         return (self.cut_point, self.alpha, self.beta, self.inv_cut_point)
 
     def forward(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_LOGTANH, p=self._p())
+        return ops.elementwise_autograd(inputs, ops.EW_LOGTANH, p=self._p())
 
     def inverse(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_LOGTANH, inverse=True, p=self._p())
+        return ops.elementwise_autograd(inputs, ops.EW_LOGTANH, inverse=True, p=self._p())
 
 
 class LeakyReLU(Transform):
+    _HIP_AUTOGRAD = True        # ``log_negative_slope`` trains through ops.elementwise_autograd
+
     def __init__(self, negative_slope=1e-2):
         if negative_slope <= 0:
             raise ValueError("Slope must be positive.")
@@ -58,14 +60,17 @@ class LeakyReLU(Transform):
         return (self.negative_slope, 1 / self.negative_slope)
 
     def forward(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_LEAKY_RELU, aux=self.log_negative_slope.reshape(1), p=self._p())
+        return ops.elementwise_autograd(inputs, ops.EW_LEAKY_RELU, aux=self.log_negative_slope.reshape(1),
+                                        p=self._p())
 
     def inverse(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_LEAKY_RELU, inverse=True, aux=self.log_negative_slope.reshape(1),
-                               p=self._p())
+        return ops.elementwise_autograd(inputs, ops.EW_LEAKY_RELU, inverse=True,
+                                        aux=self.log_negative_slope.reshape(1), p=self._p())
 
 
 class Sigmoid(Transform):
+    _HIP_AUTOGRAD = True        # a learnable ``temperature`` trains through ops.elementwise_autograd
+
     def __init__(self, temperature=1, eps=1e-6, learn_temperature=False):
         super().__init__()
         self.eps = eps
@@ -75,11 +80,11 @@ class Sigmoid(Transform):
             self.register_buffer("temperature", torch.Tensor([temperature]))
 
     def forward(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_SIGMOID, aux=self.temperature, p=(self.eps,))
+        return ops.elementwise_autograd(inputs, ops.EW_SIGMOID, aux=self.temperature, p=(self.eps,))
 
     def inverse(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_SIGMOID, inverse=True, aux=self.temperature, p=(self.eps,),
-                               may_raise=True)
+        return ops.elementwise_autograd(inputs, ops.EW_SIGMOID, inverse=True, aux=self.temperature, p=(self.eps,),
+                                        may_raise=True)
 
 
 class Softplus(Transform):
@@ -92,10 +97,10 @@ class Softplus(Transform):
         self.log_sigmoid = torch.nn.LogSigmoid()
 
     def forward(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_SOFTPLUS, p=(self.softplus.threshold, self.eps))
+        return ops.elementwise_autograd(inputs, ops.EW_SOFTPLUS, p=(self.softplus.threshold, self.eps))
 
     def inverse(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_SOFTPLUS, inverse=True, p=(self.softplus.threshold, self.eps))
+        return ops.elementwise_autograd(inputs, ops.EW_SOFTPLUS, inverse=True, p=(self.softplus.threshold, self.eps))
 
 
 class Logit(InverseTransform):
@@ -110,13 +115,13 @@ class GatedLinearUnit(Transform):
         super().__init__()
 
     def forward(self, inputs, context=None):
-        y, lad = ops.elementwise(inputs, ops.EW_GLU, aux=context.expand_as(inputs).contiguous(), row_sum=False,
-                                 elem_lad=True)
+        y, lad = ops.elementwise_autograd(inputs, ops.EW_GLU, aux=context.expand_as(inputs).contiguous(),
+                                          row_sum=False, elem_lad=True)
         return y, lad.reshape(-1)
 
     def inverse(self, inputs, context=None):
-        y, lad = ops.elementwise(inputs, ops.EW_GLU, inverse=True, aux=context.expand_as(inputs).contiguous(),
-                                 row_sum=False, elem_lad=True)
+        y, lad = ops.elementwise_autograd(inputs, ops.EW_GLU, inverse=True,
+                                          aux=context.expand_as(inputs).contiguous(), row_sum=False, elem_lad=True)
         return y, lad.reshape(-1)
 
 
@@ -125,10 +130,10 @@ class CauchyCDF(Transform):
         super().__init__()
 
     def forward(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_CAUCHY_CDF)
+        return ops.elementwise_autograd(inputs, ops.EW_CAUCHY_CDF)
 
     def inverse(self, inputs, context=None):
-        return ops.elementwise(inputs, ops.EW_CAUCHY_CDF, inverse=True, may_raise=True)
+        return ops.elementwise_autograd(inputs, ops.EW_CAUCHY_CDF, inverse=True, may_raise=True)
 
 
 class CauchyCDFInverse(InverseTransform):
@@ -324,8 +329,7 @@ class ExtendedSoftplus(torch.nn.Module):
         return self._softplus(self.shift) + 1e-1
 
     def forward(self, inputs):
-        shift = self.shift.detach()
-        if shift.shape[0] != 1:
+        if self.shift.shape[0] != 1:
             raise NotImplementedError("per-sample ExtendedSoftplus runs inside the SumOfSigmoids kernel")
-        return ops.elementwise(inputs, ops.EW_EXTENDED_SOFTPLUS, aux=shift.reshape(-1), row_sum=False,
-                               elem_lad=True)
+        return ops.elementwise_autograd(inputs, ops.EW_EXTENDED_SOFTPLUS, aux=self.shift.reshape(-1), row_sum=False,
+                                        elem_lad=True)

@@ -47,7 +47,8 @@ NAMES = [
     "deep_sigmoid", "deep_sigmoid_autograd", "deep_sigmoid_bound", "deep_sigmoid_fits", "deferred_errors", "dense_mm",
     "device_pack_affine_coupling", "device_pack_final_layer", "device_pack_made_affine",
     "device_pack_resnet_hidden_backward", "device_pack_resnet_hidden_forward", "device_plan", "drop_param_list",
-    "elementwise", "fill_triangular", "fused_backward_supported", "fused_general_supported", "fused_linear_supported",
+    "elementwise", "elementwise_autograd", "fill_triangular", "fused_backward_supported", "fused_general_supported",
+    "fused_linear_supported",
     "general_hidden_width", "has_hooks", "hdh_linear", "hdh_linear_autograd", "householder", "householder_autograd",
     "householder_matrix", "invalidate_hip_caches", "iresnet_forward", "iresnet_image_floats", "iresnet_inverse",
     "iresnet_supported", "linear", "linear_per_sample", "lu_linear_autograd", "made_inverse",
@@ -67,7 +68,7 @@ MODULES = [m.name for m in pkgutil.iter_modules(ops.__path__)]
 
 
 def test_every_name_resolves():
-    assert len(NAMES) == 256 and sum(n.startswith("_") for n in NAMES) == 68
+    assert len(NAMES) == 257 and sum(n.startswith("_") for n in NAMES) == 68
     assert [n for n in NAMES if not hasattr(ops, n)] == []
 
 
