@@ -604,153 +604,100 @@ hipError_t launch_made_inverse(const Args& a, const RQOp<0>& op, hipStream_t s) 
   return hipErrorInvalidValue;       // (context form only: the image does not fit next to its context layers)
 }
 
-template <int NB, int K0S, class Args>
-hipError_t dispatch_made_inverse_pt(const Args& a, const RQOp<0>& op, int kind, hipStream_t s) {
-  const int pt = (a.P + 15) / 16;
-  if (kind == 0) return launch_made_inverse<NB, K0S, 1, 0>(a, op, s);
-  if (op.q.K == 8) return launch_made_inverse<NB, K0S, 2, 8>(a, op, s);        // 23 / 25 parameters per dim
-  if (op.q.K == 10) return launch_made_inverse<NB, K0S, 2, 10>(a, op, s);      // 29 / 31 (the reference's default bin count)
-  switch (pt) {
-    case 1: return launch_made_inverse<NB, K0S, 1, 1>(a, op, s);
-    case 2: return launch_made_inverse<NB, K0S, 2, 1>(a, op, s);
-    case 3: return launch_made_inverse<NB, K0S, 3, 1>(a, op, s);
-    default: return hipErrorInvalidValue;
-  }
-}
+// ---- the host path of the six entries: form-specific checks, made_args_prepare, (made_context_prepare,) dispatch ---------
+// All refusals are hipErrorInvalidValue.  Sizes are checked whatever n is; pointers, and what a configuration says, only when
+// there are rows: n == 0 with valid sizes is a success before any of them is looked at.
 
-// the argument checks and the spline configuration both entries share; hipSuccess with *run = false: nothing to do (n == 0)
-inline hipError_t made_inverse_prepare(const void* z, const void* y, const void* logabsdet, const void* hidden_frag,
-                                       const void* hidden_unscale, const void* hidden_bias, const void* final_frag,
-                                       const void* final_unscale, const void* final_bias, int64_t n, int32_t d, int32_t num_blocks,
-                                       int32_t params_per_dim, int32_t kind, const fc_rq_config* cfg, RQOp<0>& op, bool* run) {
-  *run = false;
-  if (n < 0 || d < 1 || d > 64 || num_blocks < 0 || num_blocks > 3 || kind < 0 || kind > 1) return hipErrorInvalidValue;
-  if (params_per_dim < 1 || params_per_dim > 48 || (kind == 0 && params_per_dim != 2) || (kind == 1 && !cfg)) return hipErrorInvalidValue;
-  if (n % 16 != 0) return hipErrorInvalidValue;
-  if (n == 0) return hipSuccess;
-  if (!z || !y || !logabsdet || !hidden_frag || !hidden_unscale || !hidden_bias || !final_frag || !final_unscale || !final_bias)
-    return hipErrorInvalidValue;
-  if ((((uintptr_t)hidden_frag | (uintptr_t)final_frag | (uintptr_t)final_bias) & 15u) != 0) return hipErrorInvalidValue;
-  if (kind == 1) {
-    RQParams& q = op.q;
-    q = rq_params_from_config(*cfg, 1);
-    if (q.K < 1 || q.K > 16 || params_per_dim != (q.tails ? 3 * q.K - 1 : 3 * q.K + 1)) return hipErrorInvalidValue;
-    op.inv_div = 1.f / q.wh_div;
-    op.inv_beta = 1.f / q.beta;
-  }
-  *run = true;
-  return hipSuccess;
-}
-
-template <class Args>
-hipError_t dispatch_made_inverse(const Args& a, const RQOp<0>& op, int num_blocks, int kind, hipStream_t s) {
-  const bool wide = a.D > 32;
-#define FC_MI(NBV)                                                                                    \
-  case NBV:                                                                                           \
-    return wide ? dispatch_made_inverse_pt<NBV, 2>(a, op, kind, s) : dispatch_made_inverse_pt<NBV, 1>(a, op, kind, s);
-  switch (num_blocks) {
-    FC_MI(0) FC_MI(1) FC_MI(2) FC_MI(3)
-    default: return hipErrorInvalidValue;
-  }
-#undef FC_MI
-}
-
-// ---- the mixture-of-Gaussians sampler (fc_made_mog_sample.hip, fc_made_mog_sample_context.hip) ----------------------------
-// argument checks both entries share; hipSuccess with *run = false: nothing to do (n == 0)
-inline hipError_t made_mog_prepare(const void* normal, const void* uniform, const void* x, const void* logp, const void* hidden_frag,
-                                   const void* hidden_unscale, const void* hidden_bias, const void* final_frag,
-                                   const void* final_unscale, const void* final_bias, int64_t n, int32_t d, int32_t num_blocks,
-                                   int32_t c, bool* run) {
-  *run = false;
-  if (n < 0 || d < 1 || d > 64 || num_blocks < 0 || num_blocks > 3 || c < 1 || c > kMogMaxComponents) return hipErrorInvalidValue;
-  if (n % 16 != 0) return hipErrorInvalidValue;
-  if (n == 0) return hipSuccess;
-  if (!normal || !uniform || !x || !logp || !hidden_frag || !hidden_unscale || !hidden_bias || !final_frag || !final_unscale || !final_bias)
-    return hipErrorInvalidValue;
-  if ((((uintptr_t)hidden_frag | (uintptr_t)final_frag | (uintptr_t)final_bias) & 15u) != 0) return hipErrorInvalidValue;
-  *run = true;
-  return hipSuccess;
-}
-
-template <int NB, int K0S, class Args>
-hipError_t dispatch_made_mog_pt(const Args& a, hipStream_t s) {
-  const RQOp<0> op{};
-  switch ((a.P + 15) / 16) {      // 3 c parameters per dim: c <= 5, <= 10, <= 16
-    case 1: return launch_made_inverse<NB, K0S, 1, kMiMog>(a, op, s);
-    case 2: return launch_made_inverse<NB, K0S, 2, kMiMog>(a, op, s);
-    case 3: return launch_made_inverse<NB, K0S, 3, kMiMog>(a, op, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-template <class Args>
-hipError_t dispatch_made_mog(const Args& a, int num_blocks, hipStream_t s) {
-  const bool wide = a.D > 32;
-#define FC_MM(NBV) \
-  case NBV:        \
-    return wide ? dispatch_made_mog_pt<NBV, 2>(a, s) : dispatch_made_mog_pt<NBV, 1>(a, s);
-  switch (num_blocks) {
-    FC_MM(0) FC_MM(1) FC_MM(2) FC_MM(3)
-    default: return hipErrorInvalidValue;
-  }
-#undef FC_MM
-}
-
-// ---- sum-of-sigmoids and sibling-spline forms (fc_made_inverse_sos*.hip, fc_made_inverse_spline*.hip) ---------------------
-// argument checks both entries share (made_inverse_prepare's, with the form's own parameter limit); hipSuccess with
-// *run = false: nothing to do (n == 0)
-inline hipError_t made_form_prepare(const void* z, const void* y, const void* logabsdet, const void* hidden_frag,
-                                    const void* hidden_unscale, const void* hidden_bias, const void* final_frag,
-                                    const void* final_unscale, const void* final_bias, int64_t n, int32_t d, int32_t num_blocks,
-                                    int32_t params_per_dim, int32_t max_params, bool* run) {
+// the checks all six entries share, at most `max_params` parameters per dim (the form's own limit), and the MadeInvArgs base
+// of their arguments; hipSuccess with *run = false: nothing to do (n == 0)
+inline hipError_t made_args_prepare(MadeInvArgs& a, const float* z, float* y, float* logabsdet, const void* hidden_frag,
+                                    const float* hidden_unscale, const float* hidden_bias, const void* final_frag,
+                                    const float* final_unscale, const float* final_bias, const int32_t* units_needed,
+                                    uint32_t* err_flag, int64_t n, int32_t d, int32_t num_blocks, int32_t params_per_dim,
+                                    int32_t max_params, bool accumulate, bool* run) {
   *run = false;
   if (n < 0 || d < 1 || d > 64 || num_blocks < 0 || num_blocks > 3) return hipErrorInvalidValue;
-  if (params_per_dim < 1 || params_per_dim > max_params) return hipErrorInvalidValue;
-  if (n % 16 != 0) return hipErrorInvalidValue;
+  if (params_per_dim < 1 || params_per_dim > max_params || n % 16 != 0) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!z || !y || !logabsdet || !hidden_frag || !hidden_unscale || !hidden_bias || !final_frag || !final_unscale || !final_bias)
     return hipErrorInvalidValue;
   if ((((uintptr_t)hidden_frag | (uintptr_t)final_frag | (uintptr_t)final_bias) & 15u) != 0) return hipErrorInvalidValue;
+  a = MadeInvArgs{z, y, logabsdet, static_cast<const f16x8*>(hidden_frag), hidden_unscale, hidden_bias,
+                  static_cast<const f16x8*>(final_frag), final_unscale, final_bias, err_flag, units_needed, n / 16, d,
+                  params_per_dim, accumulate ? 1 : 0};
   *run = true;
   return hipSuccess;
 }
 
-template <class Op>
-MadeFormArgs<Op> made_form_args(const float* z, float* y, float* logabsdet, const void* hidden_frag, const float* hidden_unscale,
-                                const float* hidden_bias, const void* final_frag, const float* final_unscale,
-                                const float* final_bias, const int32_t* units_needed, uint32_t* err_flag, int64_t n, int32_t d,
-                                int32_t params_per_dim, int32_t lad_flags, const Op& form) {
-  return MadeFormArgs<Op>{{z, y, logabsdet, static_cast<const f16x8*>(hidden_frag), hidden_unscale, hidden_bias,
-                           static_cast<const f16x8*>(final_frag), final_unscale, final_bias, err_flag, units_needed, n / 16, d,
-                           params_per_dim, (lad_flags & FC_RQ_ACCUMULATE_LOGABSDET) ? 1 : 0},
-                          form};
+// the conditional entries' own arguments, into `a` once made_args_prepare has passed: the size whatever n is, the pointers
+// when there are rows (`run`)
+inline bool made_context_prepare(MadeInvCtxArgs& a, const float* context, const void* context_frag, const float* context_unscale,
+                                 const float* context_bias, int32_t context_features, bool run) {
+  if (context_features < 1 || context_features > 32) return false;
+  if (run && (!context || !context_frag || !context_unscale || !context_bias || ((uintptr_t)context_frag & 15u) != 0)) return false;
+  a.context = context;
+  a.cimage = static_cast<const f16x8*>(context_frag);
+  a.cimage_un = context_unscale;
+  a.cimage_bias = context_bias;
+  a.C = context_features;
+  return true;
 }
 
-// parameter tiles FIRST .. LAST of one form (one translation unit per form and tile range: compile time)
-template <int NB, int K0S, int FIRST, int LAST, class Args>
-hipError_t dispatch_made_form_pt(const Args& a, hipStream_t s) {
-  const RQOp<0> op{};
-  const int pt = (a.P + 15) / 16;
-  if constexpr (FIRST <= 1 && 1 <= LAST) if (pt == 1) return launch_made_inverse<NB, K0S, 1, kMiForm>(a, op, s);
-  if constexpr (FIRST <= 2 && 2 <= LAST) if (pt == 2) return launch_made_inverse<NB, K0S, 2, kMiForm>(a, op, s);
-  if constexpr (FIRST <= 3 && 3 <= LAST) if (pt == 3) return launch_made_inverse<NB, K0S, 3, kMiForm>(a, op, s);
-  if constexpr (FIRST <= 4 && 4 <= LAST) if (pt == 4) return launch_made_inverse<NB, K0S, 4, kMiForm>(a, op, s);
-  if constexpr (FIRST <= 5 && 5 <= LAST) if (pt == 5) return launch_made_inverse<NB, K0S, 5, kMiForm>(a, op, s);
-  if constexpr (FIRST <= 6 && 6 <= LAST) if (pt == 6) return launch_made_inverse<NB, K0S, 6, kMiForm>(a, op, s);
+// what only fc_made_inverse(_context) check: kind (0 affine, P = 2; 1 rational-quadratic, with its configuration), and the
+// spline of that configuration: K <= 16 bins, 3K -/+ 1 parameters per dim
+inline bool made_rq_prepare(int32_t kind, int32_t params_per_dim, const fc_rq_config* cfg, int64_t n, RQOp<0>& op) {
+  if (kind < 0 || kind > 1 || (kind == 0 && params_per_dim != 2) || (kind == 1 && !cfg)) return false;
+  if (kind == 0 || n == 0) return true;
+  RQParams& q = op.q;
+  q = rq_params_from_config(*cfg, 1);
+  if (q.K < 1 || q.K > 16 || params_per_dim != (q.tails ? 3 * q.K - 1 : 3 * q.K + 1)) return false;
+  op.inv_div = 1.f / q.wh_div;
+  op.inv_beta = 1.f / q.beta;
+  return true;
+}
+
+// num_blocks x k-steps of the initial layer (two for D > 32): `form(NB, K0S)`, both integral constants, picks the parameter
+// tile count and kKind of its form and launches
+template <int V>
+using MiInt = std::integral_constant<int, V>;
+template <class Form>
+hipError_t dispatch_made_blocks(int num_blocks, int d, Form&& form) {
+  switch (num_blocks) {
+    case 0: return d > 32 ? form(MiInt<0>{}, MiInt<2>{}) : form(MiInt<0>{}, MiInt<1>{});
+    case 1: return d > 32 ? form(MiInt<1>{}, MiInt<2>{}) : form(MiInt<1>{}, MiInt<1>{});
+    case 2: return d > 32 ? form(MiInt<2>{}, MiInt<2>{}) : form(MiInt<2>{}, MiInt<1>{});
+    case 3: return d > 32 ? form(MiInt<3>{}, MiInt<2>{}) : form(MiInt<3>{}, MiInt<1>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// the instantiation of kKind with PT .. LAST parameter tiles that holds a.P parameters per dim
+template <int NB, int K0S, int PT, int LAST, int kKind, class Args>
+hipError_t launch_made_tiles(const Args& a, const RQOp<0>& op, hipStream_t s) {
+  if ((a.P + 15) / 16 == PT) return launch_made_inverse<NB, K0S, PT, kKind>(a, op, s);
+  if constexpr (PT < LAST) return launch_made_tiles<NB, K0S, PT + 1, LAST, kKind>(a, op, s);
   return hipErrorInvalidValue;
 }
 
-template <int FIRST, int LAST, class Args>
-hipError_t dispatch_made_form(const Args& a, int num_blocks, hipStream_t s) {
-  const bool wide = a.D > 32;
-#define FC_MF(NBV) \
-  case NBV:        \
-    return wide ? dispatch_made_form_pt<NBV, 2, FIRST, LAST>(a, s) : dispatch_made_form_pt<NBV, 1, FIRST, LAST>(a, s);
-  switch (num_blocks) {
-    FC_MF(0) FC_MF(1) FC_MF(2) FC_MF(3)
-    default: return hipErrorInvalidValue;
-  }
-#undef FC_MF
+// affine / rational-quadratic form (fc_made_inverse.hip, fc_made_inverse_context.hip)
+template <class Args>
+hipError_t dispatch_made_inverse(const Args& a, const RQOp<0>& op, int num_blocks, int kind, hipStream_t s) {
+  return dispatch_made_blocks(num_blocks, a.D, [&](auto nb, auto k0s) {
+    constexpr int NB = decltype(nb)::value, K0S = decltype(k0s)::value;
+    if (kind == 0) return launch_made_inverse<NB, K0S, 1, 0>(a, op, s);
+    if (op.q.K == 8) return launch_made_inverse<NB, K0S, 2, 8>(a, op, s);        // 23 / 25 parameters per dim
+    if (op.q.K == 10) return launch_made_inverse<NB, K0S, 2, 10>(a, op, s);      // 29 / 31 (the reference's default bin count)
+    return launch_made_tiles<NB, K0S, 1, 3, 1>(a, op, s);
+  });
+}
+
+// one kKind at FIRST .. LAST parameter tiles: the mixture sampler (kMiMog, 3 c parameters per dim: c <= 5, <= 10, <= 16) and
+// the sum-of-sigmoids and sibling-spline forms (kMiForm; one translation unit per form and tile range: compile time)
+template <int FIRST, int LAST, int kKind, class Args>
+hipError_t dispatch_made_tiles(const Args& a, int num_blocks, hipStream_t s) {
+  return dispatch_made_blocks(num_blocks, a.D, [&](auto nb, auto k0s) {
+    return launch_made_tiles<decltype(nb)::value, decltype(k0s)::value, FIRST, LAST, kKind>(a, RQOp<0>{}, s);
+  });
 }
 
 // defined in the translation units that hold the instantiations

@@ -4,16 +4,15 @@
 extern "C" int fc_made_inverse(const float* z, float* y, float* logabsdet, const void* hidden_frag,
                                const float* hidden_unscale, const float* hidden_bias, const void* final_frag,
                                const float* final_unscale, const float* final_bias, const int32_t* units_needed,
-                               uint32_t* err_flag, int64_t n,
-                               int32_t d, int32_t num_blocks, int32_t params_per_dim, int32_t kind,
+                               uint32_t* err_flag, int64_t n, int32_t d, int32_t num_blocks, int32_t params_per_dim, int32_t kind,
                                const fc_rq_config* cfg, void* stream) {
   fc::RQOp<0> op{};
+  if (!fc::made_rq_prepare(kind, params_per_dim, cfg, n, op)) return hipErrorInvalidValue;
+  fc::MadeInvArgs a{};
   bool run;
-  const hipError_t e = fc::made_inverse_prepare(z, y, logabsdet, hidden_frag, hidden_unscale, hidden_bias, final_frag, final_unscale,
-                                                final_bias, n, d, num_blocks, params_per_dim, kind, cfg, op, &run);
+  const hipError_t e = fc::made_args_prepare(a, z, y, logabsdet, hidden_frag, hidden_unscale, hidden_bias, final_frag, final_unscale,
+                                             final_bias, units_needed, err_flag, n, d, num_blocks, params_per_dim, 48,
+                                             n != 0 && cfg && (cfg->flags & FC_RQ_ACCUMULATE_LOGABSDET), &run);
   if (e != hipSuccess || !run) return e;
-  fc::MadeInvArgs a{z, y, logabsdet, static_cast<const fc::f16x8*>(hidden_frag), hidden_unscale, hidden_bias,
-                    static_cast<const fc::f16x8*>(final_frag), final_unscale, final_bias, err_flag, units_needed, n / 16, d, params_per_dim,
-                    (cfg && (cfg->flags & FC_RQ_ACCUMULATE_LOGABSDET)) ? 1 : 0};
   return fc::dispatch_made_inverse(a, op, num_blocks, kind, static_cast<hipStream_t>(stream));
 }

@@ -8,12 +8,13 @@ extern "C" int fc_made_inverse_sos(const float* z, float* y, float* logabsdet, c
                                    int32_t num_blocks, int32_t n_sigmoids, int32_t bisection_iterations, float bisection_lim,
                                    float offset, float log_scale_postact, int32_t lad_flags, void* stream) {
   if (n_sigmoids < 1 || n_sigmoids > 31) return hipErrorInvalidValue;
-  const int32_t per_dim = 3 * n_sigmoids + 1;
+  fc::MadeFormArgs<fc::SoSOp> a{};
   bool run;
-  const hipError_t e = fc::made_form_prepare(z, y, logabsdet, hidden_frag, hidden_unscale, hidden_bias, final_frag, final_unscale,
-                                             final_bias, n, d, num_blocks, per_dim, 96, &run);
+  const hipError_t e = fc::made_args_prepare(a, z, y, logabsdet, hidden_frag, hidden_unscale, hidden_bias, final_frag, final_unscale,
+                                             final_bias, units_needed, err_flag, n, d, num_blocks, 3 * n_sigmoids + 1, 96,
+                                             lad_flags & FC_RQ_ACCUMULATE_LOGABSDET, &run);
   if (e != hipSuccess || !run) return e;
-  fc::SoSOp op;      // as fc_sum_of_sigmoids fills it
+  fc::SoSOp& op = a.form;      // as fc_sum_of_sigmoids fills it
   op.S = n_sigmoids;
   op.inverse = 1;
   op.iterations = bisection_iterations < 0 ? -bisection_iterations : bisection_iterations;
@@ -22,9 +23,7 @@ extern "C" int fc_made_inverse_sos(const float* z, float* y, float* logabsdet, c
   op.ratio_mult = 1.5f;
   op.offset = offset;
   op.log_post = log_scale_postact;
-  const auto a = fc::made_form_args(z, y, logabsdet, hidden_frag, hidden_unscale, hidden_bias, final_frag, final_unscale, final_bias,
-                                    units_needed, err_flag, n, d, per_dim, lad_flags, op);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (per_dim > 48) return fc::dispatch_made_sos_wide(a, num_blocks, s);
-  return fc::dispatch_made_form<1, 3>(a, num_blocks, s);
+  if (a.P > 48) return fc::dispatch_made_sos_wide(a, num_blocks, s);
+  return fc::dispatch_made_tiles<1, 3, fc::kMiForm>(a, num_blocks, s);
 }

@@ -4,6 +4,6 @@
 
 namespace fc {
 hipError_t dispatch_made_sos_wide(const MadeFormArgs<SoSOp>& a, int num_blocks, hipStream_t s) {
-  return dispatch_made_form<4, 6>(a, num_blocks, s);
+  return dispatch_made_tiles<4, 6, kMiForm>(a, num_blocks, s);
 }
 }  // namespace fc

@@ -10,27 +10,21 @@ extern "C" int fc_made_inverse_spline(const float* z, float* y, float* logabsdet
                                       int32_t lad_flags, void* stream) {
   if (!cfg || cfg->num_bins < 1 || cfg->num_bins > 48) return hipErrorInvalidValue;
   const int32_t k = cfg->num_bins;
-  int32_t per_dim;
-  switch (cfg->kind) {
-    case FC_SPLINE_LINEAR: per_dim = k; break;
-    case FC_SPLINE_QUADRATIC: per_dim = cfg->tails ? 2 * k - 1 : 2 * k + 1; break;
-    case FC_SPLINE_CUBIC: per_dim = 2 * k + 2; break;
-    default: return hipErrorInvalidValue;
-  }
-  bool run;
-  const hipError_t e = fc::made_form_prepare(z, y, logabsdet, hidden_frag, hidden_unscale, hidden_bias, final_frag, final_unscale,
-                                             final_bias, n, d, num_blocks, per_dim, 48, &run);
-  if (e != hipSuccess || !run) return e;
   fc::SplineParams q = fc::spline_params_from_config(*cfg);
   q.inverse = 1;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-#define FC_FORM_ARGS(OP) \
-  fc::made_form_args(z, y, logabsdet, hidden_frag, hidden_unscale, hidden_bias, final_frag, final_unscale, final_bias, units_needed, \
-                     err_flag, n, d, per_dim, lad_flags, OP)
+  // the form's parameters per dim and its unit's dispatcher, behind the shared checks
+  auto run = [&](int32_t per_dim, auto op, auto dispatch) -> int {
+    fc::MadeFormArgs<decltype(op)> a{{}, op};
+    bool rows;
+    const hipError_t e = fc::made_args_prepare(a, z, y, logabsdet, hidden_frag, hidden_unscale, hidden_bias, final_frag, final_unscale,
+                                               final_bias, units_needed, err_flag, n, d, num_blocks, per_dim, 48,
+                                               lad_flags & FC_RQ_ACCUMULATE_LOGABSDET, &rows);
+    return (e != hipSuccess || !rows) ? e : dispatch(a, num_blocks, static_cast<hipStream_t>(stream));
+  };
   switch (cfg->kind) {
-    case FC_SPLINE_LINEAR: return fc::dispatch_made_spline_linear(FC_FORM_ARGS(fc::LinearSplineOp{q}), num_blocks, s);
-    case FC_SPLINE_QUADRATIC: return fc::dispatch_made_spline_quadratic(FC_FORM_ARGS(fc::QuadraticSplineOp{q}), num_blocks, s);
-    default: return fc::dispatch_made_spline_cubic(FC_FORM_ARGS(fc::CubicSplineOp{q}), num_blocks, s);
+    case FC_SPLINE_LINEAR: return run(k, fc::LinearSplineOp{q}, fc::dispatch_made_spline_linear);
+    case FC_SPLINE_QUADRATIC: return run(cfg->tails ? 2 * k - 1 : 2 * k + 1, fc::QuadraticSplineOp{q}, fc::dispatch_made_spline_quadratic);
+    case FC_SPLINE_CUBIC: return run(2 * k + 2, fc::CubicSplineOp{q}, fc::dispatch_made_spline_cubic);
+    default: return hipErrorInvalidValue;
   }
-#undef FC_FORM_ARGS
 }

@@ -3,6 +3,6 @@
 
 namespace fc {
 hipError_t dispatch_made_spline_cubic(const MadeFormArgs<CubicSplineOp>& a, int num_blocks, hipStream_t s) {
-  return dispatch_made_form<1, 3>(a, num_blocks, s);
+  return dispatch_made_tiles<1, 3, kMiForm>(a, num_blocks, s);
 }
 }  // namespace fc

@@ -16,7 +16,7 @@ import torch
 from torch.nn import functional as F
 
 from flowconductor_amd import ops, options
-from flowconductor_amd.transforms.made import MADE, pad_rows
+from flowconductor_amd.transforms.made import MADE, device_loop_rows_ok, pad_rows
 
 
 class MixtureOfGaussiansMADE(MADE):
@@ -139,27 +139,15 @@ class MixtureOfGaussiansMADE(MADE):
         return (draws, log_prob) if with_log_prob else draws
 
     def _sample_kernel_ok(self, normal, context):
-        """``fc_made_mog_sample(_context)`` has the shape: a residual-block MADE with hidden <= 64, <= 3 ReLU blocks, no
-        batch norm / active dropout / hooks, 1 < D <= 64, <= 16 components, float32 device noise; a [rows, C <= 32]
-        float32 device context whose image fits the kernel's LDS next to the hidden stack."""
-        if not (normal.dim() == 2 and normal.is_cuda and normal.dtype == torch.float32 and 1 < normal.shape[1] <= 64
-                and normal.shape[0] >= 1 and options.get("ar_device_loop") and options.get("fused_hidden")):
-            return False
-        has_ctx = hasattr(self, "context_layer")
-        if has_ctx != (context is not None):
-            return False
-        if has_ctx and not (context.dim() == 2 and context.is_cuda and context.dtype == torch.float32
-                            and context.shape[0] == normal.shape[0] and 1 <= context.shape[1] <= 32):
+        """``fc_made_mog_sample(_context)`` has the shape: float32 device noise and context as the device loops take them
+        (``device_loop_rows_ok``), a context exactly when the net has context layers, <= 16 components, a MADE the loops
+        hold (``MADE.device_loop_supported``), no hooks.  Sampling runs under ``no_grad``: gradients are not asked about."""
+        if hasattr(self, "context_layer") != (context is not None) or not device_loop_rows_ok(normal, context):
             return False
 
         def structure_ok():
-            code = ops.activation_code(self.activation)
-            return (normal.shape[1] == self.features and len(self.blocks) <= 3 and MADE.hip_hidden_supported(self, context)
-                    and code is not None and code[0] == ops.ACT_RELU
-                    and 1 <= self.num_mixture_components <= ops.MOG_MAX_COMPONENTS
-                    and self.final_layer.out_features == 3 * self.num_mixture_components * self.features
-                    and (not has_ctx or ops.made_inverse_context_fits(self.features, len(self.blocks),
-                                                                      3 * self.num_mixture_components)))
+            return (1 <= self.num_mixture_components <= ops.MOG_MAX_COMPONENTS
+                    and self.device_loop_supported(normal.shape[1], 3 * self.num_mixture_components, 48, context))
 
         key = (normal.shape[1], None if context is None else context.shape[1]) + ops.structure_key(self)
         return ops.static_memo(self, "mog_sample_ok", key, structure_ok) and not ops.has_hooks(self)

@@ -71,100 +71,80 @@ def made_inverse_row_limit(kind, per_dim):
     return MADE_SOS_ROW_SIGMOIDS // max(1, (per_dim - 1) // 3)
 
 
-def made_inverse_form_fits(features, num_blocks, per_dim):
-    """LDS budget of ``fc_made_inverse_sos`` / ``fc_made_inverse_spline`` (fc_made_inverse.h ``mi_lds_bytes``, one 16-row
-    block per wave): the hidden stack's image and the waves' parameter strips in 160 KB.  Only D > 32 with three blocks and
-    six parameter tiles does not fit."""
+def _made_lds_bytes(features, num_blocks, per_dim, with_context):
+    """LDS of the device loop at one 16-row block per wave: fc_made_inverse.h ``mi_lds_bytes`` (the hidden stack's image and
+    the waves' parameter strips) and, with a context, ``mi_ctx_lds_bytes`` (the context layers' images behind them)."""
     k0s = 1 if features <= 32 else 2
     pt = -(-per_dim // 16)
     image = (k0s * 8 + 2 * num_blocks * 16) * 1024 + (1 + 2 * num_blocks) * 256 + 64 + 8 * 16 * (16 * pt + 4) * 4
-    return 0 <= num_blocks <= 3 and features <= 64 and 1 <= per_dim <= 96 and image <= 160 * 1024
+    return image + ((1 + num_blocks) * (8 * 1024 + 256) + 64 if with_context else 0)
+
+
+def made_inverse_form_fits(features, num_blocks, per_dim):
+    """``fc_made_inverse_sos`` / ``fc_made_inverse_spline`` in 160 KB: all but D > 32, three blocks, six parameter tiles."""
+    return (0 <= num_blocks <= 3 and features <= 64 and 1 <= per_dim <= 96
+            and _made_lds_bytes(features, num_blocks, per_dim, False) <= 160 * 1024)
 
 
 def made_inverse_context_fits(features, num_blocks, per_dim):
-    """LDS budget of ``fc_made_inverse_context`` (fc_made_inverse.h ``mi_lds_bytes`` + ``mi_ctx_lds_bytes``, one 16-row
-    block per wave): the hidden stack's image, the context layers' images and the waves' parameter strips in 160 KB."""
-    k0s = 1 if features <= 32 else 2
-    pt = -(-per_dim // 16)
-    image = (k0s * 8 + 2 * num_blocks * 16) * 1024 + (1 + 2 * num_blocks) * 256 + 64 + 8 * 16 * (16 * pt + 4) * 4
-    context = (1 + num_blocks) * (8 * 1024 + 256) + 64
-    return num_blocks <= 3 and features <= 64 and per_dim <= 48 and image + context <= 160 * 1024
+    """``fc_made_inverse_context`` / ``fc_made_mog_sample_context`` in 160 KB."""
+    return (num_blocks <= 3 and features <= 64 and per_dim <= 48
+            and _made_lds_bytes(features, num_blocks, per_dim, True) <= 160 * 1024)
 
 
-def made_inverse(inputs, packed, num_blocks, per_dim, kind, rq=None, logabsdet_accum=None, context=None,
-                 context_pack=None):
-    """The D passes of an autoregressive inverse in ONE kernel (``fc_made_inverse``): ``inputs`` [N, D <= 64] (rows a
-    multiple of 16), ``packed`` from ``pack_made_inverse``; ``kind`` ``MADE_AFFINE`` or ``MADE_RQ`` (``rq``: keyword
-    arguments of the spline as for ``rq_spline``).  With ``context`` [N, C <= 32] and ``context_pack`` from
-    ``pack_made_inverse_context`` the conditional form (``fc_made_inverse_context``).  ``MADE_SOS`` (``rq``: ``n_sigmoids``,
-    ``offset``, ``iterations``, ``lim``, ``log_scale_postact`` as for ``sum_of_sigmoids``) and ``MADE_SPLINE`` (``rq``: the
-    keyword arguments of ``piecewise_spline``) run ``fc_made_inverse_sos`` / ``fc_made_inverse_spline``, which take no
-    context.  Returns ``(outputs, logabsdet)``."""
-    lib = _hip.load()
-    z = _prep_2d(inputs)
-    _hip.require_no_grad(inputs)
-    n, d = z.shape
-    if n % HIDDEN_ROWS != 0 or d > 64:
-        raise ValueError("fc_made_inverse: rows must be a multiple of %d, D <= 64" % HIDDEN_ROWS)
-    if (context is None) != (context_pack is None):
-        raise ValueError("made_inverse: context and context_pack go together")
-    if context is not None:
-        _hip.require_no_grad(context)
-        if (not torch.is_tensor(context) or context.dtype != torch.float32 or context.dim() != 2 or context.shape[0] != n
-                or not 1 <= context.shape[1] <= 32 or not context.is_contiguous() or context.device != z.device):
-            raise ValueError("made_inverse: context must be a contiguous float32 [N, C <= 32] tensor on the inputs' device")
-        if not made_inverse_context_fits(d, num_blocks, per_dim):
-            raise ValueError("fc_made_inverse_context has no instantiation for D = %d, %d blocks, %d parameters per dim"
-                             % (d, num_blocks, per_dim))
-        cf, cu, cb = context_pack
-        if cf.numel() != (1 + num_blocks) * 4096 or cu.numel() != 1 + num_blocks or cb.numel() != (1 + num_blocks) * 64:
-            raise ValueError("made_inverse: context_pack does not match num_blocks = %d" % num_blocks)
-    if kind in (MADE_SOS, MADE_SPLINE):
-        if context is not None:
-            raise ValueError("made_inverse: the sum-of-sigmoids and sibling-spline forms take no context")
-        return _made_inverse_form(lib, z, packed, num_blocks, per_dim, kind, dict(rq), logabsdet_accum)
-    cfg = None
-    if kind == MADE_RQ:
-        rq = dict(rq)
-        cfg = _rq_config(rq.pop("num_bins"), rq.pop("tails"), rq.pop("tail_bound", 1.0),
-                         (rq.pop("left", 0.0), rq.pop("right", 1.0), rq.pop("bottom", 0.0), rq.pop("top", 1.0)),
-                         rq.pop("min_bin_width", DEFAULT_MIN_BIN_WIDTH), rq.pop("min_bin_height", DEFAULT_MIN_BIN_HEIGHT),
-                         rq.pop("min_derivative", DEFAULT_MIN_DERIVATIVE), rq.pop("enable_identity_init", False),
-                         rq.pop("wh_divisor", 1.0), True)
-        if rq:
-            raise TypeError("made_inverse: unknown spline arguments %s" % sorted(rq))
-    y = torch.empty_like(z)
-    lad, flags = _logabsdet_target(logabsdet_accum, n, z.device)
-    if flags:
-        if cfg is None:
-            cfg = _hip.RQConfig()          # affine form: only the flags are read
-        cfg.flags = flags
-    err = _err_word(z.device, True)
-    hf, hu, hb, ff, fu, fb, need = packed
-    if need.dtype != torch.int32 or need.numel() != d:
-        raise ValueError("made_inverse: units_needed must hold one int32 per dim")
-    if context is not None:
-        _call("fc_made_inverse_context", lib.fc_made_inverse_context, z.device, _hip.ptr(z), _hip.ptr(context), _hip.ptr(y),
-              _hip.ptr(lad), _hip.ptr(hf), _hip.ptr(hu), _hip.ptr(hb), _hip.ptr(cf), _hip.ptr(cu), _hip.ptr(cb), _hip.ptr(ff),
-              _hip.ptr(fu), _hip.ptr(fb), _hip.ptr(need), _hip.ptr(err), n, d, context.shape[1], num_blocks, per_dim, kind, cfg,
-              _hip.stream_ptr(z.device))
-        _finish(True)
-        return y, lad
-    _call("fc_made_inverse", lib.fc_made_inverse, z.device, _hip.ptr(z), _hip.ptr(y), _hip.ptr(lad), _hip.ptr(hf),
-          _hip.ptr(hu), _hip.ptr(hb), _hip.ptr(ff), _hip.ptr(fu), _hip.ptr(fb), _hip.ptr(need), _hip.ptr(err), n, d, num_blocks, per_dim,
-          kind, cfg, _hip.stream_ptr(z.device))
-    _finish(True)
-    return y, lad
+def _made_pack_matches(packed, d):
+    """``units_needed`` of a ``pack_made_inverse`` pack holds one int32 per dim."""
+    return packed[6].dtype == torch.int32 and packed[6].numel() == d
 
 
-def _made_inverse_form(lib, z, packed, num_blocks, per_dim, kind, form, logabsdet_accum):
-    """``made_inverse`` for ``MADE_SOS`` / ``MADE_SPLINE``: launched and timed under the entries' own names."""
-    n, d = z.shape
+def _made_context_pack(caller, rows_name, device, n, d, context, context_pack, num_blocks, per_dim, count, unit):
+    """``context_pack`` once it, the ``context`` of the [n, d] rows and the shape are what ``fc_<caller>_context`` takes."""
+    if (not torch.is_tensor(context) or context.dtype != torch.float32 or context.dim() != 2 or context.shape[0] != n
+            or not 1 <= context.shape[1] <= 32 or not context.is_contiguous() or context.device != device):
+        raise ValueError("%s: context must be a contiguous float32 [N, C <= 32] tensor on the %s device" % (caller, rows_name))
+    if not made_inverse_context_fits(d, num_blocks, per_dim):
+        raise ValueError("fc_%s_context has no instantiation for D = %d, %d blocks, %d %s" % (caller, d, num_blocks, count, unit))
+    cf, cu, cb = context_pack
+    if cf.numel() != (1 + num_blocks) * 4096 or cu.numel() != 1 + num_blocks or cb.numel() != (1 + num_blocks) * 64:
+        raise ValueError("%s: context_pack does not match num_blocks = %d" % (caller, num_blocks))
+    return cf, cu, cb
+
+
+def _made_arguments(rows, outputs, packed, context_pack, n, d, num_blocks, tail):
+    """The arguments all six device-loop entries take: the input rows (the context last of them), the two outputs, the hidden
+    stack's image (, the context layers': ``context_pack``), the final layer's with ``units_needed`` (, the error word, last
+    in ``outputs``); n, d (, C), num_blocks, the form's ``tail``, the stream.  The tensors go as plain addresses."""
+    tensors = (*rows, *outputs[:2], *packed[:3], *context_pack, *packed[3:], *outputs[2:])
+    sizes = (n, d, rows[-1].shape[1], num_blocks) if context_pack else (n, d, num_blocks)
+    return (*[t.data_ptr() for t in tensors], *sizes, *tail, _hip.stream_ptr(rows[0].device))
+
+
+def _made_inverse_entry(kind, d, num_blocks, per_dim, form, with_context=False, flags=0):
+    """``(entry, its arguments from num_blocks to the stream)`` for ``kind`` and its keyword arguments ``form``; raises what
+    the entries do not hold.  Touches neither the library nor a device.  ``flags``: 1 to add onto the logabsdet."""
+    if kind in (MADE_AFFINE, MADE_RQ):
+        cfg = None
+        if kind == MADE_RQ:
+            rq = dict(form)
+            cfg = _rq_config(rq.pop("num_bins"), rq.pop("tails"), rq.pop("tail_bound", 1.0),
+                             (rq.pop("left", 0.0), rq.pop("right", 1.0), rq.pop("bottom", 0.0), rq.pop("top", 1.0)),
+                             rq.pop("min_bin_width", DEFAULT_MIN_BIN_WIDTH), rq.pop("min_bin_height", DEFAULT_MIN_BIN_HEIGHT),
+                             rq.pop("min_derivative", DEFAULT_MIN_DERIVATIVE), rq.pop("enable_identity_init", False),
+                             rq.pop("wh_divisor", 1.0), True)
+            if rq:
+                raise TypeError("made_inverse: unknown spline arguments %s" % sorted(rq))
+        if flags:
+            cfg = cfg or _hip.RQConfig()          # affine form: only the flags are read
+            cfg.flags = flags
+        return "fc_made_inverse_context" if with_context else "fc_made_inverse", (per_dim, kind, cfg)
+    if with_context:
+        raise ValueError("made_inverse: the sum-of-sigmoids and sibling-spline forms take no context")
+    form = dict(form)
     if kind == MADE_SOS:
         sigmoids = form.pop("n_sigmoids")
         want = 3 * sigmoids + 1
-        tail = (sigmoids, int(form.pop("iterations", 50)), float(form.pop("lim", 120.0)), float(form.pop("offset", 0.0)),
-                float(form.pop("log_scale_postact", 0.0)))
+        name, tail = "fc_made_inverse_sos", (sigmoids, int(form.pop("iterations", 50)), float(form.pop("lim", 120.0)),
+                                             float(form.pop("offset", 0.0)), float(form.pop("log_scale_postact", 0.0)))
     else:
         spline, bins, tails = form.pop("kind"), form.pop("num_bins"), form.pop("tails", None)
         if tails not in (None, "linear"):
@@ -177,22 +157,42 @@ def _made_inverse_form(lib, z, packed, num_blocks, per_dim, kind, form, logabsde
         cfg = _spline_config(spline, bins, tails, form.pop("tail_bound", 1.0),
                              (form.pop("left", 0.0), form.pop("right", 1.0), form.pop("bottom", 0.0), form.pop("top", 1.0)),
                              min_w, min_h, form.pop("width_divisor", 1.0), form.pop("height_divisor", 1.0), True)
-        tail = (cfg,)
+        name, tail = "fc_made_inverse_spline", (cfg,)
     if form:
         raise TypeError("made_inverse: unknown arguments %s" % sorted(form))
     if per_dim != want or per_dim > made_inverse_param_limit(kind) or not made_inverse_form_fits(d, num_blocks, per_dim):
         raise ValueError("made_inverse: no instantiation for D = %d, %d blocks, %d parameters per dim (the form has %d)"
                          % (d, num_blocks, per_dim, want))
-    hf, hu, hb, ff, fu, fb, need = packed
-    if need.dtype != torch.int32 or need.numel() != d:
+    return name, tail + (flags,)
+
+
+def made_inverse(inputs, packed, num_blocks, per_dim, kind, rq=None, logabsdet_accum=None, context=None, context_pack=None):
+    """The D passes of an autoregressive inverse in ONE kernel (``fc_made_inverse``): ``inputs`` [N, D <= 64] (rows a
+    multiple of 16), ``packed`` from ``pack_made_inverse``; ``kind`` ``MADE_AFFINE`` or ``MADE_RQ`` (``rq``: keyword
+    arguments of the spline as for ``rq_spline``).  With ``context`` [N, C <= 32] and ``context_pack`` from
+    ``pack_made_inverse_context`` the conditional form (``fc_made_inverse_context``).  ``MADE_SOS`` (``rq``: ``n_sigmoids``,
+    ``offset``, ``iterations``, ``lim``, ``log_scale_postact`` as for ``sum_of_sigmoids``) and ``MADE_SPLINE`` (``rq``: the
+    keyword arguments of ``piecewise_spline``) run ``fc_made_inverse_sos`` / ``fc_made_inverse_spline``, which take no
+    context.  Returns ``(outputs, logabsdet)``."""
+    lib = _hip.load()
+    z = _prep_2d(inputs)
+    _hip.require_no_grad(inputs, context)
+    n, d = z.shape
+    if n % HIDDEN_ROWS != 0 or d > 64:
+        raise ValueError("fc_made_inverse: rows must be a multiple of %d, D <= 64" % HIDDEN_ROWS)
+    if (context is None) != (context_pack is None):
+        raise ValueError("made_inverse: context and context_pack go together")
+    rows = (z,) if context is None else (z, context)
+    if context is not None:
+        context_pack = _made_context_pack("made_inverse", "inputs'", z.device, n, d, context, context_pack, num_blocks, per_dim,
+                                          per_dim, "parameters per dim")
+    name, tail = _made_inverse_entry(kind, d, num_blocks, per_dim, rq, context is not None, int(logabsdet_accum is not None))
+    lad, _ = _logabsdet_target(logabsdet_accum, n, z.device)
+    if not _made_pack_matches(packed, d):
         raise ValueError("made_inverse: units_needed must hold one int32 per dim")
     y = torch.empty_like(z)
-    lad, flags = _logabsdet_target(logabsdet_accum, n, z.device)
-    err = _err_word(z.device, True)
-    name = "fc_made_inverse_sos" if kind == MADE_SOS else "fc_made_inverse_spline"
-    _call(name, getattr(lib, name), z.device, _hip.ptr(z), _hip.ptr(y), _hip.ptr(lad), _hip.ptr(hf), _hip.ptr(hu),
-          _hip.ptr(hb), _hip.ptr(ff), _hip.ptr(fu), _hip.ptr(fb), _hip.ptr(need), _hip.ptr(err), n, d, num_blocks, *tail,
-          flags, _hip.stream_ptr(z.device))
+    _call(name, getattr(lib, name), z.device,
+          *_made_arguments(rows, (y, lad, _err_word(z.device, True)), packed, context_pack or (), n, d, num_blocks, tail))
     _finish(True)
     return y, lad
 

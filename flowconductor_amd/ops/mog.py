@@ -3,7 +3,7 @@ import torch
 
 from flowconductor_amd import _hip
 from ._core import _call, _logabsdet_target, _prep_2d
-from .conditioner import HIDDEN_ROWS, made_inverse_context_fits
+from .conditioner import HIDDEN_ROWS, _made_arguments, _made_context_pack, _made_pack_matches
 
 
 MOG_MAX_COMPONENTS = 16
@@ -93,27 +93,15 @@ def made_mog_sample(normal, uniform, packed, num_blocks, components, epsilon, co
         raise ValueError("fc_made_mog_sample: 1 <= num_mixture_components <= %d" % MOG_MAX_COMPONENTS)
     if (context is None) != (context_pack is None):
         raise ValueError("made_mog_sample: context and context_pack go together")
-    hf, hu, hb, ff, fu, fb, need = packed
-    if need.dtype != torch.int32 or need.numel() != d or fb.numel() != d * 16 * -(-per_dim // 16):
+    if not _made_pack_matches(packed, d) or packed[5].numel() != d * 16 * -(-per_dim // 16):
         raise ValueError("made_mog_sample: the pack does not match D = %d, %d components" % (d, components))
+    rows = (z, u) if context is None else (z, u, context)
+    if context is not None:
+        context_pack = _made_context_pack("made_mog_sample", "noise's", z.device, n, d, context, context_pack, num_blocks, per_dim,
+                                          components, "components")
     x = torch.empty_like(z)
     logp = torch.empty(n, dtype=torch.float32, device=z.device)
-    if context is None:
-        _call("fc_made_mog_sample", lib.fc_made_mog_sample, z.device, _hip.ptr(z), _hip.ptr(u), _hip.ptr(x), _hip.ptr(logp),
-              _hip.ptr(hf), _hip.ptr(hu), _hip.ptr(hb), _hip.ptr(ff), _hip.ptr(fu), _hip.ptr(fb), _hip.ptr(need), n, d, num_blocks,
-              int(components), float(epsilon), _hip.stream_ptr(z.device))
-        return x, logp
-    if (not torch.is_tensor(context) or context.dtype != torch.float32 or context.dim() != 2 or context.shape[0] != n
-            or not 1 <= context.shape[1] <= 32 or not context.is_contiguous() or context.device != z.device):
-        raise ValueError("made_mog_sample: context must be a contiguous float32 [N, C <= 32] tensor on the noise's device")
-    if not made_inverse_context_fits(d, num_blocks, per_dim):
-        raise ValueError("fc_made_mog_sample_context has no instantiation for D = %d, %d blocks, %d components"
-                         % (d, num_blocks, components))
-    cf, cu, cb = context_pack
-    if cf.numel() != (1 + num_blocks) * 4096 or cu.numel() != 1 + num_blocks or cb.numel() != (1 + num_blocks) * 64:
-        raise ValueError("made_mog_sample: context_pack does not match num_blocks = %d" % num_blocks)
-    _call("fc_made_mog_sample_context", lib.fc_made_mog_sample_context, z.device, _hip.ptr(z), _hip.ptr(u), _hip.ptr(context),
-          _hip.ptr(x), _hip.ptr(logp), _hip.ptr(hf), _hip.ptr(hu), _hip.ptr(hb), _hip.ptr(cf), _hip.ptr(cu), _hip.ptr(cb),
-          _hip.ptr(ff), _hip.ptr(fu), _hip.ptr(fb), _hip.ptr(need), n, d, context.shape[1], num_blocks, int(components),
-          float(epsilon), _hip.stream_ptr(z.device))
+    name = "fc_made_mog_sample" if context is None else "fc_made_mog_sample_context"
+    _call(name, getattr(lib, name), z.device,
+          *_made_arguments(rows, (x, logp), packed, context_pack or (), n, d, num_blocks, (int(components), float(epsilon))))
     return x, logp

@@ -110,27 +110,21 @@ class AutoregressiveTransform(Transform):
         return None
 
     def _device_loop_ok(self, inputs, context):
-        """One kernel for the whole inverse (``fc_made_inverse``, or the form's own entry): a residual-block MADE with
-        hidden <= 64, <= 3 ReLU blocks, no batch norm / active dropout / hooks, D <= 64, float32 rows on the device,
-        inference only, at most ``ops.made_inverse_param_limit`` parameters per dim in an image that fits the LDS
-        (``ops.made_inverse_form_fits``) and at most ``ops.made_inverse_row_limit`` rows.  A net with context layers called with a context takes
+        """One kernel for the whole inverse (``fc_made_inverse``, or the form's own entry): rows the device loop takes
+        (``made.device_loop_rows_ok``), inference only, a MADE it holds (``MADE.device_loop_supported``: at most
+        ``ops.made_inverse_param_limit`` parameters per dim in an image that fits the LDS), no hooks, and at most
+        ``ops.made_inverse_row_limit`` rows.  A net with context layers called with a context takes
         ``fc_made_inverse_context`` where that kernel has the shape (affine and rational-quadratic forms only)."""
         net = self.autoregressive_net
         if context is not None:
             return self._device_loop_context_ok(inputs, context)
-        if not (context is None and inputs.dim() == 2 and inputs.is_cuda and inputs.dtype == torch.float32
-                and 1 < inputs.shape[1] <= 64 and inputs.shape[0] >= 1 and options.get("ar_device_loop")
-                and options.get("fused_hidden") and not self._needs_grad(inputs)):
+        if not (made_module.device_loop_rows_ok(inputs) and not self._needs_grad(inputs)):
             return False
 
         def structure_ok():
             form = self._device_loop_form()
-            code = ops.activation_code(net.activation) if isinstance(net, made_module.MADE) else None
-            return (form is not None and isinstance(net, made_module.MADE) and inputs.shape[1] == net.initial_layer.in_features
-                    and not hasattr(net, "context_layer") and len(net.blocks) <= 3 and net.hip_hidden_supported(None)
-                    and code is not None and code[0] == ops.ACT_RELU and form[1] <= ops.made_inverse_param_limit(form[0])
-                    and ops.made_inverse_form_fits(inputs.shape[1], len(net.blocks), form[1])
-                    and net.final_layer.out_features == form[1] * inputs.shape[1])
+            return (form is not None and isinstance(net, made_module.MADE)
+                    and net.device_loop_supported(inputs.shape[1], form[1], ops.made_inverse_param_limit(form[0])))
 
         if not (ops.static_memo(self, "device_loop_ok", (inputs.shape[1],) + ops.structure_key(net), structure_ok)
                 and not ops.has_hooks(net)):
@@ -142,28 +136,17 @@ class AutoregressiveTransform(Transform):
 
     def _device_loop_context_ok(self, inputs, context):
         """The conditional form (``fc_made_inverse_context``): everything ``_device_loop_ok`` asks without a context, a
-        ``context_layer`` beside the initial layer and in every block, a [N, C <= 32] float32 device context without
-        gradients whose rows match the inputs, and a shape the kernel is instantiated for (its LDS budget)."""
+        ``context_layer`` beside the initial layer and in every block, a [N, C <= 32] float32 context without gradients on
+        the inputs' device, and the affine or rational-quadratic form (the others have no conditional device loop)."""
         net = self.autoregressive_net
-        if not (torch.is_tensor(context) and inputs.dim() == 2 and inputs.is_cuda and inputs.dtype == torch.float32
-                and 1 < inputs.shape[1] <= 64 and inputs.shape[0] >= 1 and options.get("ar_device_loop")
-                and options.get("fused_hidden") and not self._needs_grad(inputs)
-                and context.dim() == 2 and context.shape[0] == inputs.shape[0] and 1 <= context.shape[1] <= 32
-                and context.dtype == torch.float32 and context.device == inputs.device
-                and not (context.requires_grad and torch.is_grad_enabled())):
+        if not (torch.is_tensor(context) and made_module.device_loop_rows_ok(inputs, context) and not self._needs_grad(inputs)
+                and context.device == inputs.device and not (context.requires_grad and torch.is_grad_enabled())):
             return False
 
         def structure_ok():
             form = self._device_loop_form()
-            if form is not None and form[0] not in (ops.MADE_AFFINE, ops.MADE_RQ):
-                return False                # the other forms have no conditional device loop
-            code = ops.activation_code(net.activation) if isinstance(net, made_module.MADE) else None
-            return (form is not None and isinstance(net, made_module.MADE) and inputs.shape[1] == net.initial_layer.in_features
-                    and hasattr(net, "context_layer") and all(hasattr(b, "context_layer") for b in net.blocks)
-                    and len(net.blocks) <= 3 and net.hip_hidden_supported(context)
-                    and code is not None and code[0] == ops.ACT_RELU and form[1] <= 48
-                    and net.final_layer.out_features == form[1] * inputs.shape[1]
-                    and ops.made_inverse_context_fits(inputs.shape[1], len(net.blocks), form[1]))
+            return (form is not None and form[0] in (ops.MADE_AFFINE, ops.MADE_RQ) and isinstance(net, made_module.MADE)
+                    and net.device_loop_supported(inputs.shape[1], form[1], 48, context))
 
         key = (inputs.shape[1], context.shape[1]) + ops.structure_key(net)
         return ops.static_memo(self, "device_loop_context_ok", key, structure_ok) and not ops.has_hooks(net)

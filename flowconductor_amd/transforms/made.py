@@ -8,7 +8,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from flowconductor_amd import ops
+from flowconductor_amd import ops, options
 from flowconductor_amd.utils import torchutils
 
 
@@ -255,6 +255,26 @@ class MADE(nn.Module):
         ctx_key = ops.cache_key(*[t for lin in ctx_layers for t in (lin.weight, lin.bias)], extra=(per_dim,))
         return pack, ops.memo(self, "made_inverse_context_pack", ctx_key,
                               lambda: ops.pack_made_inverse_context(self, features, per_dim))
+
+    def device_loop_supported(self, features, per_dim, param_limit, context=None):
+        """The one-kernel device loops (``ops.made_inverse``, ``ops.made_mog_sample``) hold this net for [N, ``features``]
+        rows and ``per_dim <= param_limit`` outputs per feature: <= 3 ReLU blocks that ``fc_resnet_hidden`` covers (residual,
+        hidden <= 64, no batch norm / active dropout; context layers exactly when there is a ``context``) and an image that
+        fits the LDS.  What depends on the net's structure only: callers keep the answer under ``ops.static_memo``."""
+        code = ops.activation_code(self.activation)
+        fits = ops.made_inverse_form_fits if context is None else ops.made_inverse_context_fits
+        return (features == self.initial_layer.in_features and len(self.blocks) <= 3 and MADE.hip_hidden_supported(self, context)
+                and code is not None and code[0] == ops.ACT_RELU and per_dim <= param_limit
+                and self.final_layer.out_features == per_dim * features and fits(features, len(self.blocks), per_dim))
+
+
+def device_loop_rows_ok(rows, context=None):
+    """Rows the device loops take: [N >= 1, 1 < D <= 64] float32 on the device with ``ar_device_loop`` and ``fused_hidden``
+    on; a ``context``: [N, C <= 32] float32 on the device."""
+    return (rows.dim() == 2 and rows.is_cuda and rows.dtype == torch.float32 and 1 < rows.shape[1] <= 64 and rows.shape[0] >= 1
+            and options.get("ar_device_loop") and options.get("fused_hidden")
+            and (context is None or (context.dim() == 2 and context.is_cuda and context.dtype == torch.float32
+                                     and context.shape[0] == rows.shape[0] and 1 <= context.shape[1] <= 32)))
 
 
 def pad_rows(t):

@@ -80,23 +80,21 @@ def test_row_limit_of_the_default_route():
 
 
 def test_made_inverse_refuses_what_the_entries_do_not_hold():
-    """The form's own argument checks, which come before the library is touched (hence ``lib = None``)."""
+    """The form's own argument checks: the pure step of ``made_inverse``, before the library or a device is touched."""
     from flowconductor_amd.ops import conditioner
 
     t = T.MaskedSumOfSigmoidsTransform(6, 32, n_sigmoids=6)
     kind, per_dim, kw = t._device_loop_form()
-    pack = ops.pack_made_inverse(t.autoregressive_net, 6, per_dim)
-    z = torch.zeros(16, 6)
     with pytest.raises(ValueError, match=r"20 parameters per dim \(the form has 19\)"):       # 3S + 1 does not match
-        conditioner._made_inverse_form(None, z, pack, 2, per_dim + 1, kind, dict(kw), None)
+        conditioner._made_inverse_entry(kind, 6, 2, per_dim + 1, kw)
     with pytest.raises(ValueError, match=r"D = 6, 4 blocks"):                                 # no such instantiation
-        conditioner._made_inverse_form(None, z, pack, 4, per_dim, kind, dict(kw), None)
+        conditioner._made_inverse_entry(kind, 6, 4, per_dim, kw)
     with pytest.raises(TypeError, match="unknown arguments"):
-        conditioner._made_inverse_form(None, z, pack, 2, per_dim, kind, dict(kw, bins=3), None)
+        conditioner._made_inverse_entry(kind, 6, 2, per_dim, dict(kw, bins=3))
     c = T.MaskedPiecewiseCubicAutoregressiveTransform(10, 6, 32)
     kind, per_dim, kw = c._device_loop_form()
     with pytest.raises(ValueError, match=r"23 parameters per dim \(the form has 22\)"):
-        conditioner._made_inverse_form(None, z, pack, 2, per_dim + 1, kind, dict(kw), None)
+        conditioner._made_inverse_entry(kind, 6, 2, per_dim + 1, kw)
 
 
 def _unfragment_final(frag, features, pt):
