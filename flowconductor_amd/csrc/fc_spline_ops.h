@@ -217,7 +217,11 @@ struct QuadraticSplineOp {
     float out;
     if (q.inverse) {
       const float c_ = lc - xn;
-      const float alpha = (-b + sqrtf(b * b - 4.f * a * c_)) / (2.f * a);
+      // The reference's (-b + sqrt(b^2 - 4 a c)) / (2 a) (quadratic.py:139) cancels where the two knot heights of the bin
+      // are close (a -> 0; 0 / 0 at a = 0): its float32 result is then off by up to 6e-4 against its own float64
+      // evaluation on random parameters.  2 c / (-b - sqrt(..)) is the same root without the cancellation (b = left
+      // height x width > 0, c <= 0 inside the bin), as in the cubic's a -> 0 fallback below.
+      const float alpha = (2.f * c_) / (-b - sqrtf(b * b - 4.f * a * c_));
       out = alpha * wk + loc;
       out = clamp01(out);
       lad = -logf(alpha * (hr - hl) + hl);

@@ -374,38 +374,74 @@ inline hipError_t launch_tile_pf(const Op& op, const TileArgs& a, const TilePlan
   return hipGetLastError();
 }
 
-template <class Op>
-inline hipError_t launch_tile(const Op& op, TileArgs a, hipStream_t stream) {
-  if (a.N <= 0) return hipSuccess;
+// What launch_tile launches for one call, decided on the host from the shape and the pointers' alignment alone (no
+// device is touched): at most one persistent launch over the full tiles, then at most one tile_kernel launch over
+// what is left (everything when there is no persistent launch, else the < S leftover samples).
+struct TileRoute {
+  int pf_kind;          // 0: no persistent launch, 1: tile_kernel_pf<Op, 6, 1>, 2: tile_kernel_pf<Op, 8, 2>
+  TileArgs body;        // pf_kind != 0: the full tiles (N = full_tiles * S)
+  TilePlan body_plan;
+  int64_t full_tiles;
+  int has_rest;         // 1: tile_kernel<Op, rest.vec_ok> runs `rest` with rest_plan
+  TileArgs rest;
+  TilePlan rest_plan;
+};
+
+inline hipError_t tile_route(const TileArgs& args, TileRoute* r) {
+  *r = TileRoute{};
+  if (args.N <= 0) return hipSuccess;
+  TileArgs a = args;
   TilePlan plan;
   if (!plan_tile(a, &plan)) return hipErrorInvalidConfiguration;
   a.S = plan.S;
   a.vec_ok = plan.vec_ok;
 
   // Large per-sample-parameter batches: persistent prefetching kernel on the full tiles, then the
-  // < S leftover samples through the one-tile-per-workgroup kernel below.
+  // < S leftover samples through the one-tile-per-workgroup kernel.
   const int64_t full_tiles = a.N / plan.S;
   const int64_t pvec = ((int64_t)plan.S * a.rowlen) / 4, xvec = ((int64_t)plan.S * a.D) / 4;
   if (plan.vec_ok && !a.shared_params && plan.block == kMaxBlock &&
       full_tiles >= 64 && pvec <= 8 * kMaxBlock && xvec <= 2 * kMaxBlock) {
-    TileArgs body = a;
-    body.N = full_tiles * plan.S;
-    hipError_t e = (pvec <= 6 * kMaxBlock && xvec <= kMaxBlock)
-                       ? launch_tile_pf<Op, 6, 1>(op, body, plan, full_tiles, stream)
-                       : launch_tile_pf<Op, 8, 2>(op, body, plan, full_tiles, stream);
-    if (e != hipSuccess) return e;
-    const int64_t done = body.N;
+    r->pf_kind = (pvec <= 6 * kMaxBlock && xvec <= kMaxBlock) ? 1 : 2;
+    r->body = a;
+    r->body.N = full_tiles * plan.S;
+    r->body_plan = plan;
+    r->full_tiles = full_tiles;
+    const int64_t done = r->body.N;
     if (done == a.N) return hipSuccess;
     a.x += done * a.D;
     a.y += done * a.D;
     a.params += done * a.rowlen;
     if (a.logabsdet) a.logabsdet += done;
     a.N -= done;
+    // (Neither this plan nor the grid check below can fail after a persistent launch was chosen: fewer than S rows are
+    //  left, so the plan needs no more LDS than the first and its grid is a handful of tiles.  Were one to fail, nothing
+    //  would be launched at all, where launch_tile once returned the error after the persistent launch.)
     if (!plan_tile(a, &plan)) return hipErrorInvalidConfiguration;
     a.S = plan.S;
     a.vec_ok = plan.vec_ok;
   }
   if (plan.grid > 0x7fffffffLL) return hipErrorInvalidConfiguration;
+  r->has_rest = 1;
+  r->rest = a;
+  r->rest_plan = plan;
+  return hipSuccess;
+}
+
+template <class Op>
+inline hipError_t launch_tile(const Op& op, const TileArgs& args, hipStream_t stream) {
+  TileRoute route;
+  hipError_t routed = tile_route(args, &route);
+  if (routed != hipSuccess) return routed;
+  if (route.pf_kind) {
+    hipError_t e = route.pf_kind == 1
+                       ? launch_tile_pf<Op, 6, 1>(op, route.body, route.body_plan, route.full_tiles, stream)
+                       : launch_tile_pf<Op, 8, 2>(op, route.body, route.body_plan, route.full_tiles, stream);
+    if (e != hipSuccess) return e;
+  }
+  if (!route.has_rest) return hipSuccess;
+  const TileArgs& a = route.rest;
+  const TilePlan& plan = route.rest_plan;
   dim3 grid((unsigned)plan.grid), block((unsigned)plan.block);
   if (plan.lds_bytes > 64 * 1024) {
     hipError_t e;

@@ -685,6 +685,24 @@ int fc_deep_sigmoid_backward(const float* x, const float* raw, const float* grad
  * LDS plan, expand it to per-sample rows instead. */
 int fc_deep_sigmoid_backward_rows(int64_t n, int32_t d, int32_t n_sigmoids);
 
+/* ---- launch route of the tile bijectors ---------------------------------------------------------- */
+/* What fc_affine, fc_rq_spline (its LDS-tile path), fc_sum_of_sigmoids, fc_piecewise_spline and fc_deep_sigmoid launch
+ * for a batch of n rows of d floats with d_t transformed columns and `rowlen` parameter floats per row (d_t times the
+ * entry's parameters per dim), decided by the very host function those entries call.  aligned16: whether x, y and params
+ * are all 16-byte aligned.  Touches no device and makes no HIP call.  out[8]:
+ *   out[0]  persistent prefetching launch over the full tiles: 0 none, 1 the <6, 1> instance (up to 6 parameter and 1
+ *           input float4 per thread and tile), 2 the <8, 2> instance
+ *   out[1]  its samples per tile S          out[2]  its number of full tiles
+ *   out[3]  rows left over after it (< S; 0 without a persistent launch)
+ *   out[4]  one-tile-per-workgroup launch (everything without a persistent launch, else the leftover rows):
+ *           0 none, 1 the 16-byte vector copy kernel, 2 the scalar copy kernel
+ *   out[5]  its S      out[6]  its grid      out[7]  its block
+ * Returns 0, hipErrorInvalidValue for a shape the entries refuse, or hipErrorInvalidConfiguration where a single row
+ * exceeds the LDS plan -- what the entries return for that shape before they launch.  n == 0: 0 with nothing to launch.
+ * Added under ABI version 3 (it changes no existing entry). */
+int fc_tile_route(int64_t n, int32_t d, int32_t d_t, int32_t rowlen, int32_t shared_params, int32_t aligned16,
+                  int64_t* out);
+
 /* ---- unconstrained monotonic neural networks (Clenshaw-Curtis integral of an MLP) --------------- */
 /* z[n, j] = h[n, j, 0] + int_0^x f(t, h[n, j, :]) dt with f = ELU(MLP(t, h)) + 1 and the quadrature
  *   z = h_0 + (x / 2) sum_i w_i f((x / 2)(s_i + 1), h),  s_i = cos(i pi / nb_steps), i = 0..nb_steps,

@@ -5,6 +5,7 @@ import copy
 import pytest
 import torch
 
+import _tile_util
 from _util import build_case, maxdiff
 from flowconductor_amd import ops
 from oracle import torch_oracle as O
@@ -671,6 +672,12 @@ def test_sos_backward_kernel_matches_float64_autograd(s_, d, device):
     y, lad = ops.sum_of_sigmoids_autograd(xg, rg, s_)
     ((y * gy.to(device)).sum() + (lad * gl.to(device)).sum()).backward()
     assert maxdiff(y.detach(), y_ref.detach()) <= 2e-5 * max(1.0, float(y_ref.detach().abs().max()))
+    # logabsdet: the golden margin, 4 x what the oracle's own float32 evaluation of this batch loses against float64
+    with torch.no_grad():
+        _, lad_f32 = O.sos_forward(x, raw[..., :s_], raw[..., s_:2 * s_], raw[..., 2 * s_:3 * s_], raw[..., 3 * s_])
+    lad_floor = maxdiff(lad_f32, lad_ref.detach())
+    print("sos S=%d d=%d logabsdet: err %.3g floor %.3g" % (s_, d, maxdiff(lad.detach(), lad_ref.detach()), lad_floor))
+    assert maxdiff(lad.detach(), lad_ref.detach()) <= 1e-5 * max(1.0, float(lad_ref.detach().abs().max())) + 4 * lad_floor
     assert maxdiff(xg.grad, x64.grad) <= 2e-4 * float(x64.grad.abs().max()) + 1e-6
     assert maxdiff(rg.grad.reshape(r64.grad.shape), r64.grad) <= 2e-4 * float(r64.grad.abs().max()) + 1e-6
 
@@ -736,6 +743,22 @@ def test_piecewise_spline_backward_kernel_matches_float64_autograd(kind, k, tail
     assert type(y.grad_fn).__name__ == "_PiecewiseSplineFunctionBackward"
     ((y * gy.to(device)).sum() + (lad * gl.to(device)).sum()).backward()
     assert maxdiff(y.detach()[:, cols], y_ref.detach()) <= 3e-5 * max(1.0, float(y_ref.detach().abs().max()))
+    # logabsdet per row: the golden margin, 4 x what the oracle's own float32 evaluation of this batch loses against
+    # float64; rows with an element within 1e-5 of an inner knot of the linear spline (where its logabsdet jumps) left out
+    r32 = raw.view(n, len(cols), mult)
+    parts32 = {"linear": [r32], "quadratic": [r32[..., :k], r32[..., k:]],
+               "cubic": [r32[..., :k], r32[..., k:2 * k], r32[..., 2 * k:2 * k + 1], r32[..., 2 * k + 1:]]}[kind]
+    with torch.no_grad():
+        lad_f32 = (O._unconstrained(fn, x[:, cols], bound, tails, parts32) if tails else fn(x[:, cols], *parts32))[1].sum(-1)
+    rows_ref = lad_ref.detach().sum(-1)
+    at_knot = torch.zeros(n, len(cols), dtype=torch.bool)
+    if kind == "linear":
+        at_knot = _tile_util.near_inner_knot(x[:, cols], raw, k, (-bound, bound) if tails else (0.0, 1.0), False)
+    assert float(at_knot.float().mean()) <= _tile_util.MAX_SHARE
+    keep = ~at_knot.any(-1)
+    lad_floor = maxdiff(lad_f32[keep], rows_ref[keep])
+    print("%s K=%d logabsdet: err %.3g floor %.3g" % (kind, k, maxdiff(lad.detach().cpu()[keep], rows_ref[keep]), lad_floor))
+    assert maxdiff(lad.detach().cpu()[keep], rows_ref[keep]) <= 1e-5 * max(1.0, float(rows_ref[keep].abs().max())) + 4 * lad_floor
     ident = [c for c in range(d) if c not in cols.tolist()]
     assert torch.equal(xg.grad[:, ident].cpu(), gy[:, ident])                      # identity columns pass through
     gx_ref = x64.grad[:, cols] 
