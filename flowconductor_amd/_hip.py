@@ -143,6 +143,7 @@ SIGNATURES = {
     "fc_dense_mm": [_P, _P, _P, _P, _I64, _I32, _P],
     "fc_dense_mm_shifted": [_P, _P, _P, _P, _P, _I64, _I32, _P],
     "fc_sylvester_mm": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P],
+    "fc_sylvester_inverse": [_P, _P, _P, _P, _P, _P, _I64, _I32, _P],
     "fc_affine_backward": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P],
     "fc_pack_fragments": [_P, _I32, _P],
     "fc_pack_job_bytes": [],

@@ -53,6 +53,8 @@ from .rowwave import (  # noqa: F401
     hdh_linear_autograd, householder, householder_autograd, linear, linear_per_sample, lu_linear_autograd, planar,
     planar_autograd, sylvester, sylvester_autograd, sylvester_mm, sylvester_mm_supported, upper_linear,
     upper_linear_autograd)
+from .rowwave import (  # noqa: F401
+    SYLVESTER_INVERSE_MAX_FEATURES, sylvester_inverse, sylvester_inverse_supported)
 from .rownorm import (  # noqa: F401
     _RadialFunction, _UnitVectorFunction, _radial_inverse_through_forward, radial, radial_autograd, unit_vector,
     unit_vector_autograd)

@@ -454,6 +454,58 @@ def sylvester(inputs, q_vectors, r1, r2, bias):
     return y, lad
 
 
+SYLVESTER_INVERSE_MAX_FEATURES = 128      # fc_sylvester_inverse keeps 2 * D * 256 bytes of LDS per wavefront
+
+
+def sylvester_inverse_supported(n, d):
+    """Shapes of the Sylvester back-substitution kernel (shared parameters only)."""
+    return 1 <= d <= SYLVESTER_INVERSE_MAX_FEATURES and n >= 0
+
+
+def _rotate(x, q, reverse, matrix):
+    """``householder(x, q, reverse)``; with ``matrix`` (the reflections folded into a dense [D, D] weight) the rows that
+    fill whole 16-row tiles go through the matrix cores instead."""
+    n, d = x.shape
+    if matrix is None or not sylvester_mm_supported(n, d):
+        return householder(x, q, reverse=reverse)
+    body = n - n % SYLVESTER_MM_ROWS
+    out = dense_mm(x[:body], matrix)
+    if body < n:
+        out = torch.cat((out, householder(x[body:], q, reverse=reverse)))
+    return out
+
+
+def sylvester_inverse(inputs, q_vectors, r1, r2, bias, q_matrices=None):
+    """Inverse of ``sylvester`` with shared parameters -> ``(z, logabsdet)`` (the reference has none).
+
+    Three steps: ``c = Q^T y`` (the reflections in reverse order), the back substitution ``fc_sylvester_inverse`` of
+    ``c = v + R2 tanh(R1 v + bias)`` in those coordinates, ``z = Q v`` (the reflections in index order).  ``q_matrices``:
+    optional ``(weight of Q^T, weight of Q)`` for ``dense_mm`` (``householder_matrix(q, reverse).T`` as float32), used
+    where ``sylvester_mm_supported`` holds.  At most ``SYLVESTER_INVERSE_MAX_FEATURES`` features."""
+    lib = _hip.load()
+    y = _rows(inputs)
+    _hip.require_no_grad(inputs)
+    n, d = y.shape
+    if not sylvester_inverse_supported(n, d):
+        raise ValueError("fc_sylvester_inverse: %d features exceed the %d supported" % (d, SYLVESTER_INVERSE_MAX_FEATURES))
+    q = _param(q_vectors, y.device, "q_vectors")
+    r1 = _param(r1, y.device, "R1")
+    r2 = _param(r2, y.device, "R2")
+    bv = _param(bias, y.device, "bias").reshape(-1)
+    if q.dim() != 2 or q.shape[1] != d or r1.shape != (d, d) or r2.shape != (d, d) or bv.numel() != d:
+        raise ValueError("sylvester_inverse takes shared parameters: q [M, %d], R1 / R2 [%d, %d], bias [%d]" % (d, d, d, d))
+    lad = torch.empty(n, dtype=torch.float32, device=y.device)
+    if n == 0:
+        return torch.empty_like(y), lad
+    m_rev, m_fwd = q_matrices if q_matrices is not None else (None, None)
+    r1t, r2t = r1.t().contiguous(), r2.t().contiguous()
+    c = _rotate(y, q, True, m_rev)
+    v = torch.empty_like(c)
+    _call("fc_sylvester_inverse", lib.fc_sylvester_inverse, y.device, _hip.ptr(c), _hip.ptr(v), _hip.ptr(lad),
+          _hip.ptr(r1t), _hip.ptr(r2t), _hip.ptr(bv), n, d, _hip.stream_ptr(y.device))
+    return _rotate(v, q, False, m_fwd), lad
+
+
 SYLVESTER_MM_ROWS = 16
 
 

@@ -1,7 +1,18 @@
 """Planar, Sylvester and radial flows (API of flowcon/transforms/no_analytic_inv/planar.py:13-214).
 
-Planar and Sylvester: forward direction only, like the reference.  Radial: forward as the reference, plus a closed-form
-inverse the reference does not have.  Each is one fused row-per-wavefront HIP kernel.
+Planar: forward direction only, like the reference.  Radial: forward as the reference, plus a closed-form inverse the
+reference does not have.  Each forward is one fused row-per-wavefront HIP kernel.
+
+Sylvester: forward as the reference, plus an inverse the reference does not have (its ``inverse`` raises; a deliberate
+extension, so that flows with a Sylvester layer can sample).  With ``v = Q^T z`` and ``c = Q^T y`` the map is
+``c = v + R2 tanh(R1 v + b)`` with upper-triangular R1 / R2, so v follows by back substitution: for j = D-1 .. 0, with
+``s = b_j + sum_{k>j} R1[j,k] v_k`` and ``t = c_j - sum_{k>j} R2[j,k] tanh(.)_k`` known from the later columns, v_j is the
+root of the strictly increasing scalar function ``v + r2 tanh(r1 v + s) - t`` (slope in ``[1 - |r1 r2|, 1 + |r1 r2|]``,
+``|r1 r2| < 1``), which lies in ``[t - |r2|, t + |r2|]`` and is found by a bracketed Newton search with a fixed cap of
+evaluations.  ``z = Q v`` and logabsdet is minus the forward's expression at the solution.  Float32 device inputs with at
+most 128 features take ``ops.sylvester_inverse`` (one ``fc_sylvester_inverse`` launch, one lane per row, between the two
+applications of Q); CPU tensors, other dtypes and wider layers take the same algorithm as torch ops.  The inverse has no
+gradient: a call that needs one raises and asks for ``torch.no_grad()``.
 """
 import math
 
@@ -10,7 +21,7 @@ import torch
 from torch import nn
 from torch.nn import init
 
-from flowconductor_amd import ops, options
+from flowconductor_amd import _hip, ops, options
 from flowconductor_amd.transforms.base import Transform
 from flowconductor_amd.transforms.orthogonal import HouseholderSequence
 
@@ -119,8 +130,82 @@ class SylvesterTransform(Transform):
                 return y, lad
             return ops.sylvester(inputs, self.Q_orth.q_vectors, self._create_R1(), self._create_R2(), self.bias)
 
+    def _q_matrices(self):
+        """The dense_mm weights of Q^T and Q (the reflections folded in float64), recomputed only when q changed."""
+        q = self.Q_orth.q_vectors
+        return ops.memo(self, "inverse_q", ops.cache_key(q),
+                        lambda: tuple(ops.householder_matrix(q, reverse=r).T.float().contiguous() for r in (True, False)))
+
     def inverse(self, inputs, context=None):
-        raise ops.InverseNotAvailable()
+        """The z with ``forward(z) == inputs`` and minus the forward's logabsdet there (the reference has no inverse):
+        see the module docstring.  Runs without a graph; a call that needs a gradient is refused."""
+        params = (self.Q_orth.q_vectors, self.upper_entries1, self.log_upper_diag1, self.upper_entries2,
+                  self.log_upper_diag2, self.bias)
+        _hip.require_no_grad(inputs, *params)
+        if inputs.dim() != 2 or inputs.shape[1] != self.features:
+            raise ValueError("SylvesterTransform: inputs must be [batch, %d], got %s" % (self.features, tuple(inputs.shape)))
+        with torch.no_grad():
+            n = inputs.shape[0]
+            if inputs.is_cuda and inputs.dtype == torch.float32 and ops.sylvester_inverse_supported(n, self.features):
+                dense = ops.sylvester_mm_supported(n, self.features) and options.get("sylvester_mm")
+                return ops.sylvester_inverse(inputs, self.Q_orth.q_vectors, self._create_R1(), self._create_R2(), self.bias,
+                                             q_matrices=self._q_matrices() if dense else None)
+            return self._inverse_composition(inputs)
+
+    def _inverse_composition(self, inputs):
+        """The same back substitution as ``fc_sylvester_inverse`` in torch ops, in the inputs' dtype and on their device
+        (vectorised over the batch, D sequential columns): CPU tensors, other dtypes, more features than the kernel takes."""
+        kw = dict(dtype=inputs.dtype, device=inputs.device)
+        q = self.Q_orth.q_vectors.to(**kw)
+        r1 = self._create_R(self.upper_entries1.to(**kw), self.log_upper_diag1.to(**kw))     # tanh in that dtype too
+        r2 = self._create_R(self.upper_entries2.to(**kw), self.log_upper_diag2.to(**kw))
+        bias = self.bias.to(**kw)
+        rd = torch.diagonal(r1) * torch.diagonal(r2)
+        c = _reflect(inputs, q.flip(0))                     # Q^T y
+        v, th = torch.zeros_like(c), torch.zeros_like(c)
+        for j in range(self.features - 1, -1, -1):
+            s = bias[j] + v[:, j + 1:] @ r1[j, j + 1:]
+            t = c[:, j] - th[:, j + 1:] @ r2[j, j + 1:]
+            v[:, j], th[:, j] = _solve_column(r1[j, j], r2[j, j], rd[j], s, t)
+        logabsdet = -torch.log(1 + (1 - th ** 2) * rd).sum(-1)
+        return _reflect(v, q), logabsdet                    # Q v
+
+
+def _reflect(x, q_vectors):
+    """The Householder reflections ``q_vectors [K, D]`` applied to the rows of ``x`` in index order."""
+    for q in q_vectors:
+        x = x - (x @ q).unsqueeze(-1) * ((2.0 / (q @ q)) * q)
+    return x
+
+
+def _solve_column(r1, r2, rd, s, t):
+    """Roots v [N] of ``v + r2 tanh(r1 v + s) - t = 0`` and ``tanh(r1 v + s)`` there, for scalars r1, r2 (|r1 r2| < 1: the
+    residual is strictly increasing, its root lies in ``[t - |r2|, t + |r2|]``) and batches s, t.
+
+    Bracketed Newton: every evaluation moves one end of the bracket to the current point by the sign of the residual; the next
+    point is the Newton iterate when it lies in the CLOSED bracket, else the midpoint.  An element stops when its residual
+    is at the rounding level of its own evaluation, ``2 eps (|t| + |r2|)``, when the step no longer moves it, or at the
+    cap of evaluations; a NaN element stops at once and stays NaN."""
+    eps = torch.finfo(t.dtype).eps
+    cap = 16 if t.dtype == torch.float32 else 48      # float32: the cap of fc_sylvester_inverse
+    ar2 = r2.abs()
+    tol = 2 * eps * (t.abs() + ar2)
+    lo, hi = t - ar2, t + ar2
+    v = t.clone()
+    active = torch.ones_like(t, dtype=torch.bool)
+    for it in range(cap):
+        th = torch.tanh(r1 * v + s)
+        g = (v + r2 * th) - t
+        active = active & (g.abs() > tol)
+        if it == cap - 1 or not bool(active.any()):
+            break
+        lo = torch.where(active & (g < 0), v, lo)
+        hi = torch.where(active & (g > 0), v, hi)
+        vn = v - g / (1 + rd * (1 - th * th))
+        vn = torch.where((vn >= lo) & (vn <= hi), vn, 0.5 * (lo + hi))
+        active = active & (vn != v)
+        v = torch.where(active, vn, v)
+    return v, th
 
 
 class RadialTransform(Transform):

@@ -51,7 +51,8 @@ extern "C" {
  * fc_umnn and fc_umnn_backward(_workspace), for the row-norm entries fc_radial(_backward) / fc_unit_vector(_backward) and for the discrete / uniform base
  * entries fc_bernoulli_log_prob(_backward), fc_bernoulli_sample and fc_box_log_prob, and for the batch-statistics entries
  * fc_batchnorm_train(_backward), fc_column_sums and fc_colstats_workspace), and for the device loops of the
- * sum-of-sigmoids and sibling-spline layers fc_made_inverse_sos / fc_made_inverse_spline). */
+ * sum-of-sigmoids and sibling-spline layers fc_made_inverse_sos / fc_made_inverse_spline, and for the Sylvester
+ * back substitution fc_sylvester_inverse). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -879,6 +880,22 @@ int fc_linear_per_sample(const float* x, float* y, float* logabsdet, const float
 int fc_sylvester(const float* x, float* y, float* logabsdet, const float* q, const float* r1_t,
                  const float* r2_t, const float* bias, const float* r_diag_prod, int64_t n, int32_t d,
                  int32_t num_householder, int32_t per_sample, void* stream);
+
+/* Inverse of the Sylvester flow's triangular middle with batch-shared parameters, in the coordinates rotated by Q (the
+ * reference has no inverse; the caller applies Q^T before and Q after, flowconductor_amd.ops.sylvester_inverse):
+ * given c [n, d] = Q^T y, finds v [n, d] with c = v + R2 tanh(R1 v + bias) by back substitution, j = d-1 .. 0:
+ *   s = bias_j + sum_{k>j} R1[j][k] v_k,  t = c_j - sum_{k>j} R2[j][k] th_k,
+ *   v_j the root of v + r2 tanh(r1 v + s) = t in [t - |r2|, t + |r2|] (r1 = R1[j][j], r2 = R2[j][j], |r1 r2| < 1:
+ *   unique), th_j = tanh(r1 v_j + s),
+ * by a bracketed Newton search of at most 16 evaluations (the Newton point where it lies in the closed bracket, else
+ * the midpoint; stops early once the step no longer changes v), and
+ *   logabsdet[n] = -sum_j log(1 + r1_j r2_j (1 - th_j^2)).
+ * r1_t / r2_t are the upper-triangular matrices TRANSPOSED (r1_t[k*d + j] = R1[j][k]), as for fc_sylvester.  One lane
+ * per row, 64 rows per wavefront, v and th of a wavefront in LDS: d <= 128, anything else returns
+ * hipErrorInvalidValue.  A NaN row yields NaN in that row only.  c != v.  Added under ABI version 3 (it changes no
+ * existing entry). */
+int fc_sylvester_inverse(const float* c, float* v, float* logabsdet, const float* r1_t, const float* r2_t,
+                         const float* bias, int64_t n, int32_t d, void* stream);
 
 /* Shared-weight Sylvester flow as two dense products on the matrix cores (planar.py:144-166 with the batch-
  * independent chains folded into W1 = R1 Q^T and W2 = Q R2, both [d, d] row-major):
