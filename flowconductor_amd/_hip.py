@@ -111,6 +111,9 @@ SIGNATURES = {
     "fc_planar_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P],
     "fc_sylvester_mid_backward": [_P, _P, _P, _P, _P, _P, _I64, _I32, _P],
     "fc_householder_backward": [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P],
+    "fc_linear_per_sample_backward": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _P],
+    "fc_householder_backward_per_sample": [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P],
+    "fc_planar_backward_per_sample": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P],
     "fc_hdh_linear": [_P] * 7 + [_I64, _I32, _I32, _I32, _I32, _I32, _P],
     "fc_hdh_linear_backward": [_P] * 12 + [_I64, _I32, _I32, _I32, _I32, _I32, _P],
     "fc_elementwise": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _F, _F, _F, _F, _P],

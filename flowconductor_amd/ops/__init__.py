@@ -55,6 +55,8 @@ from .rowwave import (  # noqa: F401
     upper_linear_autograd)
 from .rowwave import (  # noqa: F401
     SYLVESTER_INVERSE_MAX_FEATURES, sylvester_inverse, sylvester_inverse_supported)
+from .rowwave import (  # noqa: F401
+    _HouseholderPerSampleFunction, _LinearPerSampleFunction, _PlanarPerSampleFunction, linear_per_sample_autograd)
 from .rownorm import (  # noqa: F401
     _RadialFunction, _UnitVectorFunction, _radial_inverse_through_forward, radial, radial_autograd, unit_vector,
     unit_vector_autograd)

@@ -184,6 +184,64 @@ def linear_per_sample(inputs, matrices, mode=PER_SAMPLE_DENSE, offdiag_scale=1.0
     return (y, lad) if want_logabsdet else y
 
 
+class _LinearPerSampleFunction(torch.autograd.Function):
+    """``linear_per_sample`` with its HIP backward kernel (``fc_linear_per_sample_backward``): gradients for the rows,
+    the per-sample matrices (written once per row: no reduction) and a 0-dim ``offdiag_scale`` tensor (the sum of the
+    kernel's per-row terms).  Saves the inputs -- for the LU inverse the OUTPUT -- and the matrices."""
+
+    @staticmethod
+    def forward(ctx, inputs, matrices, offdiag_scale, mode, eps):
+        sp = float(offdiag_scale.detach()) if isinstance(offdiag_scale, torch.Tensor) else float(offdiag_scale)
+        with torch.no_grad():
+            outputs, logabsdet = linear_per_sample(inputs, matrices.detach(), mode=mode, offdiag_scale=sp, eps=eps,
+                                                   want_logabsdet=True)
+        ctx.save_for_backward(outputs if mode == PER_SAMPLE_LU_INVERSE else inputs, matrices)
+        ctx.mode, ctx.sp, ctx.eps = mode, sp, eps
+        ctx.sp_like = offdiag_scale if isinstance(offdiag_scale, torch.Tensor) and offdiag_scale.requires_grad else None
+        if mode < PER_SAMPLE_LU_FORWARD:
+            ctx.mark_non_differentiable(logabsdet)      # the dense forms have no log-determinant of their own (zeros)
+        return outputs, logabsdet
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable      # no double backward: create_graph=True raises instead of going silent
+    def backward(ctx, grad_outputs, grad_logabsdet):
+        saved, matrices = ctx.saved_tensors
+        lib = _hip.load()
+        x = _hip.dev_f32(saved, "inputs")
+        m = _hip.dev_f32(matrices, "matrices")
+        n, d = x.shape
+        gy = _hip.dev_f32(grad_outputs.contiguous() if grad_outputs is not None else torch.zeros_like(x), "grad_outputs")
+        lu = ctx.mode >= PER_SAMPLE_LU_FORWARD
+        gl = _hip.dev_f32(grad_logabsdet.contiguous(), "grad_logabsdet") if lu and grad_logabsdet is not None else None
+        gx = torch.empty_like(x)
+        gm = torch.empty_like(m)
+        gsp = torch.empty(n, dtype=torch.float32, device=x.device) if lu and ctx.sp_like is not None else None
+        _call("fc_linear_per_sample_backward", lib.fc_linear_per_sample_backward, x.device, _hip.ptr(x), _hip.ptr(gy),
+              _hip.ptr(gl), _hip.ptr(m), _hip.ptr(gx), _hip.ptr(gm), _hip.ptr(gsp), n, d, ctx.mode, ctx.sp, float(ctx.eps),
+              _hip.stream_ptr(x.device))
+        g_scale = None
+        if ctx.sp_like is not None:
+            g_scale = gsp.sum().to(ctx.sp_like.dtype).view_as(ctx.sp_like) if lu else torch.zeros_like(ctx.sp_like)
+        return gx, gm, g_scale, None, None
+
+
+def linear_per_sample_autograd(inputs, matrices, mode=PER_SAMPLE_DENSE, offdiag_scale=1.0, eps=0.0, want_logabsdet=False):
+    """``linear_per_sample`` behind ``_LinearPerSampleFunction`` when a gradient is needed (``offdiag_scale`` may be a
+    0-dim tensor with a graph; the kernel receives its float value); otherwise exactly ``linear_per_sample``."""
+    scale_grad = isinstance(offdiag_scale, torch.Tensor) and offdiag_scale.requires_grad
+    if torch.is_grad_enabled() and (inputs.requires_grad or matrices.requires_grad or scale_grad):
+        x = _rows(inputs)
+        m = _hip.dev_f32(matrices, "matrices")
+        if m.numel() != x.shape[0] * x.shape[1] * x.shape[1]:
+            raise ValueError("matrices must be [%d, %d, %d]" % (x.shape[0], x.shape[1], x.shape[1]))
+        if scale_grad:
+            offdiag_scale = _hip.dev_f32(offdiag_scale, "offdiag_scale")
+        outputs, logabsdet = _LinearPerSampleFunction.apply(x, m, offdiag_scale, mode, eps)
+        return (outputs, logabsdet) if want_logabsdet else outputs
+    return linear_per_sample(inputs, matrices, mode=mode, offdiag_scale=float(offdiag_scale), eps=eps,
+                             want_logabsdet=want_logabsdet)
+
+
 LINEAR_DENSE, LINEAR_LU_FORWARD, LINEAR_LU_INVERSE, LINEAR_DENSE_SHIFTED = 0, 1, 2, 3
 
 
@@ -232,11 +290,49 @@ class _HouseholderFunction(torch.autograd.Function):
         return gx, gq, None
 
 
+class _HouseholderPerSampleFunction(torch.autograd.Function):
+    """``householder`` with per-sample q-vectors ``[N, K, D]`` and its HIP backward kernel
+    (``fc_householder_backward_per_sample``: the saved OUTPUT is walked back through the involutions with each row's own
+    q block; the q gradient is written per row and reflection)."""
+
+    @staticmethod
+    def forward(ctx, inputs, q_vectors, reverse):
+        with torch.no_grad():
+            outputs = householder(inputs, q_vectors.detach(), reverse=reverse)
+        ctx.save_for_backward(outputs, q_vectors)
+        ctx.reverse = reverse
+        return outputs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable      # no double backward: create_graph=True raises instead of going silent
+    def backward(ctx, grad_outputs):
+        outputs, q_vectors = ctx.saved_tensors
+        lib = _hip.load()
+        y = _hip.dev_f32(outputs, "outputs")
+        q = _hip.dev_f32(q_vectors, "q_vectors")
+        gy = _hip.dev_f32(grad_outputs.contiguous(), "grad_outputs")
+        n, d = y.shape
+        gx = torch.empty_like(y)
+        gq = torch.empty_like(q)
+        _call("fc_householder_backward_per_sample", lib.fc_householder_backward_per_sample, y.device, _hip.ptr(y),
+              _hip.ptr(gy), _hip.ptr(q), _hip.ptr(gx), _hip.ptr(gq), n, d, q.shape[1], 1 if ctx.reverse else 0,
+              _hip.stream_ptr(y.device))
+        return gx, gq, None
+
+
 def householder_autograd(inputs, q_vectors, reverse=False):
-    """``householder`` -> (outputs, zeros); under autograd the shared-q form sits behind ``_HouseholderFunction``."""
-    if torch.is_grad_enabled() and (inputs.requires_grad or q_vectors.requires_grad) and q_vectors.dim() == 2:
-        x = _prep_2d(inputs)
-        return _HouseholderFunction.apply(x, q_vectors, bool(reverse)), x.new_zeros(x.shape[0])
+    """``householder`` -> (outputs, zeros); under autograd the shared-q form sits behind ``_HouseholderFunction`` and the
+    per-sample form ``[N, K, D]`` behind ``_HouseholderPerSampleFunction``."""
+    if torch.is_grad_enabled() and (inputs.requires_grad or q_vectors.requires_grad):
+        if q_vectors.dim() == 2:
+            x = _prep_2d(inputs)
+            return _HouseholderFunction.apply(x, q_vectors, bool(reverse)), x.new_zeros(x.shape[0])
+        if q_vectors.dim() == 3:
+            x = _rows(inputs)
+            q = _hip.dev_f32(q_vectors, "q_vectors")
+            if q.shape[0] != x.shape[0] or q.shape[2] != x.shape[1]:
+                raise ValueError("q_vectors of shape %s do not match inputs %s" % (tuple(q.shape), tuple(x.shape)))
+            return _HouseholderPerSampleFunction.apply(x, q, bool(reverse)), x.new_zeros(x.shape[0])
     return householder(inputs, q_vectors, reverse=reverse), inputs.new_zeros(inputs.shape[0])
 
 
@@ -355,11 +451,45 @@ class _PlanarFunction(torch.autograd.Function):
         return gx, gpar[:d].view_as(w), gpar[d:2 * d].view_as(u_hat), gpar[2 * d:].view_as(b)
 
 
-def planar_autograd(inputs, w, u_hat, b):
-    """Shared-parameter planar flow (no_analytic_inv/planar.py:30-49) with an autograd node when needed."""
+class _PlanarPerSampleFunction(torch.autograd.Function):
+    """``planar(per_sample=True)`` with its HIP backward kernel (``fc_planar_backward_per_sample``): ``w``, ``u_hat``
+    ``[N, D]`` and ``b`` ``[N]`` per row, their gradients written per row."""
+
+    @staticmethod
+    def forward(ctx, inputs, w, u_hat, b):
+        with torch.no_grad():
+            outputs, logabsdet = planar(inputs, w.detach(), u_hat.detach(), b.detach(), per_sample=True)
+        ctx.save_for_backward(inputs, w, u_hat, b)
+        return outputs, logabsdet
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable      # no double backward: create_graph=True raises instead of going silent
+    def backward(ctx, grad_outputs, grad_logabsdet):
+        x, wv, uv, bv = ctx.saved_tensors
+        lib = _hip.load()
+        n, d = x.shape
+        gy = _hip.dev_f32(grad_outputs.contiguous() if grad_outputs is not None else torch.zeros_like(x), "grad_outputs")
+        gl = None if grad_logabsdet is None else _hip.dev_f32(grad_logabsdet.contiguous(), "grad_logabsdet")
+        gx, gw, gu, gb = torch.empty_like(x), torch.empty_like(wv), torch.empty_like(uv), torch.empty_like(bv)
+        _call("fc_planar_backward_per_sample", lib.fc_planar_backward_per_sample, x.device, _hip.ptr(x), _hip.ptr(gy),
+              _hip.ptr(gl), _hip.ptr(wv), _hip.ptr(uv), _hip.ptr(bv), _hip.ptr(gx), _hip.ptr(gw), _hip.ptr(gu), _hip.ptr(gb),
+              n, d, _hip.stream_ptr(x.device))
+        return gx, gw, gu, gb
+
+
+def planar_autograd(inputs, w, u_hat, b, per_sample=False):
+    """Planar flow (no_analytic_inv/planar.py:30-49) with an autograd node when needed: shared parameters, or with
+    ``per_sample`` the [N, D] / [N] parameters of ConditionalPlanarTransform (conditional.py:824-838)."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (inputs, w, u_hat, b)):
-        return _PlanarFunction.apply(_prep_2d(inputs), w, u_hat, b)
-    return planar(inputs, w, u_hat, b)
+        if not per_sample:
+            return _PlanarFunction.apply(_prep_2d(inputs), w, u_hat, b)
+        x = _rows(inputs)
+        n, d = x.shape
+        wv, uv, bv = (_hip.dev_f32(t, name) for t, name in ((w, "w"), (u_hat, "u"), (b, "b")))
+        if wv.numel() != n * d or uv.numel() != n * d or bv.numel() != n:
+            raise ValueError("planar parameters do not match %d features" % d)
+        return _PlanarPerSampleFunction.apply(x, wv.reshape(n, d), uv.reshape(n, d), bv.reshape(n))
+    return planar(inputs, w, u_hat, b, per_sample=per_sample)
 
 
 def _householder_backward(outputs, grad_outputs, q, reverse):
@@ -415,9 +545,23 @@ class _SylvesterFunction(torch.autograd.Function):
             return gy + g_x2, gq_a + gq_b, g_r1, g_r2, sums[0].view_as(bias)
 
 
+def _sylvester_per_sample_composed(inputs, q_vectors, r1, r2, bias):
+    """Per-sample Sylvester flow under autograd, composed of the per-sample nodes (no kernel of its own): the two
+    Householder sequences and the two products with R1 / R2 (``PER_SAMPLE_DENSE``, which reads the zero triangle of the
+    upper-triangular matrices too) on their HIP kernels, tanh and the log-determinant as torch ops on [N, D]."""
+    qtz, _ = householder_autograd(inputs, q_vectors, reverse=True)                      # Q^T z
+    act = torch.tanh(linear_per_sample_autograd(qtz, r1, mode=PER_SAMPLE_DENSE) + bias)
+    rot, _ = householder_autograd(linear_per_sample_autograd(act, r2, mode=PER_SAMPLE_DENSE), q_vectors)
+    rdiag = torch.diagonal(r1, dim1=-2, dim2=-1) * torch.diagonal(r2, dim1=-2, dim2=-1)
+    return inputs + rot, torch.log(1 + (1 - act ** 2) * rdiag).sum(-1)
+
+
 def sylvester_autograd(inputs, q_vectors, r1, r2, bias):
-    """Shared-parameter Sylvester flow (no_analytic_inv/planar.py:144-166) with an autograd node when needed."""
+    """Sylvester flow (no_analytic_inv/planar.py:144-166) with autograd when needed: one node for shared parameters, the
+    per-sample nodes composed for per-sample ones (``r1`` [N, D, D])."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (inputs, q_vectors, r1, r2, bias)):
+        if r1.dim() == 3:
+            return _sylvester_per_sample_composed(inputs, q_vectors, r1, r2, bias)
         return _SylvesterFunction.apply(_prep_2d(inputs), q_vectors, r1, r2, bias)
     return sylvester(inputs, q_vectors, r1, r2, bias)
 

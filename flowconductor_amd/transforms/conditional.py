@@ -172,6 +172,8 @@ class ConditionalLUTransform(ConditionalTransform):
     """Per-sample W = L U from one raw [F, F] block per sample (conditional.py:275-346):
     L = sp * tril(M, -1) + I, U = sp * triu(M, 1) + diag(softplus(diag M) + eps), sp = softplus(scale_non_diag)."""
 
+    _HIP_AUTOGRAD = True      # fc_linear_per_sample_backward: the hyper-network and scale_non_diag train
+
     def __init__(self, features, hidden_features, context_features, num_blocks=2, use_residual_blocks=True,
                  activation=F.relu, dropout_probability=0.0, use_batch_norm=False, eps=1e-7):
         super().__init__(features=features, hidden_features=hidden_features, context_features=context_features,
@@ -195,13 +197,19 @@ class ConditionalLUTransform(ConditionalTransform):
         return ops.memo(self, "offdiag_scale", ops.cache_key(self.scale_non_diag),
                         lambda: float(F.softplus(self.scale_non_diag.detach())))
 
+    def _scale_operand(self):
+        """softplus(scale_non_diag): as a tensor with a graph when the parameter trains, else the memoised float."""
+        if torch.is_grad_enabled() and self.scale_non_diag.requires_grad:
+            return F.softplus(self.scale_non_diag)
+        return self._offdiag_scale()
+
     def _forward_given_params(self, inputs, conditional_params):
-        return ops.linear_per_sample(inputs, conditional_params, mode=ops.PER_SAMPLE_LU_FORWARD,
-                                     offdiag_scale=self._offdiag_scale(), eps=self.eps, want_logabsdet=True)
+        return ops.linear_per_sample_autograd(inputs, conditional_params, mode=ops.PER_SAMPLE_LU_FORWARD,
+                                              offdiag_scale=self._scale_operand(), eps=self.eps, want_logabsdet=True)
 
     def _inverse_given_params(self, inputs, conditional_params):
-        return ops.linear_per_sample(inputs, conditional_params, mode=ops.PER_SAMPLE_LU_INVERSE,
-                                     offdiag_scale=self._offdiag_scale(), eps=self.eps, want_logabsdet=True)
+        return ops.linear_per_sample_autograd(inputs, conditional_params, mode=ops.PER_SAMPLE_LU_INVERSE,
+                                              offdiag_scale=self._scale_operand(), eps=self.eps, want_logabsdet=True)
 
     def _unconstrained_entries(self, conditional_params):
         return conditional_params.view(-1, self.features, self._output_dim_multiplier())
@@ -238,11 +246,12 @@ class ConditionalRotationTransform(ConditionalTransform):
         return torch.cat([c, -s, s, c], -1).view(-1, self.features, self.features)
 
     def _forward_given_params(self, inputs, conditional_params):
-        outputs = ops.linear_per_sample(inputs, self.build_matrix(conditional_params), mode=ops.PER_SAMPLE_DENSE)
+        outputs = ops.linear_per_sample_autograd(inputs, self.build_matrix(conditional_params), mode=ops.PER_SAMPLE_DENSE)
         return outputs, inputs.new_zeros(inputs.shape[0])
 
     def _inverse_given_params(self, inputs, conditional_params):
-        outputs = ops.linear_per_sample(inputs, self.build_matrix(conditional_params), mode=ops.PER_SAMPLE_DENSE_T)
+        outputs = ops.linear_per_sample_autograd(inputs, self.build_matrix(conditional_params),
+                                                 mode=ops.PER_SAMPLE_DENSE_T)
         return outputs, inputs.new_zeros(inputs.shape[0])
 
 
@@ -291,11 +300,11 @@ class ConditionalSVDTransform(ConditionalTransform):
 
     def _forward_given_params(self, inputs, conditional_params):
         q_u, q_v, s, bias = self._parts(conditional_params)
-        vtx = ops.householder(inputs, q_v)
+        vtx, _ = ops.householder_autograd(inputs, q_v)
         shift = bias if bias is not None else torch.zeros_like(s)
         svtx, _ = ops.affine_coupling(vtx, torch.cat((torch.zeros_like(s), s), dim=1), None,
                                       activation=ops.AFFINE_SCALE_GIVEN)
-        usvtx = ops.householder(svtx, q_u)
+        usvtx, _ = ops.householder_autograd(svtx, q_u)
         if bias is not None:
             usvtx, _ = ops.affine_coupling(usvtx, shift, None, activation=ops.AFFINE_ADDITIVE)
         return usvtx, s.log().sum(-1)
@@ -305,10 +314,10 @@ class ConditionalSVDTransform(ConditionalTransform):
         y = inputs
         if bias is not None:
             y, _ = ops.affine_coupling(y, bias, None, activation=ops.AFFINE_ADDITIVE, inverse=True)
-        uty = ops.householder(y, q_u, reverse=True)
+        uty, _ = ops.householder_autograd(y, q_u, reverse=True)
         sinv, _ = ops.affine_coupling(uty, torch.cat((torch.zeros_like(s), s), dim=1), None,
                                       activation=ops.AFFINE_SCALE_GIVEN, inverse=True)
-        outputs = ops.householder(sinv, q_v, reverse=True)
+        outputs, _ = ops.householder_autograd(sinv, q_v, reverse=True)
         return outputs.squeeze(), -s.log().sum(-1)
 
     def _parts(self, conditional_params):
@@ -503,8 +512,8 @@ class ConditionalPlanarTransform(ConditionalTransform):
 
     def _forward_given_params(self, inputs, conditional_params):
         u_, w_, b_ = self._create_uwb(conditional_params)
-        return ops.planar(inputs, w_.reshape(-1, self.features), u_.reshape(-1, self.features), b_.reshape(-1),
-                          per_sample=True)
+        return ops.planar_autograd(inputs, w_.reshape(-1, self.features), u_.reshape(-1, self.features), b_.reshape(-1),
+                                   per_sample=True)
 
     def _inverse_given_params(self, inputs, conditional_params):
         raise NotImplementedError()
@@ -555,7 +564,7 @@ class ConditionalSylvesterTransform(ConditionalTransform):
 
     def _forward_given_params(self, inputs, conditional_params):
         r1, r2, q_vectors, bias = self._create_mats(conditional_params)
-        return ops.sylvester(inputs, q_vectors, r1, r2, bias)
+        return ops.sylvester_autograd(inputs, q_vectors, r1, r2, bias)
 
     def _inverse_given_params(self, inputs, conditional_params):
         raise NotImplementedError()

@@ -52,7 +52,8 @@ extern "C" {
  * entries fc_bernoulli_log_prob(_backward), fc_bernoulli_sample and fc_box_log_prob, and for the batch-statistics entries
  * fc_batchnorm_train(_backward), fc_column_sums and fc_colstats_workspace), and for the device loops of the
  * sum-of-sigmoids and sibling-spline layers fc_made_inverse_sos / fc_made_inverse_spline, and for the Sylvester
- * back substitution fc_sylvester_inverse). */
+ * back substitution fc_sylvester_inverse, and for the per-sample backward entries fc_linear_per_sample_backward,
+ * fc_householder_backward_per_sample and fc_planar_backward_per_sample). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -852,6 +853,39 @@ int fc_unit_vector_backward(const float* x_or_y, const float* grad_out, const fl
 int fc_sylvester_mid_backward(const float* pre, float* grad_act_inout, const float* grad_logabsdet,
                               const float* r_diag_prod, float* grad_bias, float* grad_r_diag_prod, int64_t n, int32_t d,
                               void* stream);
+
+/* ---- backward with PER-SAMPLE parameters (a hyper-network's output) ------------------------------
+ * One wavefront owns one sample row and that sample's parameter block, so a parameter gradient is WRITTEN once per row
+ * (nothing to zero first): no batch reduction, no atomics, bitwise reproducible.  d <= 512; n == 0 launches nothing.
+ * Added under ABI version 3 (they change no existing entry).
+ *
+ * fc_linear_per_sample_backward: the four modes of fc_linear_per_sample, m [n, d, d] raw, sp = offdiag_scale,
+ * dg_j = softplus(M_jj) + eps.  grad_logabsdet [n] may be NULL (zeros; unused in modes 0 and 1), grad_sp_rows [n] may be NULL.
+ *   mode 0 (y = M x):    x_or_out = x;  grad_in = M^T grad_out,  grad_m_ij = grad_out_i x_j
+ *   mode 1 (y = M^T x):  x_or_out = x;  grad_in = M grad_out,    grad_m_ij = x_i grad_out_j
+ *   mode 2 (y = L U x, logabsdet = sum log dg):  x_or_out = x;  with t = U x, g_t = L^T grad_out:  grad_in = U^T g_t,
+ *     grad_m_ij = sp grad_out_i t_j (j < i), sp g_t_i x_j (j > i), (g_t_i x_i + grad_logabsdet / dg_i) sigmoid(M_ii) (j = i),
+ *     grad_sp_rows = sum_{j<i} M_ij grad_out_i t_j + sum_{j>i} M_ij g_t_i x_j  (d / d offdiag_scale of this row's terms)
+ *   mode 3 (x = U^-1 L^-1 y, logabsdet = -sum log dg):  x_or_out = the saved OUTPUT x;  grad_in = L^-T U^-T grad_out,
+ *     grad_m / grad_sp_rows = mode 2's expressions at the input x with upstream -grad_in and -grad_logabsdet.
+ *   Modes 0 / 1 write grad_sp_rows = 0.  Modes 2 / 3 read m twice and write grad_m once; d <= 16 runs four samples per
+ *   wavefront with the matrix in registers.
+ *
+ * fc_householder_backward_per_sample: fc_householder_backward with q [n, K, d] indexed per row, from the saved OUTPUT y;
+ * grad_q [n, K, d] is written per row and reflection.  num_transforms == 0: grad_x = grad_y (q, grad_q may be NULL).
+ *
+ * fc_planar_backward_per_sample: fc_planar_backward with w, u_hat [n, d] and b [n] per row (per_sample != 0 of fc_planar);
+ * grad_w, grad_u_hat [n, d] and grad_b [n] are written per row.  grad_logabsdet may be NULL (zeros). */
+int fc_linear_per_sample_backward(const float* x_or_out, const float* grad_out, const float* grad_logabsdet,
+                                  const float* m, float* grad_in, float* grad_m, float* grad_sp_rows, int64_t n, int32_t d,
+                                  int32_t mode, float offdiag_scale, float eps, void* stream);
+
+int fc_householder_backward_per_sample(const float* y, const float* grad_y, const float* q, float* grad_x, float* grad_q,
+                                       int64_t n, int32_t d, int32_t num_transforms, int32_t reverse, void* stream);
+
+int fc_planar_backward_per_sample(const float* x, const float* grad_y, const float* grad_logabsdet, const float* w,
+                                  const float* u_hat, const float* b, float* grad_x, float* grad_w, float* grad_u_hat,
+                                  float* grad_b, int64_t n, int32_t d, void* stream);
 
 /* Dense linear maps with batch-shared [d, d] matrices given TRANSPOSED (a_t[j*d + i] = A[i][j]).
  * mode 0: y = A x + bias                        (linear.py:45-52 cached weight; bias may be NULL)
