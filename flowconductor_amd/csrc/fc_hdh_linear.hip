@@ -100,8 +100,8 @@ __global__ __launch_bounds__(256) void hdh_linear_kernel(const float* __restrict
       }
     }
   };
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock * R;
-  for (int64_t base = ((int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * R; base < n; base += stride) {
+  const int64_t stride = wave_unit_stride() * R;
+  for (int64_t base = wave_first_unit() * R; base < n; base += stride) {
     Row<E> r[R];
 #pragma unroll
     for (int j = 0; j < R; ++j) {
@@ -184,8 +184,8 @@ __global__ __launch_bounds__(256) void hdh_linear_backward_kernel(
     }
   };
   auto nothing = [](int, float) {};
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  const int64_t row0 = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  const int64_t stride = wave_unit_stride();
+  const int64_t row0 = wave_first_unit();
   for (int hi = positions; hi > 0; hi -= chunk) {      // positions [lo, hi), the chunk nearest the output first
     const int lo = hi - chunk > 0 ? hi - chunk : 0;
     const bool first = hi == positions, last = lo == 0;
@@ -257,40 +257,25 @@ __global__ __launch_bounds__(256) void hdh_linear_backward_kernel(
   }
 }
 
-inline int hdh_elems_for(int d) { return d <= 64 ? 1 : d <= 128 ? 2 : d <= 256 ? 4 : 8; }
-
-inline unsigned hdh_grid(int64_t units, int64_t cap) {
-  int64_t g = (units + kWavesPerBlock - 1) / kWavesPerBlock;
-  if (g > cap) g = cap;
-  return (unsigned)(g < 1 ? 1 : g);
-}
-
 }  // namespace fc
-
-#define FC_HDH_DISPATCH(D, CALL)                  \
-  switch (fc::hdh_elems_for(D)) {                 \
-    case 1: { constexpr int E = 1; CALL; break; } \
-    case 2: { constexpr int E = 2; CALL; break; } \
-    case 4: { constexpr int E = 4; CALL; break; } \
-    default: { constexpr int E = 8; CALL; break; } \
-  }
 
 extern "C" int fc_hdh_linear(const float* x, float* y, const float* q_a, const float* q_b, const float* scale,
                              const float* pre, const float* post, int64_t n, int32_t d, int32_t ka, int32_t kb,
                              int32_t reverse_a, int32_t reverse_b, void* stream) {
-  if (n < 0 || d <= 0 || d > 512 || ka < 0 || kb < 0 || ka + kb > fc::kHdhMaxReflections) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures || ka < 0 || kb < 0 || ka + kb > fc::kHdhMaxReflections)
+    return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x || !y || !scale || (!q_a && ka > 0) || (!q_b && kb > 0)) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int w = 64 * fc::hdh_elems_for(d), table = (ka + kb + 3) & ~3;
+  const int w = 64 * fc::elems_for(d), table = (ka + kb + 3) & ~3;
   const size_t staged = sizeof(float) * ((size_t)table + (size_t)(ka + kb) * w);
   const bool stage = staged <= (size_t)fc::kHdhLdsBudget;
   const size_t lds = stage ? staged : sizeof(float) * table;
   // two rows per wave where the registers are few (E <= 2)
 #define FC_HDH_FWD(RV, STAGE)                                                                                            \
-  hipLaunchKernelGGL((fc::hdh_linear_kernel<E, RV, STAGE>), dim3(fc::hdh_grid((n + RV - 1) / RV, 256 * 8)), dim3(256), lds, s, \
-                     x, y, q_a, q_b, scale, pre, post, n, d, ka, kb, reverse_a, reverse_b)
-  FC_HDH_DISPATCH(d, {
+  hipLaunchKernelGGL((fc::hdh_linear_kernel<E, RV, STAGE>), dim3(fc::row_grid((n + RV - 1) / RV, fc::kStreamGridCap)),    \
+                     dim3(256), lds, s, x, y, q_a, q_b, scale, pre, post, n, d, ka, kb, reverse_a, reverse_b)
+  FC_ROW_DISPATCH(d, {
     constexpr int RV = E <= 2 ? 2 : 1;
     if (stage) FC_HDH_FWD(RV, true);
     else FC_HDH_FWD(RV, false);
@@ -304,22 +289,23 @@ extern "C" int fc_hdh_linear_backward(const float* y, const float* grad_y, const
                                       float* grad_q_b, float* grad_scale, float* grad_pre, float* grad_post, int64_t n,
                                       int32_t d, int32_t ka, int32_t kb, int32_t reverse_a, int32_t reverse_b,
                                       void* stream) {
-  if (n < 0 || d <= 0 || d > 512 || ka < 0 || kb < 0 || ka + kb > fc::kHdhMaxReflections) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures || ka < 0 || kb < 0 || ka + kb > fc::kHdhMaxReflections)
+    return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!y || !grad_y || !scale || !grad_x || !grad_scale || (ka > 0 && (!q_a || !grad_q_a)) || (kb > 0 && (!q_b || !grad_q_b)))
     return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int w = 64 * fc::hdh_elems_for(d), table = (ka + kb + 3) & ~3;
+  const int w = 64 * fc::elems_for(d), table = (ka + kb + 3) & ~3;
   const size_t rows_all = sizeof(float) * ((size_t)table + (size_t)(ka + kb + 3) * w);      // every position + gpost + gpre
   const size_t rows_staged = rows_all + sizeof(float) * (size_t)(ka + kb) * w;
   const size_t rows_chunk = sizeof(float) * ((size_t)table + (size_t)(fc::kHdhChunk + 2) * w);
   const int mode = rows_staged <= (size_t)fc::kHdhLdsBudget ? 0 : rows_all <= (size_t)fc::kHdhLdsBudget ? 1 : 2;
   const size_t lds = mode == 0 ? rows_staged : mode == 1 ? rows_all : rows_chunk;
 #define FC_HDH_BWD(MODE)                                                                                                  \
-  hipLaunchKernelGGL((fc::hdh_linear_backward_kernel<E, MODE>), dim3(fc::hdh_grid(n, 256 * 4)), dim3(256), lds, s, y, grad_y, \
-                     q_a, q_b, scale, post, grad_x, grad_q_a, grad_q_b, grad_scale, grad_pre, grad_post, n, d, ka, kb,    \
-                     reverse_a, reverse_b)
-  FC_HDH_DISPATCH(d, {
+  hipLaunchKernelGGL((fc::hdh_linear_backward_kernel<E, MODE>), dim3(fc::row_grid(n, fc::kReduceGridCap)), dim3(256), lds, \
+                     s, y, grad_y, q_a, q_b, scale, post, grad_x, grad_q_a, grad_q_b, grad_scale, grad_pre, grad_post, n, \
+                     d, ka, kb, reverse_a, reverse_b)
+  FC_ROW_DISPATCH(d, {
     if (mode == 0) FC_HDH_BWD(0);
     else if (mode == 1) FC_HDH_BWD(1);
     else FC_HDH_BWD(2);

@@ -60,8 +60,8 @@ __global__ __launch_bounds__(256) void radial_kernel(const float* __restrict__ x
   const int lane = threadIdx.x & 63;
   Row<E> zv;
   load_row<E>(zv, z0, d, lane);
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     Row<E> r, dz;
     load_row<E>(r, x + row * d, d, lane);
     float s = 0.f;
@@ -97,8 +97,8 @@ __global__ __launch_bounds__(256) void radial_rows4_kernel(const float* __restri
   float4 zv = zero4;
   if (live) zv = reinterpret_cast<const float4*>(z0)[sub];
   const int64_t groups = (n + kRows - 1) / kRows;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  int64_t grp = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  const int64_t stride = wave_unit_stride();
+  int64_t grp = wave_first_unit();
   auto fetch = [&](int64_t g) {
     const int64_t row = g * kRows + rw;
     float4 v = zero4;
@@ -132,8 +132,8 @@ __global__ __launch_bounds__(256) void radial_narrow_kernel(const float* __restr
   const float a = a_ptr[0], b = b_ptr[0];
   const int lane = threadIdx.x & 63, j = lane & 15;
   const float zv = j < d ? z0[j] : 0.f;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock * 4;
-  for (int64_t base = ((int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * 4; base < n; base += stride) {
+  const int64_t stride = wave_unit_stride() * 4;
+  for (int64_t base = wave_first_unit() * 4; base < n; base += stride) {
     const int64_t row = base + (lane >> 4);
     const bool live = row < n && j < d;
     const float v = live ? x[row * d + j] : 0.f;
@@ -162,8 +162,8 @@ __global__ __launch_bounds__(256) void unit_vector_kernel(const float* __restric
   const int lane = threadIdx.x & 63;
   const int d_in = inverse ? d + 1 : d, d_out = inverse ? d : d + 1;
   bool outside = false;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     Row<E> r;
     load_row<E>(r, x + row * d_in, d_in, lane);
     float s = dot_rows<E>(r, r);
@@ -229,8 +229,8 @@ __global__ __launch_bounds__(256) void unit_vector_pieces_kernel(const float* __
   const bool last_apart = 4 * L <= d;
   bool outside = false;
   const int64_t groups = (n + kRows - 1) / kRows;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t grp = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); grp < groups; grp += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t grp = wave_first_unit(); grp < groups; grp += stride) {
     const int64_t row = grp * kRows + rw;
     const bool live = row < n;
     const int64_t rr = live ? row : n - 1;
@@ -269,8 +269,8 @@ __global__ __launch_bounds__(256) void unit_vector_narrow_kernel(const float* __
   const int lane = threadIdx.x & 63, j = lane & 15;
   const int d_in = inverse ? d + 1 : d, d_out = inverse ? d : d + 1;
   bool outside = false;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock * 4;
-  for (int64_t base = ((int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * 4; base < n; base += stride) {
+  const int64_t stride = wave_unit_stride() * 4;
+  for (int64_t base = wave_first_unit() * 4; base < n; base += stride) {
     const int64_t row = base + (lane >> 4);
     const bool live = row < n;
     float v = (live && j < d_in) ? x[row * d_in + j] : 0.f;
@@ -290,76 +290,42 @@ __global__ __launch_bounds__(256) void unit_vector_narrow_kernel(const float* __
   if (outside && err) atomicOr(err, FC_ERR_OUTSIDE_DOMAIN);
 }
 
-inline unsigned rownorm_grid(int64_t n) {
-  int64_t g = (n + kWavesPerBlock - 1) / kWavesPerBlock;
-  const int64_t cap = 256 * 8;
-  if (g > cap) g = cap;
-  return (unsigned)(g < 1 ? 1 : g);
-}
-
-inline int lanes_for(int pieces) {
-  int lanes = 1;
-  while (lanes < pieces) lanes <<= 1;
-  return lanes;
-}
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 }  // namespace fc
-
-#define FC_RN_DISPATCH(D, CALL)                   \
-  switch ((D) <= 64 ? 1 : (D) <= 128 ? 2 : (D) <= 256 ? 4 : 8) { \
-    case 1: { constexpr int E = 1; CALL; break; } \
-    case 2: { constexpr int E = 2; CALL; break; } \
-    case 4: { constexpr int E = 4; CALL; break; } \
-    default: { constexpr int E = 8; CALL; break; } \
-  }
-
-#define FC_RN_LANES(LANES, CALL)                    \
-  switch (LANES) {                                  \
-    case 1: { constexpr int L = 1; CALL; break; }   \
-    case 2: { constexpr int L = 2; CALL; break; }   \
-    case 4: { constexpr int L = 4; CALL; break; }   \
-    case 8: { constexpr int L = 8; CALL; break; }   \
-    case 16: { constexpr int L = 16; CALL; break; } \
-    case 32: { constexpr int L = 32; CALL; break; } \
-    default: { constexpr int L = 64; CALL; break; } \
-  }
 
 extern "C" int fc_radial(const float* x, float* y, float* logabsdet, const float* z0, const float* a, const float* b,
                          int64_t n, int32_t d, int32_t inverse, void* stream) {
-  if (n < 0 || d <= 0 || d > 512) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x || !y || !z0 || !a || !b) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (d % 4 == 0 && d <= 256 && fc::aligned16(x) && fc::aligned16(y) && fc::aligned16(z0)) {
     const int lanes = fc::lanes_for(d / 4);
     const int rows = 64 / lanes;
-    const unsigned grid = fc::rownorm_grid((n + rows - 1) / rows);
-    FC_RN_LANES(lanes, hipLaunchKernelGGL(fc::radial_rows4_kernel<L>, dim3(grid), dim3(256), 0, s, x, y, logabsdet, z0, a,
+    const unsigned grid = fc::row_grid((n + rows - 1) / rows, fc::kStreamGridCap);
+    FC_ROW_LANES(lanes, hipLaunchKernelGGL(fc::radial_rows4_kernel<L>, dim3(grid), dim3(256), 0, s, x, y, logabsdet, z0, a,
                                           b, n, d, inverse));
     return hipGetLastError();
   }
   if (d <= 16) {
-    hipLaunchKernelGGL(fc::radial_narrow_kernel, dim3(fc::rownorm_grid((n + 3) / 4)), dim3(256), 0, s, x, y, logabsdet, z0,
-                       a, b, n, d, inverse);
+    hipLaunchKernelGGL(fc::radial_narrow_kernel, dim3(fc::row_grid((n + 3) / 4, fc::kStreamGridCap)), dim3(256), 0, s, x, y,
+                       logabsdet, z0, a, b, n, d, inverse);
     return hipGetLastError();
   }
-  FC_RN_DISPATCH(d, hipLaunchKernelGGL(fc::radial_kernel<E>, dim3(fc::rownorm_grid(n)), dim3(256), 0, s, x, y, logabsdet,
-                                       z0, a, b, n, d, inverse));
+  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::radial_kernel<E>, dim3(fc::row_grid(n, fc::kStreamGridCap)), dim3(256), 0, s, x, y,
+                                        logabsdet, z0, a, b, n, d, inverse));
   return hipGetLastError();
 }
 
 extern "C" int fc_unit_vector(const float* x, float* y, float* logabsdet, uint32_t* err, int64_t n, int32_t d,
                               int32_t inverse, void* stream) {
-  if (n < 0 || d <= 0 || d + 1 > 512) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d + 1 > fc::kMaxRowFeatures) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x || !y) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int wide = d + 1;
   if (wide <= 16) {
-    hipLaunchKernelGGL(fc::unit_vector_narrow_kernel, dim3(fc::rownorm_grid((n + 3) / 4)), dim3(256), 0, s, x, y, logabsdet,
-                       err, n, d, inverse);
+    hipLaunchKernelGGL(fc::unit_vector_narrow_kernel, dim3(fc::row_grid((n + 3) / 4, fc::kStreamGridCap)), dim3(256), 0, s, x,
+                       y, logabsdet, err, n, d, inverse);
     return hipGetLastError();
   }
   // the side that moves as 16-byte pieces: R^d rows when d % 4 == 0, sphere rows when (d + 1) % 4 == 0
@@ -369,17 +335,17 @@ extern "C" int fc_unit_vector(const float* x, float* y, float* logabsdet, uint32
   if ((vec_d && d <= 256) || (vec_s && wide <= 256)) {
     const int lanes = fc::lanes_for(vec_d ? d / 4 : wide / 4);
     const int rows = 64 / lanes;
-    const unsigned grid = fc::rownorm_grid((n + rows - 1) / rows);
+    const unsigned grid = fc::row_grid((n + rows - 1) / rows, fc::kStreamGridCap);
     if (vec_d) {
-      FC_RN_LANES(lanes, hipLaunchKernelGGL((fc::unit_vector_pieces_kernel<L, true>), dim3(grid), dim3(256), 0, s, x, y,
+      FC_ROW_LANES(lanes, hipLaunchKernelGGL((fc::unit_vector_pieces_kernel<L, true>), dim3(grid), dim3(256), 0, s, x, y,
                                             logabsdet, err, n, d, inverse));
     } else {
-      FC_RN_LANES(lanes, hipLaunchKernelGGL((fc::unit_vector_pieces_kernel<L, false>), dim3(grid), dim3(256), 0, s, x, y,
+      FC_ROW_LANES(lanes, hipLaunchKernelGGL((fc::unit_vector_pieces_kernel<L, false>), dim3(grid), dim3(256), 0, s, x, y,
                                             logabsdet, err, n, d, inverse));
     }
     return hipGetLastError();
   }
-  FC_RN_DISPATCH(wide, hipLaunchKernelGGL(fc::unit_vector_kernel<E>, dim3(fc::rownorm_grid(n)), dim3(256), 0, s, x, y,
-                                          logabsdet, err, n, d, inverse));
+  FC_ROW_DISPATCH(wide, hipLaunchKernelGGL(fc::unit_vector_kernel<E>, dim3(fc::row_grid(n, fc::kStreamGridCap)), dim3(256), 0,
+                                           s, x, y, logabsdet, err, n, d, inverse));
   return hipGetLastError();
 }

@@ -39,8 +39,8 @@ __global__ __launch_bounds__(256) void radial_backward_kernel(const float* __res
 #pragma unroll
   for (int e = 0; e < E; ++e) gzv.v[e] = 0.f;
   float gav = 0.f, gbv = 0.f;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     Row<E> dz, g;
     load_row<E>(dz, x + row * d, d, lane);
     load_row<E>(g, gy + row * d, d, lane);
@@ -83,8 +83,8 @@ __global__ __launch_bounds__(256) void unit_vector_backward_kernel(const float* 
                                                                    int64_t n, int d, int inverse) {
   const int lane = threadIdx.x & 63;
   const int d_in = inverse ? d + 1 : d, d_out = inverse ? d : d + 1;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     Row<E> v, g;
     load_row<E>(v, in + row * d_in, d_in, lane);
     load_row<E>(g, gout + row * d_out, d_out, lane);
@@ -113,42 +113,27 @@ __global__ __launch_bounds__(256) void unit_vector_backward_kernel(const float* 
   }
 }
 
-inline unsigned rownorm_bwd_grid(int64_t n) {
-  int64_t g = (n + kWavesPerBlock - 1) / kWavesPerBlock;
-  const int64_t cap = 256 * 4;
-  if (g > cap) g = cap;
-  return (unsigned)(g < 1 ? 1 : g);
-}
-
 }  // namespace fc
-
-#define FC_RN_DISPATCH_B(D, CALL)                 \
-  switch ((D) <= 64 ? 1 : (D) <= 128 ? 2 : (D) <= 256 ? 4 : 8) { \
-    case 1: { constexpr int E = 1; CALL; break; } \
-    case 2: { constexpr int E = 2; CALL; break; } \
-    case 4: { constexpr int E = 4; CALL; break; } \
-    default: { constexpr int E = 8; CALL; break; } \
-  }
 
 extern "C" int fc_radial_backward(const float* x, const float* grad_y, const float* grad_logabsdet, const float* z0,
                                   const float* a, const float* b, float* grad_x, float* grad_z0, float* grad_a,
                                   float* grad_b, int64_t n, int32_t d, void* stream) {
-  if (n < 0 || d <= 0 || d > 512) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x || !grad_y || !z0 || !a || !b || !grad_x || !grad_z0 || !grad_a || !grad_b) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  FC_RN_DISPATCH_B(d, hipLaunchKernelGGL(fc::radial_backward_kernel<E>, dim3(fc::rownorm_bwd_grid(n)), dim3(256), 0, s, x,
-                                         grad_y, grad_logabsdet, z0, a, b, grad_x, grad_z0, grad_a, grad_b, n, d));
+  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::radial_backward_kernel<E>, dim3(fc::row_grid(n, fc::kReduceGridCap)), dim3(256), 0,
+                                        s, x, grad_y, grad_logabsdet, z0, a, b, grad_x, grad_z0, grad_a, grad_b, n, d));
   return hipGetLastError();
 }
 
 extern "C" int fc_unit_vector_backward(const float* x_or_y, const float* grad_out, const float* grad_logabsdet,
                                        float* grad_in, int64_t n, int32_t d, int32_t inverse, void* stream) {
-  if (n < 0 || d <= 0 || d + 1 > 512) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d + 1 > fc::kMaxRowFeatures) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x_or_y || !grad_out || !grad_in) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  FC_RN_DISPATCH_B(d + 1, hipLaunchKernelGGL(fc::unit_vector_backward_kernel<E>, dim3(fc::rownorm_bwd_grid(n)), dim3(256), 0,
-                                             s, x_or_y, grad_out, grad_logabsdet, grad_in, n, d, inverse));
+  FC_ROW_DISPATCH(d + 1, hipLaunchKernelGGL(fc::unit_vector_backward_kernel<E>, dim3(fc::row_grid(n, fc::kReduceGridCap)),
+                                            dim3(256), 0, s, x_or_y, grad_out, grad_logabsdet, grad_in, n, d, inverse));
   return hipGetLastError();
 }

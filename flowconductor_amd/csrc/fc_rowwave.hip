@@ -158,8 +158,8 @@ __global__ __launch_bounds__(256) void householder_kernel(const float* __restric
                                                           const float* __restrict__ q, int64_t n, int d,
                                                           int k_count, int per_sample, int reverse) {
   const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     Row<E> r;
     load_row<E>(r, x + row * d, d, lane);
     const float* qr = per_sample ? q + row * (int64_t)k_count * d : q;
@@ -175,8 +175,8 @@ __global__ __launch_bounds__(256) void householder_narrow_kernel(const float* __
                                                                  const float* __restrict__ q, int64_t n, int d,
                                                                  int k_count, int per_sample, int reverse) {
   const int lane = threadIdx.x & 63, j = lane & 15;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock * 4;
-  for (int64_t base = ((int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * 4; base < n; base += stride) {
+  const int64_t stride = wave_unit_stride() * 4;
+  for (int64_t base = wave_first_unit() * 4; base < n; base += stride) {
     const int64_t row = base + (lane >> 4);
     const bool live = row < n && j < d;
     const int64_t rr = row < n ? row : n - 1;
@@ -209,8 +209,8 @@ __global__ __launch_bounds__(256) void planar_kernel(const float* __restrict__ x
   Row<E> wv, uv;
   load_row<E>(wv, w, d, lane);
   load_row<E>(uv, u_hat, d, lane);
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     Row<E> r;
     load_row<E>(r, x + row * d, d, lane);
     if (per_sample) {
@@ -252,8 +252,8 @@ __global__ __launch_bounds__(256) void planar_rows4_kernel(const float* __restri
   float4 wv = (live && !per_sample) ? reinterpret_cast<const float4*>(w)[sub] : zero4;
   float4 uv = (live && !per_sample) ? reinterpret_cast<const float4*>(u_hat)[sub] : zero4;
   const int64_t groups = (n + kRows - 1) / kRows;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  int64_t grp = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  const int64_t stride = wave_unit_stride();
+  int64_t grp = wave_first_unit();
   auto fetch = [&](int64_t g, const float* src) {
     const int64_t row = g * kRows + rw;
     return (live && row < n) ? reinterpret_cast<const float4*>(src + row * d)[sub] : zero4;
@@ -300,8 +300,8 @@ __global__ __launch_bounds__(256) void linear_kernel(const float* __restrict__ x
 #pragma unroll
     for (int e = 0; e < E; ++e) bv.v[e] = 0.f;
   }
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     Row<E> r, t;
     load_row<E>(r, x + row * d, d, lane);
     if (mode == 0) {
@@ -364,8 +364,8 @@ __global__ __launch_bounds__(256) void sylvester_kernel(const float* __restrict_
                                                         int64_t n, int d, int m) {
   constexpr bool per_sample = kPS;
   const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     Row<E> z, t, a;
     load_row<E>(z, x + row * d, d, lane);
     const float* qr = per_sample ? q + row * (int64_t)m * d : q;
@@ -409,8 +409,8 @@ __global__ __launch_bounds__(256) void linear_per_sample_kernel(const float* __r
                                                                 float* __restrict__ lad, const float* __restrict__ m,
                                                                 int64_t n, int d, int mode, float sp, float eps) {
   const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     const float* mr = m + row * (int64_t)d * d;
     Row<E> v, out;
     load_row<E>(v, x + row * d, d, lane);
@@ -556,8 +556,8 @@ __global__ __launch_bounds__(256) void linear_per_sample_narrow_kernel(const flo
                                                                        const float* __restrict__ m, int64_t n, int d,
                                                                        int mode, float sp, float eps) {
   const int lane = threadIdx.x & 63, j = lane & 15, rowbase = lane & 48;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock * 4;
-  for (int64_t base = ((int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * 4; base < n; base += stride) {
+  const int64_t stride = wave_unit_stride() * 4;
+  for (int64_t base = wave_first_unit() * 4; base < n; base += stride) {
     const int64_t row = base + (lane >> 4);
     const int64_t rr = row < n ? row : n - 1;
     const bool live = row < n && j < d;
@@ -612,109 +612,85 @@ __global__ __launch_bounds__(256) void linear_per_sample_narrow_kernel(const flo
   }
 }
 
-inline unsigned row_grid(int64_t n) {
-  int64_t g = (n + kWavesPerBlock - 1) / kWavesPerBlock;
-  const int64_t cap = 256 * 8;
-  if (g > cap) g = cap;
-  return (unsigned)(g < 1 ? 1 : g);
-}
-
-inline int elems_for(int d) { return d <= 64 ? 1 : d <= 128 ? 2 : d <= 256 ? 4 : 8; }
-
 }  // namespace fc
-
-#define FC_ROW_DISPATCH(D, CALL)                  \
-  switch (fc::elems_for(D)) {                     \
-    case 1: { constexpr int E = 1; CALL; break; } \
-    case 2: { constexpr int E = 2; CALL; break; } \
-    case 4: { constexpr int E = 4; CALL; break; } \
-    default: { constexpr int E = 8; CALL; break; } \
-  }
 
 extern "C" int fc_householder(const float* x, float* y, const float* q, int64_t n, int32_t d,
                               int32_t num_transforms, int32_t per_sample, int32_t reverse, void* stream) {
-  if (n < 0 || d <= 0 || d > 512 || num_transforms < 0) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures || num_transforms < 0) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x || !y || (!q && num_transforms > 0)) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (d <= 16) {
-    hipLaunchKernelGGL(fc::householder_narrow_kernel, dim3(fc::row_grid((n + 3) / 4)), dim3(256), 0, s, x, y, q, n, d,
-                       num_transforms, per_sample, reverse);
+    hipLaunchKernelGGL(fc::householder_narrow_kernel, dim3(fc::row_grid((n + 3) / 4, fc::kStreamGridCap)), dim3(256), 0, s, x,
+                       y, q, n, d, num_transforms, per_sample, reverse);
     return hipGetLastError();
   }
-  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::householder_kernel<E>, dim3(fc::row_grid(n)), dim3(256), 0, s, x, y,
-                                        q, n, d, num_transforms, per_sample, reverse));
+  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::householder_kernel<E>, dim3(fc::row_grid(n, fc::kStreamGridCap)), dim3(256), 0, s,
+                                        x, y, q, n, d, num_transforms, per_sample, reverse));
   return hipGetLastError();
 }
 
 extern "C" int fc_planar(const float* x, float* y, float* logabsdet, const float* w, const float* u_hat,
                          const float* b, int64_t n, int32_t d, int32_t per_sample, void* stream) {
-  if (n < 0 || d <= 0 || d > 512) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x || !y || !w || !u_hat || !b) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (d % 4 == 0 && d <= 256 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w | (uintptr_t)u_hat) & 15u) == 0) {
-    int lanes = 1;
-    while (lanes < d / 4) lanes <<= 1;
+  if (d % 4 == 0 && d <= 256 && fc::aligned16(x) && fc::aligned16(y) && fc::aligned16(w) && fc::aligned16(u_hat)) {
+    const int lanes = fc::lanes_for(d / 4);
     const int rows = 64 / lanes;
-    const unsigned grid = fc::row_grid((n + rows - 1) / rows);
-#define FC_PLANAR4(LV)                                                                                          \
-  case LV:                                                                                                      \
-    hipLaunchKernelGGL(fc::planar_rows4_kernel<LV>, dim3(grid), dim3(256), 0, s, x, y, logabsdet, w, u_hat, b, n, d, \
-                       per_sample);                                                                             \
-    break;
-    switch (lanes) {
-      FC_PLANAR4(1) FC_PLANAR4(2) FC_PLANAR4(4) FC_PLANAR4(8) FC_PLANAR4(16) FC_PLANAR4(32) FC_PLANAR4(64)
-    }
-#undef FC_PLANAR4
+    const unsigned grid = fc::row_grid((n + rows - 1) / rows, fc::kStreamGridCap);
+    FC_ROW_LANES(lanes, hipLaunchKernelGGL(fc::planar_rows4_kernel<L>, dim3(grid), dim3(256), 0, s, x, y, logabsdet, w, u_hat,
+                                           b, n, d, per_sample));
     return hipGetLastError();
   }
-  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::planar_kernel<E>, dim3(fc::row_grid(n)), dim3(256), 0, s, x, y,
+  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::planar_kernel<E>, dim3(fc::row_grid(n, fc::kStreamGridCap)), dim3(256), 0, s, x, y,
                                         logabsdet, w, u_hat, b, n, d, per_sample));
   return hipGetLastError();
 }
 
 extern "C" int fc_linear(const float* x, float* y, const float* a_t, const float* b_t, const float* bias,
                          int64_t n, int32_t d, int32_t mode, void* stream) {
-  if (n < 0 || d <= 0 || d > 512 || mode < 0 || mode > 3) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures || mode < 0 || mode > 3) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x || !y || !a_t || ((mode == 1 || mode == 2) && !b_t)) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::linear_kernel<E>, dim3(fc::row_grid(n)), dim3(256), 0, s, x, y, a_t,
-                                        b_t, bias, n, d, mode));
+  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::linear_kernel<E>, dim3(fc::row_grid(n, fc::kStreamGridCap)), dim3(256), 0, s, x, y,
+                                        a_t, b_t, bias, n, d, mode));
   return hipGetLastError();
 }
 
 extern "C" int fc_linear_per_sample(const float* x, float* y, float* logabsdet, const float* m, int64_t n,
                                     int32_t d, int32_t mode, float offdiag_scale, float eps, void* stream) {
-  if (n < 0 || d <= 0 || d > 512 || mode < 0 || mode > 3) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures || mode < 0 || mode > 3) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x || !y || !m) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (d <= 16) {
-    hipLaunchKernelGGL(fc::linear_per_sample_narrow_kernel, dim3(fc::row_grid((n + 3) / 4)), dim3(256), 0, s, x, y,
-                       logabsdet, m, n, d, mode, offdiag_scale, eps);
+    hipLaunchKernelGGL(fc::linear_per_sample_narrow_kernel, dim3(fc::row_grid((n + 3) / 4, fc::kStreamGridCap)), dim3(256), 0,
+                       s, x, y, logabsdet, m, n, d, mode, offdiag_scale, eps);
     return hipGetLastError();
   }
-  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::linear_per_sample_kernel<E>, dim3(fc::row_grid(n)), dim3(256), 0, s, x,
-                                        y, logabsdet, m, n, d, mode, offdiag_scale, eps));
+  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::linear_per_sample_kernel<E>, dim3(fc::row_grid(n, fc::kStreamGridCap)), dim3(256),
+                                        0, s, x, y, logabsdet, m, n, d, mode, offdiag_scale, eps));
   return hipGetLastError();
 }
 
 extern "C" int fc_sylvester(const float* x, float* y, float* logabsdet, const float* q, const float* r1_t,
                             const float* r2_t, const float* bias, const float* r_diag_prod, int64_t n,
                             int32_t d, int32_t num_householder, int32_t per_sample, void* stream) {
-  if (n < 0 || d <= 0 || d > 512 || num_householder < 0) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures || num_householder < 0) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x || !y || !r1_t || !r2_t || !bias || !r_diag_prod || (!q && num_householder > 0))
     return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (per_sample) {
-    FC_ROW_DISPATCH(d, hipLaunchKernelGGL((fc::sylvester_kernel<E, true>), dim3(fc::row_grid(n)), dim3(256), 0, s, x,
-                                          y, logabsdet, q, r1_t, r2_t, bias, r_diag_prod, n, d, num_householder));
+    FC_ROW_DISPATCH(d, hipLaunchKernelGGL((fc::sylvester_kernel<E, true>), dim3(fc::row_grid(n, fc::kStreamGridCap)), dim3(256),
+                                          0, s, x, y, logabsdet, q, r1_t, r2_t, bias, r_diag_prod, n, d, num_householder));
   } else {
-    FC_ROW_DISPATCH(d, hipLaunchKernelGGL((fc::sylvester_kernel<E, false>), dim3(fc::row_grid(n)), dim3(256), 0, s, x,
-                                          y, logabsdet, q, r1_t, r2_t, bias, r_diag_prod, n, d, num_householder));
+    FC_ROW_DISPATCH(d, hipLaunchKernelGGL((fc::sylvester_kernel<E, false>), dim3(fc::row_grid(n, fc::kStreamGridCap)),
+                                          dim3(256), 0, s, x, y, logabsdet, q, r1_t, r2_t, bias, r_diag_prod, n, d,
+                                          num_householder));
   }
   return hipGetLastError();
 }

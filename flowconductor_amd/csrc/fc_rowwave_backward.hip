@@ -37,27 +37,19 @@ __global__ __launch_bounds__(256) void planar_backward_kernel(const float* __res
   for (int e = 0; e < E; ++e) gwv.v[e] = guv.v[e] = 0.f;
   float gbv = 0.f;
   const float uw = dot_rows<E>(uv, wv);
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     Row<E> r, g;
     load_row<E>(r, x + row * d, d, lane);
     load_row<E>(g, gy + row * d, d, lane);
-    const float glr = gl ? gl[row] : 0.f;
-    const float a = dot_rows<E>(r, wv) + b;
-    const float t = tanhf(a);
-    const float dt = 1.f - t * t;
-    const float psi = 1.f + dt * uw;
-    const float dl = glr * (psi >= 0.f ? 1.f : -1.f) / (1e-7f + fabsf(psi));      // d lad / d psi times gl
-    const float g_t = dot_rows<E>(g, uv) - dl * (2.f * t * uw);
-    const float g_a = g_t * dt;
-    const float c = dl * dt;
+    const Row<E> gyv = g;
+    const PlanarBackward k = planar_backward_row<E>(r, g, wv, uv, b, gl ? gl[row] : 0.f, uw);
 #pragma unroll
     for (int e = 0; e < E; ++e) {
-      gwv.v[e] += g_a * r.v[e] + c * uv.v[e];
-      guv.v[e] += t * g.v[e] + c * wv.v[e];
-      g.v[e] = g.v[e] + g_a * wv.v[e];
+      gwv.v[e] += k.gw(r.v[e], uv.v[e]);
+      guv.v[e] += k.gu(gyv.v[e], wv.v[e]);
     }
-    gbv += g_a;
+    gbv += k.g_a;
     store_row<E>(g, gx + row * d, d, lane);
   }
 #pragma unroll
@@ -79,8 +71,8 @@ __global__ __launch_bounds__(256) void householder_backward_kernel(const float* 
                                                                    float* __restrict__ gq, int64_t n, int d, int k_count,
                                                                    int reverse) {
   const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  const int64_t row0 = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  const int64_t stride = wave_unit_stride();
+  const int64_t row0 = wave_first_unit();
   // position p in application order (0 = first reflection applied) -> index into q
   auto qidx = [&](int p) { return reverse ? k_count - 1 - p : p; };
   for (int hi = k_count; hi > 0; hi -= KQ) {        // reflections [lo, hi) in application order, last chunk first
@@ -155,8 +147,8 @@ __global__ __launch_bounds__(256) void sylvester_mid_backward_kernel(const float
   load_row<E>(rdv, rd, d, lane);
 #pragma unroll
   for (int e = 0; e < E; ++e) sb.v[e] = sr.v[e] = 0.f;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     Row<E> p, gv;
     load_row<E>(p, pre + row * d, d, lane);
     load_row<E>(gv, g + row * d, d, lane);
@@ -183,55 +175,41 @@ __global__ __launch_bounds__(256) void sylvester_mid_backward_kernel(const float
   }
 }
 
-inline unsigned bwd_row_grid(int64_t n) {
-  int64_t g = (n + kWavesPerBlock - 1) / kWavesPerBlock;
-  const int64_t cap = 256 * 4;
-  if (g > cap) g = cap;
-  return (unsigned)(g < 1 ? 1 : g);
-}
-
 }  // namespace fc
-
-#define FC_ROW_DISPATCH_B(D, CALL)                \
-  switch ((D) <= 64 ? 1 : (D) <= 128 ? 2 : (D) <= 256 ? 4 : 8) { \
-    case 1: { constexpr int E = 1; CALL; break; } \
-    case 2: { constexpr int E = 2; CALL; break; } \
-    case 4: { constexpr int E = 4; CALL; break; } \
-    default: { constexpr int E = 8; CALL; break; } \
-  }
 
 extern "C" int fc_planar_backward(const float* x, const float* grad_y, const float* grad_logabsdet, const float* w,
                                   const float* u_hat, const float* b, float* grad_x, float* grad_w, float* grad_u_hat,
                                   float* grad_b, int64_t n, int32_t d, void* stream) {
-  if (n < 0 || d <= 0 || d > 512) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x || !grad_y || !w || !u_hat || !b || !grad_x || !grad_w || !grad_u_hat || !grad_b) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  FC_ROW_DISPATCH_B(d, hipLaunchKernelGGL(fc::planar_backward_kernel<E>, dim3(fc::bwd_row_grid(n)), dim3(256), 0, s, x,
-                                          grad_y, grad_logabsdet, w, u_hat, b, grad_x, grad_w, grad_u_hat, grad_b, n, d));
+  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::planar_backward_kernel<E>, dim3(fc::row_grid(n, fc::kReduceGridCap)), dim3(256), 0,
+                                        s, x, grad_y, grad_logabsdet, w, u_hat, b, grad_x, grad_w, grad_u_hat, grad_b, n, d));
   return hipGetLastError();
 }
 
 extern "C" int fc_householder_backward(const float* y, const float* grad_y, const float* q, float* grad_x, float* grad_q,
                                        int64_t n, int32_t d, int32_t num_transforms, int32_t reverse, void* stream) {
-  if (n < 0 || d <= 0 || d > 512 || num_transforms < 0) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures || num_transforms < 0) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!y || !grad_y || !grad_x || (num_transforms > 0 && (!q || !grad_q))) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (num_transforms == 0) return hipMemcpyAsync(grad_x, grad_y, sizeof(float) * n * d, hipMemcpyDeviceToDevice, s);
-  FC_ROW_DISPATCH_B(d, hipLaunchKernelGGL((fc::householder_backward_kernel<E, 8>), dim3(fc::bwd_row_grid(n)), dim3(256), 0,
-                                          s, y, grad_y, q, grad_x, grad_q, n, d, num_transforms, reverse));
+  FC_ROW_DISPATCH(d, hipLaunchKernelGGL((fc::householder_backward_kernel<E, 8>), dim3(fc::row_grid(n, fc::kReduceGridCap)),
+                                        dim3(256), 0, s, y, grad_y, q, grad_x, grad_q, n, d, num_transforms, reverse));
   return hipGetLastError();
 }
 
 extern "C" int fc_sylvester_mid_backward(const float* pre, float* grad_act_inout, const float* grad_logabsdet,
                                          const float* r_diag_prod, float* grad_bias, float* grad_r_diag_prod, int64_t n,
                                          int32_t d, void* stream) {
-  if (n < 0 || d <= 0 || d > 512) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!pre || !grad_act_inout || !r_diag_prod || !grad_bias || !grad_r_diag_prod) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  FC_ROW_DISPATCH_B(d, hipLaunchKernelGGL(fc::sylvester_mid_backward_kernel<E>, dim3(fc::bwd_row_grid(n)), dim3(256), 0, s,
-                                          pre, grad_act_inout, grad_logabsdet, r_diag_prod, grad_bias, grad_r_diag_prod, n, d));
+  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::sylvester_mid_backward_kernel<E>, dim3(fc::row_grid(n, fc::kReduceGridCap)),
+                                        dim3(256), 0, s, pre, grad_act_inout, grad_logabsdet, r_diag_prod, grad_bias,
+                                        grad_r_diag_prod, n, d));
   return hipGetLastError();
 }

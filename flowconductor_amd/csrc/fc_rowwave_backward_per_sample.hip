@@ -27,7 +27,8 @@
 // Householder (formulas: header of fc_rowwave_backward.hip): the walk back from the saved output with this row's q block;
 // gq is stored per row and reflection, so neither the register chunking over reflections nor the re-walk is needed.
 //
-// Planar: the formulas of planar_backward_kernel with this row's w, u_hat, b and u.w; gw, gu, gb stored per row.
+// Planar: planar_backward_row (fc_row.h), which planar_backward_kernel uses too, with this row's w, u_hat, b and u.w; gw, gu,
+// gb stored per row.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fc_math.h"
@@ -44,8 +45,8 @@ __global__ __launch_bounds__(256) void linear_ps_backward_kernel(const float* __
                                                                  float* __restrict__ gsp, int64_t n, int d, int mode,
                                                                  float sp, float eps) {
   const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     const float* mr = m + row * (int64_t)d * d;
     float* gr = gm + row * (int64_t)d * d;
     Row<E> x, g, out;
@@ -207,8 +208,8 @@ __global__ __launch_bounds__(256) void linear_ps_backward_narrow_kernel(const fl
                                                                         float* __restrict__ gm, float* __restrict__ gsp,
                                                                         int64_t n, int d, int mode, float sp, float eps) {
   const int lane = threadIdx.x & 63, j = lane & 15, rowbase = lane & 48;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock * 4;
-  for (int64_t base = ((int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * 4; base < n; base += stride) {
+  const int64_t stride = wave_unit_stride() * 4;
+  for (int64_t base = wave_first_unit() * 4; base < n; base += stride) {
     const int64_t row = base + (lane >> 4);
     const int64_t rr = row < n ? row : n - 1;
     const bool live = row < n && j < d;
@@ -291,8 +292,8 @@ __global__ __launch_bounds__(256) void householder_ps_backward_kernel(const floa
                                                                       float* __restrict__ gq, int64_t n, int d, int k_count,
                                                                       int reverse) {
   const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     const float* qr = q + row * (int64_t)k_count * d;
     float* gqr = gq + row * (int64_t)k_count * d;
     Row<E> v, g;
@@ -342,81 +343,57 @@ __global__ __launch_bounds__(256) void planar_ps_backward_kernel(const float* __
                                                                  float* __restrict__ gu, float* __restrict__ gb, int64_t n,
                                                                  int d) {
   const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); row < n; row += stride) {
+  const int64_t stride = wave_unit_stride();
+  for (int64_t row = wave_first_unit(); row < n; row += stride) {
     Row<E> r, g, wv, uv, gwv, guv;
     load_row<E>(r, x + row * d, d, lane);
     load_row<E>(g, gy + row * d, d, lane);
     load_row<E>(wv, w + row * d, d, lane);
     load_row<E>(uv, u_hat + row * d, d, lane);
-    const float glr = gl ? gl[row] : 0.f;
-    const float uw = dot_rows<E>(uv, wv);
-    const float a = dot_rows<E>(r, wv) + b[row];
-    const float t = tanhf(a);
-    const float dt = 1.f - t * t;
-    const float psi = 1.f + dt * uw;
-    const float dl = glr * (psi >= 0.f ? 1.f : -1.f) / (1e-7f + fabsf(psi));      // d lad / d psi times gl
-    const float g_t = dot_rows<E>(g, uv) - dl * (2.f * t * uw);
-    const float g_a = g_t * dt;
-    const float c = dl * dt;
+    const Row<E> gyv = g;
+    const PlanarBackward k = planar_backward_row<E>(r, g, wv, uv, b[row], gl ? gl[row] : 0.f, dot_rows<E>(uv, wv));
 #pragma unroll
     for (int e = 0; e < E; ++e) {
-      gwv.v[e] = g_a * r.v[e] + c * uv.v[e];
-      guv.v[e] = t * g.v[e] + c * wv.v[e];
-      g.v[e] = g.v[e] + g_a * wv.v[e];
+      gwv.v[e] = k.gw(r.v[e], uv.v[e]);
+      guv.v[e] = k.gu(gyv.v[e], wv.v[e]);
     }
     store_row<E>(g, gx + row * d, d, lane);
     store_row<E>(gwv, gw + row * d, d, lane);
     store_row<E>(guv, gu + row * d, d, lane);
-    if (lane == 0) gb[row] = g_a;
+    if (lane == 0) gb[row] = k.g_a;
   }
-}
-
-inline unsigned ps_row_grid(int64_t n) {
-  int64_t g = (n + kWavesPerBlock - 1) / kWavesPerBlock;
-  const int64_t cap = 256 * 8;
-  if (g > cap) g = cap;
-  return (unsigned)(g < 1 ? 1 : g);
 }
 
 }  // namespace fc
 
-#define FC_ROW_DISPATCH_PS(D, CALL)               \
-  switch ((D) <= 64 ? 1 : (D) <= 128 ? 2 : (D) <= 256 ? 4 : 8) { \
-    case 1: { constexpr int E = 1; CALL; break; } \
-    case 2: { constexpr int E = 2; CALL; break; } \
-    case 4: { constexpr int E = 4; CALL; break; } \
-    default: { constexpr int E = 8; CALL; break; } \
-  }
-
 extern "C" int fc_linear_per_sample_backward(const float* x_or_out, const float* grad_out, const float* grad_logabsdet,
                                              const float* m, float* grad_in, float* grad_m, float* grad_sp_rows, int64_t n,
                                              int32_t d, int32_t mode, float offdiag_scale, float eps, void* stream) {
-  if (n < 0 || d <= 0 || d > 512 || mode < 0 || mode > 3) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures || mode < 0 || mode > 3) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x_or_out || !grad_out || !m || !grad_in || !grad_m) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (d <= 16) {
-    hipLaunchKernelGGL(fc::linear_ps_backward_narrow_kernel, dim3(fc::ps_row_grid((n + 3) / 4)), dim3(256), 0, s, x_or_out,
-                       grad_out, grad_logabsdet, m, grad_in, grad_m, grad_sp_rows, n, d, mode, offdiag_scale, eps);
+    hipLaunchKernelGGL(fc::linear_ps_backward_narrow_kernel, dim3(fc::row_grid((n + 3) / 4, fc::kStreamGridCap)), dim3(256), 0,
+                       s, x_or_out, grad_out, grad_logabsdet, m, grad_in, grad_m, grad_sp_rows, n, d, mode, offdiag_scale, eps);
     return hipGetLastError();
   }
-  FC_ROW_DISPATCH_PS(d, hipLaunchKernelGGL(fc::linear_ps_backward_kernel<E>, dim3(fc::ps_row_grid(n)), dim3(256), 0, s,
-                                           x_or_out, grad_out, grad_logabsdet, m, grad_in, grad_m, grad_sp_rows, n, d, mode,
-                                           offdiag_scale, eps));
+  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::linear_ps_backward_kernel<E>, dim3(fc::row_grid(n, fc::kStreamGridCap)), dim3(256),
+                                        0, s, x_or_out, grad_out, grad_logabsdet, m, grad_in, grad_m, grad_sp_rows, n, d, mode,
+                                        offdiag_scale, eps));
   return hipGetLastError();
 }
 
 extern "C" int fc_householder_backward_per_sample(const float* y, const float* grad_y, const float* q, float* grad_x,
                                                   float* grad_q, int64_t n, int32_t d, int32_t num_transforms,
                                                   int32_t reverse, void* stream) {
-  if (n < 0 || d <= 0 || d > 512 || num_transforms < 0) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures || num_transforms < 0) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!y || !grad_y || !grad_x || (num_transforms > 0 && (!q || !grad_q))) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (num_transforms == 0) return hipMemcpyAsync(grad_x, grad_y, sizeof(float) * n * d, hipMemcpyDeviceToDevice, s);
-  FC_ROW_DISPATCH_PS(d, hipLaunchKernelGGL(fc::householder_ps_backward_kernel<E>, dim3(fc::ps_row_grid(n)), dim3(256), 0, s,
-                                           y, grad_y, q, grad_x, grad_q, n, d, num_transforms, reverse));
+  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::householder_ps_backward_kernel<E>, dim3(fc::row_grid(n, fc::kStreamGridCap)),
+                                        dim3(256), 0, s, y, grad_y, q, grad_x, grad_q, n, d, num_transforms, reverse));
   return hipGetLastError();
 }
 
@@ -424,11 +401,12 @@ extern "C" int fc_planar_backward_per_sample(const float* x, const float* grad_y
                                              const float* w, const float* u_hat, const float* b, float* grad_x,
                                              float* grad_w, float* grad_u_hat, float* grad_b, int64_t n, int32_t d,
                                              void* stream) {
-  if (n < 0 || d <= 0 || d > 512) return hipErrorInvalidValue;
+  if (n < 0 || d <= 0 || d > fc::kMaxRowFeatures) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x || !grad_y || !w || !u_hat || !b || !grad_x || !grad_w || !grad_u_hat || !grad_b) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  FC_ROW_DISPATCH_PS(d, hipLaunchKernelGGL(fc::planar_ps_backward_kernel<E>, dim3(fc::ps_row_grid(n)), dim3(256), 0, s, x,
-                                           grad_y, grad_logabsdet, w, u_hat, b, grad_x, grad_w, grad_u_hat, grad_b, n, d));
+  FC_ROW_DISPATCH(d, hipLaunchKernelGGL(fc::planar_ps_backward_kernel<E>, dim3(fc::row_grid(n, fc::kStreamGridCap)), dim3(256),
+                                        0, s, x, grad_y, grad_logabsdet, w, u_hat, b, grad_x, grad_w, grad_u_hat, grad_b, n,
+                                        d));
   return hipGetLastError();
 }

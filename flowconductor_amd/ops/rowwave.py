@@ -125,6 +125,28 @@ def _param(t, device, name):
     return _hip.dev_f32(torch.as_tensor(t).detach().to(device), name)
 
 
+def _check_q_vectors(q, x):
+    """``q`` [K, D] shared or [N, K, D] per sample against the rows ``x``; True when per-sample."""
+    n, d = x.shape
+    per_sample = q.dim() == 3
+    if q.shape[-1] != d or (per_sample and q.shape[0] != n) or q.dim() not in (2, 3):
+        raise ValueError("q_vectors of shape %s do not match inputs %s" % (tuple(q.shape), tuple(x.shape)))
+    return per_sample
+
+
+def _check_planar_parameters(wv, uv, bv, x, per_sample):
+    n, d = x.shape
+    rows = n if per_sample else 1
+    if wv.numel() != rows * d or uv.numel() != rows * d or bv.numel() != rows:
+        raise ValueError("planar parameters do not match %d features" % d)
+
+
+def _check_matrices(m, x):
+    n, d = x.shape
+    if m.numel() != n * d * d:
+        raise ValueError("matrices must be [%d, %d, %d]" % (n, d, d))
+
+
 def householder(inputs, q_vectors, reverse=False):
     """Apply K Householder reflections (reference orthogonal.py:144-194).
 
@@ -134,9 +156,7 @@ def householder(inputs, q_vectors, reverse=False):
     _hip.require_no_grad(inputs, q_vectors)
     q = _param(q_vectors, x.device, "q_vectors")
     n, d = x.shape
-    per_sample = q.dim() == 3
-    if q.shape[-1] != d or (per_sample and q.shape[0] != n) or q.dim() not in (2, 3):
-        raise ValueError("q_vectors of shape %s do not match inputs %s" % (tuple(q.shape), tuple(x.shape)))
+    per_sample = _check_q_vectors(q, x)
     y = torch.empty_like(x)
     _call("fc_householder", lib.fc_householder, x.device, _hip.ptr(x), _hip.ptr(y), _hip.ptr(q), n, d,
           q.shape[-2], 1 if per_sample else 0, 1 if reverse else 0, _hip.stream_ptr(x.device))
@@ -153,9 +173,7 @@ def planar(inputs, w, u_hat, b, per_sample=False):
     wv = _param(w, x.device, "w").reshape(-1)
     uv = _param(u_hat, x.device, "u").reshape(-1)
     bv = _param(b, x.device, "b").reshape(-1)
-    rows = n if per_sample else 1
-    if wv.numel() != rows * d or uv.numel() != rows * d or bv.numel() != rows:
-        raise ValueError("planar parameters do not match %d features" % d)
+    _check_planar_parameters(wv, uv, bv, x, per_sample)
     y = torch.empty_like(x)
     lad = torch.empty(n, dtype=torch.float32, device=x.device)
     _call("fc_planar", lib.fc_planar, x.device, _hip.ptr(x), _hip.ptr(y), _hip.ptr(lad), _hip.ptr(wv),
@@ -175,8 +193,7 @@ def linear_per_sample(inputs, matrices, mode=PER_SAMPLE_DENSE, offdiag_scale=1.0
     m = _hip.dev_f32(matrices, "matrices")
     _hip.require_no_grad(inputs, matrices)
     n, d = x.shape
-    if m.numel() != n * d * d:
-        raise ValueError("matrices must be [%d, %d, %d]" % (n, d, d))
+    _check_matrices(m, x)
     y = torch.empty_like(x)
     lad = torch.empty(n, dtype=torch.float32, device=x.device) if want_logabsdet else None
     _call("fc_linear_per_sample", lib.fc_linear_per_sample, x.device, _hip.ptr(x), _hip.ptr(y), _hip.ptr(lad),
@@ -232,8 +249,7 @@ def linear_per_sample_autograd(inputs, matrices, mode=PER_SAMPLE_DENSE, offdiag_
     if torch.is_grad_enabled() and (inputs.requires_grad or matrices.requires_grad or scale_grad):
         x = _rows(inputs)
         m = _hip.dev_f32(matrices, "matrices")
-        if m.numel() != x.shape[0] * x.shape[1] * x.shape[1]:
-            raise ValueError("matrices must be [%d, %d, %d]" % (x.shape[0], x.shape[1], x.shape[1]))
+        _check_matrices(m, x)
         if scale_grad:
             offdiag_scale = _hip.dev_f32(offdiag_scale, "offdiag_scale")
         outputs, logabsdet = _LinearPerSampleFunction.apply(x, m, offdiag_scale, mode, eps)
@@ -263,6 +279,21 @@ def linear(inputs, a, b=None, bias=None, mode=LINEAR_DENSE):
     return y
 
 
+def _householder_backward(outputs, grad_outputs, q, reverse):
+    """(grad_inputs, grad_q) of ``householder`` from its saved OUTPUT.  Shared q [K, D]: ``fc_householder_backward`` adds
+    the batch's sum into a zeroed grad_q; per-sample q [N, K, D]: ``fc_householder_backward_per_sample`` writes every
+    element of grad_q once."""
+    lib = _hip.load()
+    n, d = outputs.shape
+    per_sample = q.dim() == 3
+    entry = "fc_householder_backward_per_sample" if per_sample else "fc_householder_backward"
+    gx = torch.empty_like(outputs)
+    gq = torch.empty_like(q) if per_sample else torch.zeros_like(q)
+    _call(entry, getattr(lib, entry), outputs.device, _hip.ptr(outputs), _hip.ptr(grad_outputs), _hip.ptr(q), _hip.ptr(gx),
+          _hip.ptr(gq), n, d, q.shape[-2], 1 if reverse else 0, _hip.stream_ptr(outputs.device))
+    return gx, gq
+
+
 class _HouseholderFunction(torch.autograd.Function):
     """``householder`` with batch-shared q-vectors and its HIP backward kernel (``fc_householder_backward``: the
     reflections are involutions, so the saved OUTPUT is walked back to every intermediate)."""
@@ -278,15 +309,8 @@ class _HouseholderFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_outputs):
         outputs, q_vectors = ctx.saved_tensors
-        lib = _hip.load()
-        y = _hip.dev_f32(outputs, "outputs")
-        q = _hip.dev_f32(q_vectors.detach(), "q_vectors")
-        gy = _hip.dev_f32(grad_outputs, "grad_outputs")
-        n, d = y.shape
-        gx = torch.empty_like(y)
-        gq = torch.zeros_like(q)
-        _call("fc_householder_backward", lib.fc_householder_backward, y.device, _hip.ptr(y), _hip.ptr(gy), _hip.ptr(q),
-              _hip.ptr(gx), _hip.ptr(gq), n, d, q.shape[0], 1 if ctx.reverse else 0, _hip.stream_ptr(y.device))
+        gx, gq = _householder_backward(_hip.dev_f32(outputs, "outputs"), _hip.dev_f32(grad_outputs, "grad_outputs"),
+                                       _hip.dev_f32(q_vectors.detach(), "q_vectors"), ctx.reverse)
         return gx, gq, None
 
 
@@ -307,16 +331,9 @@ class _HouseholderPerSampleFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable      # no double backward: create_graph=True raises instead of going silent
     def backward(ctx, grad_outputs):
         outputs, q_vectors = ctx.saved_tensors
-        lib = _hip.load()
-        y = _hip.dev_f32(outputs, "outputs")
-        q = _hip.dev_f32(q_vectors, "q_vectors")
-        gy = _hip.dev_f32(grad_outputs.contiguous(), "grad_outputs")
-        n, d = y.shape
-        gx = torch.empty_like(y)
-        gq = torch.empty_like(q)
-        _call("fc_householder_backward_per_sample", lib.fc_householder_backward_per_sample, y.device, _hip.ptr(y),
-              _hip.ptr(gy), _hip.ptr(q), _hip.ptr(gx), _hip.ptr(gq), n, d, q.shape[1], 1 if ctx.reverse else 0,
-              _hip.stream_ptr(y.device))
+        gx, gq = _householder_backward(_hip.dev_f32(outputs, "outputs"),
+                                       _hip.dev_f32(grad_outputs.contiguous(), "grad_outputs"),
+                                       _hip.dev_f32(q_vectors, "q_vectors"), ctx.reverse)
         return gx, gq, None
 
 
@@ -330,8 +347,7 @@ def householder_autograd(inputs, q_vectors, reverse=False):
         if q_vectors.dim() == 3:
             x = _rows(inputs)
             q = _hip.dev_f32(q_vectors, "q_vectors")
-            if q.shape[0] != x.shape[0] or q.shape[2] != x.shape[1]:
-                raise ValueError("q_vectors of shape %s do not match inputs %s" % (tuple(q.shape), tuple(x.shape)))
+            _check_q_vectors(q, x)
             return _HouseholderPerSampleFunction.apply(x, q, bool(reverse)), x.new_zeros(x.shape[0])
     return householder(inputs, q_vectors, reverse=reverse), inputs.new_zeros(inputs.shape[0])
 
@@ -422,6 +438,27 @@ def hdh_linear_autograd(inputs, q_a, q_b, scale, pre=None, post=None, reverse_a=
     return hdh_linear(inputs, q_a, q_b, scale, pre, post, reverse_a, reverse_b)
 
 
+def _planar_backward(x, grad_outputs, grad_logabsdet, wv, uv, bv, per_sample):
+    """(gx, gw, gu, gb) of ``planar`` for device f32 operands.  Shared parameters [D] / [1]: ``fc_planar_backward`` adds
+    the batch's sums into one zeroed buffer; per-sample [N, D] / [N]: ``fc_planar_backward_per_sample`` writes every
+    element once."""
+    lib = _hip.load()
+    n, d = x.shape
+    gy = _hip.dev_f32(grad_outputs if grad_outputs is not None else torch.zeros_like(x), "grad_outputs")
+    gl = None if grad_logabsdet is None else _hip.dev_f32(grad_logabsdet, "grad_logabsdet")
+    gx = torch.empty_like(x)
+    if per_sample:
+        entry = "fc_planar_backward_per_sample"
+        gw, gu, gb = torch.empty_like(wv), torch.empty_like(uv), torch.empty_like(bv)
+    else:
+        entry = "fc_planar_backward"
+        gpar = torch.zeros(2 * d + 1, dtype=torch.float32, device=x.device)      # gw | gu | gb, one zero fill
+        gw, gu, gb = gpar[:d], gpar[d:2 * d], gpar[2 * d:]
+    _call(entry, getattr(lib, entry), x.device, _hip.ptr(x), _hip.ptr(gy), _hip.ptr(gl), _hip.ptr(wv), _hip.ptr(uv),
+          _hip.ptr(bv), _hip.ptr(gx), _hip.ptr(gw), _hip.ptr(gu), _hip.ptr(gb), n, d, _hip.stream_ptr(x.device))
+    return gx, gw, gu, gb
+
+
 class _PlanarFunction(torch.autograd.Function):
     """Shared-parameter ``planar`` with its HIP backward kernel (``fc_planar_backward``)."""
 
@@ -435,20 +472,10 @@ class _PlanarFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_outputs, grad_logabsdet):
         inputs, w, u_hat, b = ctx.saved_tensors
-        lib = _hip.load()
-        x = _hip.dev_f32(inputs.detach(), "inputs")
-        n, d = x.shape
-        wv = _hip.dev_f32(w.detach().reshape(-1), "w")
-        uv = _hip.dev_f32(u_hat.detach().reshape(-1), "u")
-        bv = _hip.dev_f32(b.detach().reshape(-1), "b")
-        gy = _hip.dev_f32(grad_outputs if grad_outputs is not None else torch.zeros_like(x), "grad_outputs")
-        gl = None if grad_logabsdet is None else _hip.dev_f32(grad_logabsdet, "grad_logabsdet")
-        gx = torch.empty_like(x)
-        gpar = torch.zeros(2 * d + 1, dtype=torch.float32, device=x.device)      # gw | gu | gb, one zero fill
-        _call("fc_planar_backward", lib.fc_planar_backward, x.device, _hip.ptr(x), _hip.ptr(gy), _hip.ptr(gl),
-              _hip.ptr(wv), _hip.ptr(uv), _hip.ptr(bv), _hip.ptr(gx), _hip.ptr(gpar[:d]), _hip.ptr(gpar[d:2 * d]),
-              _hip.ptr(gpar[2 * d:]), n, d, _hip.stream_ptr(x.device))
-        return gx, gpar[:d].view_as(w), gpar[d:2 * d].view_as(u_hat), gpar[2 * d:].view_as(b)
+        wv, uv, bv = (_hip.dev_f32(t.detach().reshape(-1), name) for t, name in ((w, "w"), (u_hat, "u"), (b, "b")))
+        gx, gw, gu, gb = _planar_backward(_hip.dev_f32(inputs.detach(), "inputs"), grad_outputs, grad_logabsdet, wv, uv, bv,
+                                          False)
+        return gx, gw.view_as(w), gu.view_as(u_hat), gb.view_as(b)
 
 
 class _PlanarPerSampleFunction(torch.autograd.Function):
@@ -466,15 +493,7 @@ class _PlanarPerSampleFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable      # no double backward: create_graph=True raises instead of going silent
     def backward(ctx, grad_outputs, grad_logabsdet):
         x, wv, uv, bv = ctx.saved_tensors
-        lib = _hip.load()
-        n, d = x.shape
-        gy = _hip.dev_f32(grad_outputs.contiguous() if grad_outputs is not None else torch.zeros_like(x), "grad_outputs")
-        gl = None if grad_logabsdet is None else _hip.dev_f32(grad_logabsdet.contiguous(), "grad_logabsdet")
-        gx, gw, gu, gb = torch.empty_like(x), torch.empty_like(wv), torch.empty_like(uv), torch.empty_like(bv)
-        _call("fc_planar_backward_per_sample", lib.fc_planar_backward_per_sample, x.device, _hip.ptr(x), _hip.ptr(gy),
-              _hip.ptr(gl), _hip.ptr(wv), _hip.ptr(uv), _hip.ptr(bv), _hip.ptr(gx), _hip.ptr(gw), _hip.ptr(gu), _hip.ptr(gb),
-              n, d, _hip.stream_ptr(x.device))
-        return gx, gw, gu, gb
+        return _planar_backward(x, grad_outputs, grad_logabsdet, wv, uv, bv, True)
 
 
 def planar_autograd(inputs, w, u_hat, b, per_sample=False):
@@ -486,21 +505,9 @@ def planar_autograd(inputs, w, u_hat, b, per_sample=False):
         x = _rows(inputs)
         n, d = x.shape
         wv, uv, bv = (_hip.dev_f32(t, name) for t, name in ((w, "w"), (u_hat, "u"), (b, "b")))
-        if wv.numel() != n * d or uv.numel() != n * d or bv.numel() != n:
-            raise ValueError("planar parameters do not match %d features" % d)
+        _check_planar_parameters(wv, uv, bv, x, True)
         return _PlanarPerSampleFunction.apply(x, wv.reshape(n, d), uv.reshape(n, d), bv.reshape(n))
     return planar(inputs, w, u_hat, b, per_sample=per_sample)
-
-
-def _householder_backward(outputs, grad_outputs, q, reverse):
-    """(grad_inputs, grad_q) of ``householder`` with shared q from its saved OUTPUT (``fc_householder_backward``)."""
-    lib = _hip.load()
-    n, d = outputs.shape
-    gx = torch.empty_like(outputs)
-    gq = torch.zeros_like(q)
-    _call("fc_householder_backward", lib.fc_householder_backward, outputs.device, _hip.ptr(outputs), _hip.ptr(grad_outputs),
-          _hip.ptr(q), _hip.ptr(gx), _hip.ptr(gq), n, d, q.shape[0], 1 if reverse else 0, _hip.stream_ptr(outputs.device))
-    return gx, gq
 
 
 class _SylvesterFunction(torch.autograd.Function):

@@ -6,8 +6,8 @@ import torch
 from torch.nn import functional as F
 
 LINEAR_SHAPES = [(37, 2), (37, 5), (50, 16), (37, 17), (21, 64), (21, 65), (9, 130), (5, 260)]
-HOUSEHOLDER_SHAPES = [(5, 5), (16, 3), (17, 17), (64, 8), (100, 11), (260, 2)]
-PLANAR_WIDTHS = [2, 7, 16, 30, 64, 100]
+HOUSEHOLDER_SHAPES = [(5, 5), (16, 3), (17, 17), (64, 8), (100, 11), (200, 9), (260, 2)]
+PLANAR_WIDTHS = [2, 7, 16, 30, 64, 100, 130, 300]
 OFFDIAG_SCALE, EPS = 0.3, 1e-3
 
 
