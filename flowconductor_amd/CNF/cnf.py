@@ -1,0 +1,141 @@
+"""``CNF``: a continuous normalizing flow, the solution map of ``dz/dt = f(t, z)`` with ``dlogp/dt = -div f`` carried
+along (class, constructor arguments and ``state_dict`` keys of flowcon/CNF/cnf.py), and ``CNFTransform``, which makes
+one a ``Transform``.
+
+The solver is the package's own (``flowconductor_amd.CNF.odeint``).  ``solver_options`` reaches it in eval mode as
+well as in training mode (a fixed-step ``test_solver`` is of little use without its ``step_size``).
+
+Routes of ``CNF.forward`` in eval mode, for an ``odefunc`` the kernels take (see ``ODEfunc``) and two integration
+times:
+* ``test_solver`` in ``euler`` / ``midpoint`` / ``rk4``: the whole solve is one ``fc_cnf_integrate`` launch;
+* ``dopri5``: the host loop of ``odeint`` with one ``fc_cnf_field`` launch per evaluation.
+Everything else is the torch composition on the tensors' device."""
+import torch
+from torch import nn
+
+from flowconductor_amd import ops
+from flowconductor_amd.transforms.base import Transform
+
+from .neural_odes.odefunc import ODEfunc
+from .neural_odes.wrappers.cnf_regularization import RegularizedODEfunc
+from .odeint import fixed_grid_steps, odeint
+
+__all__ = ["CNF", "CNFTransform"]
+
+
+class CNF(nn.Module):
+    def __init__(self, odefunc, T=1.0, train_T=False, regularization_fns=None, solver='dopri5', atol=1e-5, rtol=1e-5):
+        super().__init__()
+        sqrt_end_time = torch.sqrt(torch.tensor(float(T)))
+        if train_T:
+            self.register_parameter("sqrt_end_time", nn.Parameter(sqrt_end_time))
+        else:
+            self.register_buffer("sqrt_end_time", sqrt_end_time)
+        nreg = 0
+        if regularization_fns is not None:
+            odefunc = RegularizedODEfunc(odefunc, regularization_fns)
+            nreg = len(regularization_fns)
+        self.odefunc = odefunc
+        self.nreg = nreg
+        self.regularization_states = None
+        self.solver = solver
+        self.atol = atol
+        self.rtol = rtol
+        self.test_solver = solver
+        self.test_atol = atol
+        self.test_rtol = rtol
+        self.solver_options = {}
+
+    def _default_times(self, z):
+        """``[0, sqrt_end_time ** 2]``: a tensor where the end time is being trained, else two floats whose read of
+        the buffer is kept per version of it (no host sync on later calls)."""
+        end = self.sqrt_end_time
+        if end.requires_grad and torch.is_grad_enabled():
+            return torch.stack([torch.zeros_like(end), end * end]).to(z)
+        value = ops.memo(self, "end_time", ops.cache_key(end), lambda: float((end.detach() * end.detach()).float()))
+        return [0.0, value]
+
+    def _kernel_solve(self, z, logpz, times):
+        """``(z_t, logp_t)`` from one ``fc_cnf_integrate`` launch, or None when this call is not one for it."""
+        method = ops.CNF_METHODS.get(self.test_solver)
+        if self.training or method is None or len(times) != 2 or any(isinstance(v, torch.Tensor) for v in times):
+            return None
+        func = self.odefunc.odefunc if isinstance(self.odefunc, RegularizedODEfunc) else self.odefunc
+        if type(func) is not ODEfunc or ops.has_hooks(self):
+            return None
+        if not (isinstance(logpz, torch.Tensor) and logpz.is_cuda and logpz.dtype == torch.float32
+                and logpz.device == z.device and logpz.numel() == z.shape[0] and logpz.is_contiguous()
+                and not (torch.is_grad_enabled() and logpz.requires_grad)):
+            return None
+        plan = func._use_kernels(z)
+        if plan is None:
+            return None
+        steps = fixed_grid_steps(times[0], times[1], self.solver_options)
+        z_t, logp_t = ops.cnf_integrate(z, logpz, t0=times[0], t1=times[1], steps=steps, method=method,
+                                        **func._kernel_args(plan))
+        return z_t, logp_t.view(logpz.shape)
+
+    def forward(self, z, logpz=None, integration_times=None, reverse=False):
+        _logpz = torch.zeros(z.shape[0], 1).to(z) if logpz is None else logpz
+        if integration_times is None:
+            times = self._default_times(z)
+        elif isinstance(integration_times, torch.Tensor) and integration_times.requires_grad \
+                and torch.is_grad_enabled():
+            times = integration_times.to(z)
+        else:       # numbers on the host (reading a device tensor waits for the device)
+            times = [float(v) for v in torch.as_tensor(integration_times).detach().reshape(-1).tolist()]
+        if reverse:
+            times = torch.flip(times, [0]) if isinstance(times, torch.Tensor) else times[::-1]
+
+        self.odefunc.before_odeint()        # refresh the evaluation count and the noise
+        solved = self._kernel_solve(z, _logpz, times)
+        if solved is not None:
+            z_t, logpz_t = solved
+            self.regularization_states = ()
+        else:
+            if self.training:
+                state = (z, _logpz) + tuple(torch.tensor(0).to(z) for _ in range(self.nreg))
+                state_t = odeint(self.odefunc, state, times, atol=self.atol, rtol=self.rtol, method=self.solver,
+                                 options=self.solver_options)
+            else:
+                state_t = odeint(self.odefunc, (z, _logpz), times, atol=self.test_atol, rtol=self.test_rtol,
+                                 method=self.test_solver, options=self.solver_options)
+            if len(times) == 2:
+                state_t = tuple(s[1] for s in state_t)
+            z_t, logpz_t = state_t[:2]
+            self.regularization_states = state_t[2:]
+        return (z_t, logpz_t) if logpz is not None else z_t
+
+    def get_regularization_states(self):
+        reg_states = self.regularization_states
+        self.regularization_states = None
+        return reg_states
+
+    def num_evals(self):
+        """Function evaluations of the last solve (reads a device word: a host sync)."""
+        return self.odefunc._num_evals.item()
+
+
+class CNFTransform(Transform):
+    """A ``CNF`` as a ``Transform`` (an extension: the reference has no such adapter): ``forward`` integrates from 0 to
+    T and returns ``(z_T, logabsdet)`` with ``logabsdet = log|det dz_T / dz_0| = -(logp_T - logp_0)``; ``inverse``
+    integrates backwards.  With it a CNF sits in ``CompositeTransform`` and ``Flow``."""
+
+    _HIP_AUTOGRAD = True    # delegates: the routes that run with autograd on are the differentiable composition
+
+    def __init__(self, cnf):
+        super().__init__()
+        self.cnf = cnf
+
+    def _run(self, inputs, context, reverse):
+        if context is not None:
+            raise ValueError("CNFTransform takes no context")
+        outputs, delta = self.cnf(inputs, torch.zeros(inputs.shape[0], 1, dtype=inputs.dtype, device=inputs.device),
+                                  reverse=reverse)
+        return outputs, -delta.reshape(inputs.shape[0])
+
+    def forward(self, inputs, context=None):
+        return self._run(inputs, context, reverse=False)
+
+    def inverse(self, inputs, context=None):
+        return self._run(inputs, context, reverse=True)

@@ -1,0 +1,467 @@
+// Continuous normalizing flows in eval mode (reference flowcon/CNF/cnf.py with neural_odes/odefunc.py and
+// neural_odes/diffeq_layers/basic.py).
+//
+//   fc_cnf_field       dy = f(t, y) and -div_y f(t, y) of an ODEnet over time-conditioned linear layers    one launch
+//   fc_cnf_integrate   z(t1), logp(t1) from z(t0), logp(t0) under d/dt (z, logp) = (f, -div f) with a fixed-step
+//                      Runge-Kutta method, every row on its own                                            one launch
+//
+// f is an MLP whose layers all reduce to
+//     pre = W x + b + w_t t,   out = pre * gate + w_b t,   gate = sigmoid(w_g t + b_g)  or  1
+// (ignore / concat / concat_v2 / squash / concatsquash), an element-wise activation between the layers and none after
+// the last.  The host hands over an IMAGE of the net, all of it float32, every piece on a 16-byte boundary, per layer
+//     b[op] w_t[op] w_g[op] b_g[op] w_b[op] wt[in][op]        op = out rounded up to 4, wt[k][o] = W[o][k]
+// with zero padding.  A block copies the image into LDS once and walks over row tiles.
+//
+// The exact divergence is a forward-mode computation of the same shape as f, laid out like ires_net
+// (fc_iresblock.hip): a row is carried by a group of G lanes (the smallest power of two >= d + 1), lane 0 runs the
+// value stream, lane j + 1 the tangent d/dy_j (no bias, no time terms); the tangent streams pick the value stream's
+// gated pre-activation up with a shuffle inside the group for the activation's derivative.  Activations ping-pong in
+// LDS as st[k][thread].  Lane j + 1 ends with row j of its Jacobian column, of which only df_j/dy_j is used: the
+// divergence is a sum over the group, no LU.
+//
+// Whatever depends on t alone (b + w_t t, the gate, w_b t) is the same for every row: the block computes it once per
+// evaluation into an LDS table, in float64.  In the integrator all rows of a launch share the step sequence, so the
+// table is rebuilt per stage behind a barrier.
+//
+// Numerics: sums in float64 over the float32 weights, a stored activation rounded to float32 once (cnf_net is the
+// one place that decides this); the integrator keeps (z, logp) and the stage slopes in float64 registers and rounds
+// a stage's state to float32 where it enters the net.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/flowcon_hip.h"
+#include "fc_device.h"
+
+namespace fc {
+
+struct CnfShape {
+  int d, layers, act, gated, residual;
+  int w[FC_CNF_MAX_HIDDEN_LAYERS + 2];  // w[0] = d, hidden widths, w[layers] = d
+  double scale, p0;
+};
+
+__host__ __device__ inline int cnf_pad4(int v) { return (v + 3) & ~3; }
+
+__host__ __device__ inline int cnf_image_floats(const CnfShape& sh) {
+  int total = 0;
+  for (int l = 0; l < sh.layers; ++l) total += (5 + sh.w[l]) * cnf_pad4(sh.w[l + 1]);
+  return total;
+}
+
+__host__ __device__ inline int cnf_table_doubles(const CnfShape& sh) {
+  int total = 0;
+  for (int l = 0; l < sh.layers; ++l) total += 3 * cnf_pad4(sh.w[l + 1]);
+  return total;
+}
+
+__host__ __device__ inline int cnf_max_width(const CnfShape& sh) {
+  int m = sh.d;
+  for (int l = 1; l < sh.layers; ++l) m = sh.w[l] > m ? sh.w[l] : m;
+  return m;
+}
+
+// value and derivative of the activation, in float64 on the float64 pre-activation
+__device__ __forceinline__ void cnf_act(int act, double x, double p0, double& f, double& df) {
+  switch (act) {
+    case FC_CNF_ACT_TANH: {
+      const double th = tanh(x);
+      f = th;
+      df = 1.0 - th * th;
+      break;
+    }
+    case FC_CNF_ACT_RELU:
+      f = x > 0.0 ? x : 0.0;
+      df = x > 0.0 ? 1.0 : 0.0;
+      break;
+    case FC_CNF_ACT_SOFTPLUS: {  // beta 1, threshold 20 as torch evaluates it
+      const double sg = 1.0 / (1.0 + exp(-x));
+      f = x > 20.0 ? x : log1p(exp(x));
+      df = x > 20.0 ? 1.0 : sg;
+      break;
+    }
+    case FC_CNF_ACT_ELU:
+      f = x > 0.0 ? x : p0 * expm1(x);
+      df = x > 0.0 ? 1.0 : p0 * exp(x);
+      break;
+    case FC_CNF_ACT_SWISH: {
+      const double sg = 1.0 / (1.0 + exp(-x));
+      f = x * sg;
+      df = sg + x * sg * (1.0 - sg);
+      break;
+    }
+    case FC_CNF_ACT_SQUARE:
+      f = x * x;
+      df = 2.0 * x;
+      break;
+    default:
+      f = x;
+      df = 1.0;
+      break;
+  }
+}
+
+// What depends on t alone, per layer [b + w_t t | gate | w_b t], each op doubles.  The whole block takes part; the
+// caller puts barriers round it.
+__device__ __forceinline__ void cnf_time_table(const float* img, double* tab, const CnfShape& sh, double t, int tid,
+                                               int T) {
+  const float* p = img;
+  double* q = tab;
+  for (int l = 0; l < sh.layers; ++l) {
+    const int op = cnf_pad4(sh.w[l + 1]);
+    for (int o = tid; o < op; o += T) {
+      q[o] = (double)p[o] + (double)p[op + o] * t;
+      q[op + o] = sh.gated ? 1.0 / (1.0 + exp(-((double)p[2 * op + o] * t + (double)p[3 * op + o]))) : 1.0;
+      q[2 * op + o] = (double)p[4 * op + o] * t;
+    }
+    p += (5 + sh.w[l]) * op;
+    q += 3 * op;
+  }
+}
+
+// ---- the net on one stream -------------------------------------------------------------------------------------------
+
+// Runs the layers on the state column `mine` (stride T, the second buffer `half` floats further on), whose first d
+// entries the caller has set: the input (value stream, s == 0) or a unit tangent (s >= 1).  out[i], i < DP: the last
+// layer in unrounded float64 -- f in the value stream, column s - 1 of df/dy in stream s.  This is the one place that
+// fixes where float32 roundings happen: a stored activation, once.
+template <int G, int DP>
+__device__ __forceinline__ void cnf_net(const float* img, const double* tab, float* mine, int T, int half,
+                                        const CnfShape& sh, int s, double (&out)[DP]) {
+  const bool value = s == 0;
+  const float* p = img;
+  const double* q = tab;
+  float* cur = mine;
+  float* nxt = mine + half;
+  for (int l = 0; l + 1 < sh.layers; ++l) {
+    const int in = sh.w[l], width = sh.w[l + 1], op = cnf_pad4(width);
+    const float* wt = p + 5 * op;
+    for (int o = 0; o < op; o += 4) {
+      double sum[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) sum[c] = value ? q[o + c] : 0.0;  // a tangent has no bias and no time terms
+      for (int k = 0; k < in; ++k) {
+        const double v = (double)cur[k * T];
+        const float4 w4 = *reinterpret_cast<const float4*>(wt + k * op + o);
+        sum[0] = fma((double)w4.x, v, sum[0]);
+        sum[1] = fma((double)w4.y, v, sum[1]);
+        sum[2] = fma((double)w4.z, v, sum[2]);
+        sum[3] = fma((double)w4.w, v, sum[3]);
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        double lin = sum[c] * q[op + o + c];
+        if (value) lin += q[2 * op + o + c];
+        const double pre = __shfl(lin, 0, G);  // the value stream's
+        if (o + c < width) {
+          double f, df;
+          cnf_act(sh.act, pre, sh.p0, f, df);
+          nxt[(o + c) * T] = (float)(value ? f : df * lin);
+        }
+      }
+    }
+    float* swap = cur;
+    cur = nxt;
+    nxt = swap;
+    p = wt + in * op;
+    q += 3 * op;
+  }
+  const int in = sh.w[sh.layers - 1], dp = cnf_pad4(sh.d);
+  const float* wt = p + 5 * dp;
+#pragma unroll
+  for (int i = 0; i < DP; ++i) out[i] = (value && i < dp) ? q[i] : 0.0;
+  for (int k = 0; k < in; ++k) {
+    const double v = (double)cur[k * T];
+#pragma unroll
+    for (int c = 0; c < DP / 4; ++c) {
+      if (4 * c < dp) {
+        const float4 w4 = *reinterpret_cast<const float4*>(wt + k * dp + 4 * c);
+        out[4 * c + 0] = fma((double)w4.x, v, out[4 * c + 0]);
+        out[4 * c + 1] = fma((double)w4.y, v, out[4 * c + 1]);
+        out[4 * c + 2] = fma((double)w4.z, v, out[4 * c + 2]);
+        out[4 * c + 3] = fma((double)w4.w, v, out[4 * c + 3]);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < DP; ++i) {
+    if (i < dp) {
+      out[i] *= q[dp + i];
+      if (value) out[i] += q[2 * dp + i];
+    }
+  }
+}
+
+// One evaluation of the ODE function for the row of this group at the float32 state xin: k[i] = dy_i (meaningful in
+// the value lane), negdiv = -div (the same in every lane of the group), scale_output and residual folded in.
+template <int G, int DP>
+__device__ __forceinline__ void cnf_field_row(const float* img, const double* tab, float* mine, int T, int half,
+                                              const CnfShape& sh, int s, const float (&xin)[DP], double (&k)[DP],
+                                              double& negdiv) {
+#pragma unroll
+  for (int i = 0; i < DP; ++i)
+    if (i < sh.d) mine[i * T] = s == 0 ? xin[i] : (i == s - 1 ? 1.f : 0.f);
+  cnf_net<G, DP>(img, tab, mine, T, half, sh, s, k);
+  double diag = 0.0;
+#pragma unroll
+  for (int i = 0; i < DP; ++i)
+    if (i == s - 1 && i < sh.d) diag = k[i];
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) diag += __shfl_xor(diag, off, G);
+  double div = diag * sh.scale;
+#pragma unroll
+  for (int i = 0; i < DP; ++i) {
+    k[i] *= sh.scale;
+    if (sh.residual) k[i] -= (double)xin[i];
+  }
+  if (sh.residual) div -= (double)sh.d;
+  negdiv = -div;
+}
+
+template <int G>
+struct CnfGroup {
+  static constexpr int DMAX = G == 32 ? 16 : G - 1;
+  static constexpr int DP = (DMAX + 3) & ~3;
+};
+
+// ---- one evaluation -------------------------------------------------------------------------------------------------
+
+template <int G>
+__global__ __launch_bounds__(256) void cnf_field_kernel(const float* __restrict__ y, const float* __restrict__ image,
+                                                        float* __restrict__ dy, float* __restrict__ negdiv,
+                                                        float* __restrict__ evals, int64_t n, CnfShape sh,
+                                                        int image_floats, int table_doubles, float t_host,
+                                                        const float* __restrict__ t_dev) {
+  constexpr int DP = CnfGroup<G>::DP;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* img = lds;
+  double* tab = reinterpret_cast<double*>(lds + image_floats);
+  float* st = lds + image_floats + 2 * table_doubles;
+  const int T = blockDim.x, tid = threadIdx.x;
+  for (int i = tid; i < image_floats; i += T) img[i] = image[i];
+  __syncthreads();
+  cnf_time_table(img, tab, sh, t_dev ? (double)t_dev[0] : (double)t_host, tid, T);
+  __syncthreads();
+  const int d = sh.d, s = tid % G, rows_per_block = T / G, half = cnf_max_width(sh) * T;
+  const int64_t tiles = (n + rows_per_block - 1) / rows_per_block;
+  float* mine = st + tid;
+  if (evals && blockIdx.x == 0 && tid == 0) atomicAdd(evals, 1.f);
+
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    int64_t row = tile * rows_per_block + tid / G;
+    const bool live = row < n;
+    if (!live) row = n - 1;  // every lane runs (the shuffles need them); only live rows are stored
+    float xin[DP];
+#pragma unroll
+    for (int i = 0; i < DP; ++i) xin[i] = i < d ? y[row * d + i] : 0.f;
+    double k[DP], nd;
+    cnf_field_row<G, DP>(img, tab, mine, T, half, sh, s, xin, k, nd);
+    if (s == 0 && live) {
+#pragma unroll
+      for (int i = 0; i < DP; ++i)
+        if (i < d) dy[row * d + i] = (float)k[i];
+      negdiv[row] = (float)nd;
+    }
+  }
+}
+
+// ---- the whole solve ------------------------------------------------------------------------------------------------
+
+// Explicit methods whose stage i reads the slope of stage i - 1 only: y_i = y + a_i h k_{i-1}, t_i = t + c_i h,
+// y <- y + h sum b_i k_i.  Euler, the explicit midpoint rule, the classical fourth-order Runge-Kutta method.
+// (kept as selects, not as arrays: a run-time index into a local array would put it in scratch memory)
+__host__ __device__ inline int cnf_stages(int method) {
+  return method == FC_CNF_EULER ? 1 : method == FC_CNF_MIDPOINT ? 2 : 4;
+}
+
+// c_i, which is a_i as well: a stage that reads one slope sits at t + a_i h
+__device__ __forceinline__ double cnf_node(int method, int stage) {
+  if (method == FC_CNF_RK4) return stage == 0 ? 0.0 : stage == 3 ? 1.0 : 0.5;
+  return stage == 0 ? 0.0 : 0.5;
+}
+
+__device__ __forceinline__ double cnf_weight(int method, int stage) {
+  if (method == FC_CNF_RK4) return (stage == 0 || stage == 3) ? 1.0 / 6.0 : 1.0 / 3.0;
+  if (method == FC_CNF_MIDPOINT) return stage == 1 ? 1.0 : 0.0;
+  return 1.0;
+}
+
+template <int G>
+__global__ __launch_bounds__(256) void cnf_integrate_kernel(const float* __restrict__ z, const float* __restrict__ logp,
+                                                            const float* __restrict__ image, float* __restrict__ z_out,
+                                                            float* __restrict__ logp_out, float* __restrict__ evals,
+                                                            int64_t n, CnfShape sh, int image_floats,
+                                                            int table_doubles, double t0, double t1, int steps,
+                                                            int method) {
+  constexpr int DP = CnfGroup<G>::DP;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* img = lds;
+  double* tab = reinterpret_cast<double*>(lds + image_floats);
+  float* st = lds + image_floats + 2 * table_doubles;
+  const int T = blockDim.x, tid = threadIdx.x;
+  for (int i = tid; i < image_floats; i += T) img[i] = image[i];
+  const int d = sh.d, s = tid % G, rows_per_block = T / G, half = cnf_max_width(sh) * T;
+  const int64_t tiles = (n + rows_per_block - 1) / rows_per_block;
+  float* mine = st + tid;
+  const int stages = cnf_stages(method);
+  const double h = (t1 - t0) / (double)steps;
+  bool have_table = false;
+  double table_t = 0.0;
+  if (evals && blockIdx.x == 0 && tid == 0)  // non-negative floats order like their bit patterns
+    atomicMax(reinterpret_cast<int*>(evals), __float_as_int((float)steps * (float)stages));
+
+  // the tile loop's trip count depends on the block alone, so the barriers below are met by every thread
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    int64_t row = tile * rows_per_block + tid / G;
+    const bool live = row < n;
+    if (!live) row = n - 1;
+    double yv[DP], acc[DP], k[DP];
+#pragma unroll
+    for (int i = 0; i < DP; ++i) {
+      yv[i] = i < d ? (double)z[row * d + i] : 0.0;
+      k[i] = 0.0;
+    }
+    double lp = logp ? (double)logp[row] : 0.0, lk = 0.0, lacc;
+    for (int step = 0; step < steps; ++step) {
+      const double ts = t0 + (double)step * h;
+#pragma unroll
+      for (int i = 0; i < DP; ++i) acc[i] = 0.0;
+      lacc = 0.0;
+      for (int stage = 0; stage < stages; ++stage) {
+        const double node = cnf_node(method, stage), weight = cnf_weight(method, stage);
+        const double tt = ts + node * h;
+        if (!have_table || tt != table_t) {
+          __syncthreads();  // the image copy, and the readers of the previous table
+          cnf_time_table(img, tab, sh, tt, tid, T);
+          __syncthreads();
+          have_table = true;
+          table_t = tt;
+        }
+        float xin[DP];
+        const double ah = node * h;
+#pragma unroll
+        for (int i = 0; i < DP; ++i) xin[i] = (float)(stage == 0 ? yv[i] : yv[i] + ah * k[i]);
+        cnf_field_row<G, DP>(img, tab, mine, T, half, sh, s, xin, k, lk);
+#pragma unroll
+        for (int i = 0; i < DP; ++i) acc[i] += weight * k[i];
+        lacc += weight * lk;
+      }
+#pragma unroll
+      for (int i = 0; i < DP; ++i) yv[i] += h * acc[i];
+      lp += h * lacc;
+    }
+    if (s == 0 && live) {
+#pragma unroll
+      for (int i = 0; i < DP; ++i)
+        if (i < d) z_out[row * d + i] = (float)yv[i];
+      logp_out[row] = (float)lp;
+    }
+  }
+}
+
+// ---- launch ---------------------------------------------------------------------------------------------------------
+
+constexpr int kCnfLdsLimit = 128 * 1024;
+constexpr int kCnfMaxBlocks = 2048;
+
+static bool cnf_shape(int d, int layers, const int32_t* hidden, int kind, int act, int residual, float scale, float p0,
+                      int image_floats, CnfShape* sh) {
+  if (d < 1 || d > FC_CNF_MAX_DIM || layers < 1 || layers > FC_CNF_MAX_HIDDEN_LAYERS + 1) return false;
+  if (kind < 0 || kind > FC_CNF_LAYER_CONCATSQUASH || act < 0 || act > FC_CNF_ACT_IDENTITY) return false;
+  if (layers > 1 && !hidden) return false;
+  sh->d = d;
+  sh->layers = layers;
+  sh->act = act;
+  sh->gated = (kind == FC_CNF_LAYER_SQUASH || kind == FC_CNF_LAYER_CONCATSQUASH) ? 1 : 0;
+  sh->residual = residual ? 1 : 0;
+  sh->scale = (double)scale;
+  sh->p0 = (double)p0;
+  for (int l = 0; l < FC_CNF_MAX_HIDDEN_LAYERS + 2; ++l) sh->w[l] = 0;
+  sh->w[0] = d;
+  for (int l = 1; l < layers; ++l) {
+    if (hidden[l - 1] < 1 || hidden[l - 1] > FC_CNF_MAX_WIDTH) return false;
+    sh->w[l] = hidden[l - 1];
+  }
+  sh->w[layers] = d;
+  return cnf_image_floats(*sh) == image_floats;
+}
+
+// the largest block (256, 128, 64 threads) whose image + table + state fits 64 KiB, else 64 threads
+static int cnf_threads(const CnfShape& sh, int image_floats, int min_threads, size_t* lds) {
+  int threads = 256;
+  for (;; threads >>= 1) {
+    *lds = sizeof(float) * ((size_t)image_floats + 2 * (size_t)cnf_max_width(sh) * threads) +
+           sizeof(double) * (size_t)cnf_table_doubles(sh);
+    if (*lds <= 64 * 1024 || threads <= 64 || threads <= min_threads) break;
+  }
+  return threads;
+}
+
+template <int G>
+static int launch_cnf(const float* y, const float* logp, const float* image, float* out, float* out1, float* evals,
+                      int64_t n, const CnfShape& sh, int image_floats, bool integrate, float t_host, const float* t_dev,
+                      double t0, double t1, int steps, int method, hipStream_t s) {
+  size_t lds;
+  const int threads = cnf_threads(sh, image_floats, G, &lds);
+  if (lds > (size_t)kCnfLdsLimit) return hipErrorInvalidConfiguration;
+  static PerDeviceOnce once_field, once_integrate;
+  const hipError_t e =
+      integrate ? ensure_max_dynamic_lds(once_integrate, reinterpret_cast<const void*>(&cnf_integrate_kernel<G>),
+                                         kCnfLdsLimit)
+                : ensure_max_dynamic_lds(once_field, reinterpret_cast<const void*>(&cnf_field_kernel<G>), kCnfLdsLimit);
+  if (e != hipSuccess) return e;
+  const int rows = threads / G;
+  int64_t grid = (n + rows - 1) / rows;
+  if (grid > kCnfMaxBlocks) grid = kCnfMaxBlocks;
+  const int table = cnf_table_doubles(sh);
+  if (integrate)
+    hipLaunchKernelGGL((cnf_integrate_kernel<G>), dim3((unsigned)grid), dim3(threads), lds, s, y, logp, image, out,
+                       out1, evals, n, sh, image_floats, table, t0, t1, steps, method);
+  else
+    hipLaunchKernelGGL((cnf_field_kernel<G>), dim3((unsigned)grid), dim3(threads), lds, s, y, image, out, out1, evals,
+                       n, sh, image_floats, table, t_host, t_dev);
+  return hipGetLastError();
+}
+
+static int dispatch_cnf(const float* y, const float* logp, const float* image, float* out, float* out1, float* evals,
+                        int64_t n, const CnfShape& sh, int image_floats, bool integrate, float t_host,
+                        const float* t_dev, double t0, double t1, int steps, int method, hipStream_t s) {
+#define FC_CNF_GO(G) \
+  return launch_cnf<G>(y, logp, image, out, out1, evals, n, sh, image_floats, integrate, t_host, t_dev, t0, t1, steps, \
+                       method, s)
+  if (sh.d < 2) FC_CNF_GO(2);
+  if (sh.d < 4) FC_CNF_GO(4);
+  if (sh.d < 8) FC_CNF_GO(8);
+  if (sh.d < 16) FC_CNF_GO(16);
+  FC_CNF_GO(32);
+#undef FC_CNF_GO
+}
+
+}  // namespace fc
+
+extern "C" int fc_cnf_field(const float* y, const float* image, float* dy, float* negdiv, float* evals, int64_t n,
+                            int32_t d, int32_t layers, const int32_t* hidden, int32_t layer_kind, int32_t activation,
+                            int32_t residual, float scale_output, float p0, int32_t image_floats, float t,
+                            const float* t_dev, void* stream) {
+  fc::CnfShape sh;
+  if (n < 0 || !fc::cnf_shape(d, layers, hidden, layer_kind, activation, residual, scale_output, p0, image_floats, &sh))
+    return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  if (!y || !image || !dy || !negdiv || y == dy) return hipErrorInvalidValue;
+  return fc::dispatch_cnf(y, nullptr, image, dy, negdiv, evals, n, sh, image_floats, false, t, t_dev, 0.0, 0.0, 0, 0,
+                          static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fc_cnf_integrate(const float* z, const float* logp, const float* image, float* z_out, float* logp_out,
+                                float* evals, int64_t n, int32_t d, int32_t layers, const int32_t* hidden,
+                                int32_t layer_kind, int32_t activation, int32_t residual, float scale_output, float p0,
+                                int32_t image_floats, double t0, double t1, int32_t steps, int32_t method,
+                                void* stream) {
+  fc::CnfShape sh;
+  if (n < 0 || steps < 1 || method < FC_CNF_EULER || method > FC_CNF_RK4 || !(t0 == t0) || !(t1 == t1))
+    return hipErrorInvalidValue;
+  if (!fc::cnf_shape(d, layers, hidden, layer_kind, activation, residual, scale_output, p0, image_floats, &sh))
+    return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  if (!z || !image || !z_out || !logp_out || z == z_out) return hipErrorInvalidValue;
+  return fc::dispatch_cnf(z, logp, image, z_out, logp_out, evals, n, sh, image_floats, true, 0.f, nullptr, t0, t1,
+                          steps, method, static_cast<hipStream_t>(stream));
+}

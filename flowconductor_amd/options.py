@@ -41,6 +41,10 @@ _DEFAULTS = {
     # batch-axis reduction kernels (fc_batchnorm_train, fc_batchnorm_train_backward, fc_column_sums) instead of torch
     # reductions; False selects the torch expressions for A/B measurements.
     "batch_statistics_kernels": True,
+    # eval-mode continuous normalizing flows: the ODE function in fc_cnf_field (one launch per evaluation) and the
+    # fixed-step solves in fc_cnf_integrate (one launch per solve) instead of the torch composition, for batches up to
+    # ops.CNF_KERNEL_MAX_LANES lanes; "force" takes them at any batch size (measurements), False never
+    "cnf_kernels": True,
 }
 
 _values = dict(_DEFAULTS)

@@ -53,7 +53,8 @@ extern "C" {
  * fc_batchnorm_train(_backward), fc_column_sums and fc_colstats_workspace), and for the device loops of the
  * sum-of-sigmoids and sibling-spline layers fc_made_inverse_sos / fc_made_inverse_spline, and for the Sylvester
  * back substitution fc_sylvester_inverse, and for the per-sample backward entries fc_linear_per_sample_backward,
- * fc_householder_backward_per_sample and fc_planar_backward_per_sample). */
+ * fc_householder_backward_per_sample and fc_planar_backward_per_sample, and for the continuous-normalizing-flow
+ * entries fc_cnf_field / fc_cnf_integrate). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -580,6 +581,51 @@ int fc_iresnet_inverse(const float* y, const float* extra, const float* scale, c
                        uint32_t* max_iters, int64_t n, int32_t d, int32_t e, int32_t depth, int32_t growth,
                        int32_t activation, int32_t image_floats, int32_t max_iterations, float atol, float rtol,
                        void* stream);
+
+/* ---- continuous normalizing flows (eval mode) ------------------------------------------------- */
+/* ODEfunc over an ODEnet of time-conditioned linear layers (CNF/neural_odes/odefunc.py:98-182,
+ * diffeq_layers/basic.py:36-94): f(t, y) = scale_output * net(t, y) (- y with residual), every layer
+ *     pre = W x + b + w_t t,  out = pre * gate + w_b t,  gate = sigmoid(w_g t + b_g) or 1,
+ * the activation between layers, none after the last.  layers = hidden layers + 1; hidden[layers - 1] their widths
+ * (host memory, NULL when layers == 1).
+ *   image   float32 [image_floats]; per layer b[op] w_t[op] w_g[op] b_g[op] w_b[op] wt[in][op], op = out rounded
+ *           up to 4, wt[k][o] = W[o][k], zero padding; vectors a layer kind does not have are zero.  layer_kind
+ *           says whether the gate is evaluated (SQUASH, CONCATSQUASH) or is 1.  image_floats must equal the length
+ *           this layout gives.
+ *   p0      alpha of ELU
+ *   evals   float32 device word or NULL
+ * fc_cnf_field      dy [n, d] = f(t, y), negdiv [n] = -sum_j df_j/dy_j (exact, forward mode), t = t_dev[0] when
+ *           t_dev is not NULL, else the argument t; adds 1 to *evals.  y != dy.
+ * fc_cnf_integrate  (z_out [n, d], logp_out [n]) = (z, logp) + int_{t0}^{t1} (f, -div f) dt in `steps` equal steps of
+ *           Euler, the explicit midpoint rule or the classical Runge-Kutta method, every row on its own; logp NULL
+ *           means zeros; max-reduces steps * stages into *evals.  t1 < t0 integrates backwards.  z != z_out.
+ * 1 <= d <= FC_CNF_MAX_DIM, layers <= FC_CNF_MAX_HIDDEN_LAYERS + 1, widths <= FC_CNF_MAX_WIDTH
+ * (hipErrorInvalidValue otherwise). */
+#define FC_CNF_MAX_DIM 16
+#define FC_CNF_MAX_HIDDEN_LAYERS 4
+#define FC_CNF_MAX_WIDTH 64
+#define FC_CNF_LAYER_IGNORE 0
+#define FC_CNF_LAYER_CONCAT 1
+#define FC_CNF_LAYER_CONCAT_V2 2
+#define FC_CNF_LAYER_SQUASH 3
+#define FC_CNF_LAYER_CONCATSQUASH 4
+#define FC_CNF_ACT_TANH 0
+#define FC_CNF_ACT_RELU 1
+#define FC_CNF_ACT_SOFTPLUS 2      /* beta 1, threshold 20 */
+#define FC_CNF_ACT_ELU 3
+#define FC_CNF_ACT_SWISH 4         /* t sigmoid(t) */
+#define FC_CNF_ACT_SQUARE 5
+#define FC_CNF_ACT_IDENTITY 6
+#define FC_CNF_EULER 0
+#define FC_CNF_MIDPOINT 1
+#define FC_CNF_RK4 2
+int fc_cnf_field(const float* y, const float* image, float* dy, float* negdiv, float* evals, int64_t n, int32_t d,
+                 int32_t layers, const int32_t* hidden, int32_t layer_kind, int32_t activation, int32_t residual,
+                 float scale_output, float p0, int32_t image_floats, float t, const float* t_dev, void* stream);
+int fc_cnf_integrate(const float* z, const float* logp, const float* image, float* z_out, float* logp_out,
+                     float* evals, int64_t n, int32_t d, int32_t layers, const int32_t* hidden, int32_t layer_kind,
+                     int32_t activation, int32_t residual, float scale_output, float p0, int32_t image_floats,
+                     double t0, double t1, int32_t steps, int32_t method, void* stream);
 
 /* ---- batch-shared point-wise affine maps ---------------------------------------------------- */
 /* x, y viewed as [n, m] (m = elements of one batch item); scale/shift have 1 or m entries.
