@@ -1,7 +1,7 @@
 """``ODEnet`` (the dynamics network) and ``ODEfunc`` (dynamics plus divergence: the right-hand side of the CNF's
 augmented ODE); classes, constructor arguments and ``state_dict`` keys of flowcon/CNF/neural_odes/odefunc.py.
 
-Two routes for ``ODEfunc.forward``:
+Three routes for ``ODEfunc.forward``:
 
 * the torch composition: the net, then in eval mode the exact divergence from ``D`` backward passes, in training mode
   ``divergence_fn`` (Hutchinson's estimator with a noise vector fixed per solve, or the exact one).  Any device and
@@ -10,9 +10,16 @@ Two routes for ``ODEfunc.forward``:
   the kernel's limits (D <= 16, at most 4 hidden layers of at most 64 units, ignore / concat / concat_v2 / squash /
   concatsquash layers, no act_norm): ``fc_cnf_field`` computes the value and the exact forward-mode divergence in
   one launch, for batches up to the size at which it measured faster than the composition (``ops.cnf_rows_pay``;
-  DESIGN.md, "Continuous normalizing flows").
+  DESIGN.md, "Continuous normalizing flows");
+* with options ``cnf_training``, in training mode or wherever a gradient is needed, under the same conditions with at
+  most 3 hidden layers, two states and no gradient for ``t``: one autograd node of ``fc_cnf_field_train`` and
+  ``fc_cnf_field_backward`` (Hutchinson's estimate with the solve's noise, or the exact divergence), once
+  differentiable, for batches up to ``ops.CNF_TRAIN_MAX_LANES`` lanes ("CNF training").
 
 Only ``conv=False`` nets are built."""
+import contextlib
+import weakref
+
 import torch
 from torch import nn
 
@@ -134,6 +141,7 @@ class ODEfunc(nn.Module):
 
     def before_odeint(self, e=None):
         self._e = e
+        self._drop_training_image()
         self._num_evals.fill_(0)
 
     def num_evals(self):
@@ -166,7 +174,7 @@ class ODEfunc(nn.Module):
         return kind, act[0], act[1], tuple(widths[1:-1])
 
     def _use_kernels(self, y):
-        """The plan when this call can run on the kernels, else None."""
+        """The plan when this call can run on the eval-mode kernels, else None."""
         route = options.get("cnf_kernels")
         if not route or self.training or not isinstance(y, torch.Tensor):
             return None
@@ -174,14 +182,50 @@ class ODEfunc(nn.Module):
             return None
         if route != "force" and not ops.cnf_rows_pay(y.shape[0], y.shape[1]):
             return None     # measured slower than the composition ("Continuous normalizing flows")
-        params = ops.param_list(self)
-        if torch.is_grad_enabled() and (y.requires_grad or any(p.requires_grad for p in params)):
+        if self._needs_grad(y):
             return None
+        if any(m.training for m in ops.module_list(self)):
+            return None
+        return self._plan_for(y)
+
+    def _needs_grad(self, y):
+        return torch.is_grad_enabled() and (y.requires_grad or any(p.requires_grad for p in ops.param_list(self)))
+
+    def _use_training_kernels(self, t, states):
+        """``(plan, hutchinson)`` when this call can run as one ``fc_cnf_field_train`` / ``fc_cnf_field_backward``
+        node (options ``cnf_training``), else None: training mode or a gradient needed, no regulariser states (they
+        differentiate ``dy`` again), no gradient for ``t``, the eval kernels' conditions on the net and the rows, a
+        net within ``ops.cnf_train_supported`` and a batch within ``ops.CNF_TRAIN_MAX_LANES`` lanes."""
+        route = options.get("cnf_training")
+        y = states[0]
+        if not route or len(states) != 2 or not isinstance(y, torch.Tensor):
+            return None
+        if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
+            return None
+        if not (y.is_cuda and y.dtype == torch.float32 and y.dim() == 2 and y.shape[0] > 0 and y.is_contiguous()):
+            return None
+        if not (self.training or self._needs_grad(y)):
+            return None
+        hutchinson = self.training and self.divergence_fn is divergence_approx      # eval mode is always exact
+        if route != "force" and not ops.cnf_train_rows_pay(y.shape[0], y.shape[1], hutchinson):
+            return None     # no measured win over the composition (DESIGN.md, "CNF training")
+        e = self._e
+        if hutchinson and e is not None and not (
+                isinstance(e, torch.Tensor) and e.dtype == torch.float32 and e.device == y.device
+                and e.shape == y.shape and e.is_contiguous() and not e.requires_grad):
+            return None
+        plan = self._plan_for(y)
+        if plan is None or not ops.cnf_train_supported(y.shape[1], plan[3]):
+            return None
+        return plan, hutchinson
+
+    def _plan_for(self, y):
+        """The plan when the net, its parameters and the evaluation counter are what the kernels take for the float32
+        device rows ``y``, else None."""
+        params = ops.param_list(self)
         if any(p.dtype != torch.float32 or p.device != y.device for p in params) or ops.has_hooks(self):
             return None
         if self._num_evals.dtype != torch.float32 or self._num_evals.device != y.device:
-            return None
-        if any(m.training for m in ops.module_list(self)):
             return None
         net = self.diffeq
         structure = (id(net), len(getattr(net, "layers", ())), id(getattr(net, "activation_fns", None)),
@@ -198,9 +242,31 @@ class ODEfunc(nn.Module):
         """The packed net on the device, once per parameter version (torch ops on the device, no host sync)."""
         return ops.memo(self, "cnf_image", ops.cache_key(*ops.param_list(self)), lambda: self._pack_image(plan))
 
-    def _pack_image(self, plan):
+    def _training_image(self, plan):
+        """The packed net as a differentiable function of the parameters, one tensor per solve: every evaluation of
+        a solve hands its ``g_image`` to the same node, so the unpacking runs once per backward.  ``before_odeint``
+        drops it, and so does the first gradient that reaches it (a backward frees its graph): a later call packs
+        again."""
+        def build():
+            image, token, owner = self._pack_image(plan, differentiable=True), object(), weakref.ref(self)
+
+            def consumed(grad):
+                module = owner()
+                held = None if module is None else ops.cached(module, "cnf_training_image")
+                if held is not None and held[0] is token:
+                    module._drop_training_image()
+
+            image.register_hook(consumed)
+            return token, image
+
+        return ops.memo(self, "cnf_training_image", ops.cache_key(*ops.param_list(self)), build)[1]
+
+    def _drop_training_image(self):
+        self.__dict__.get("_fc_cache", {}).pop("cnf_training_image", None)
+
+    def _pack_image(self, plan, differentiable=False):
         kind, pieces = plan[0], []
-        with torch.no_grad():
+        with (contextlib.nullcontext() if differentiable else torch.no_grad()):
             for layer in self.diffeq.layers:
                 weight, bias = layer._layer.weight, layer._layer.bias
                 out = weight.shape[0]
@@ -251,7 +317,28 @@ class ODEfunc(nn.Module):
                         t = float(t)
                 dy, negdiv = ops.cnf_field(t, y, **self._kernel_args(plan))
                 return dy, negdiv.view(-1, 1)
+        route = self._use_training_kernels(t, states)
+        if route is not None:
+            return self._training_node(t, y, *route)
         return self._composition(t, states)
+
+    def _training_node(self, t, y, plan, hutchinson):
+        """One evaluation as one autograd node (one launch forward, one backward); without a gradient to carry, the
+        forward launch alone."""
+        if self.training and self._e is None:       # where, and by the call with which, the composition draws it
+            self._e = sample_rademacher_like(y) if self.rademacher else sample_gaussian_like(y)
+        if isinstance(t, torch.Tensor):
+            t = t.detach().reshape(1).to(device=y.device, dtype=torch.float32) if t.is_cuda else float(t)
+        e = self._e if hutchinson else None
+        kw = self._kernel_args(plan)
+        if not self._needs_grad(y):
+            dy, negdiv = ops.cnf_field_train(t, y, e, **kw)
+        else:
+            if torch.is_grad_enabled() and any(p.requires_grad for p in ops.param_list(self)):
+                kw["image"] = self._training_image(plan)
+            image = kw.pop("image")
+            dy, negdiv = ops._CnfFieldFunction.apply(y, image, e, t, kw)
+        return dy, negdiv.view(-1, 1)
 
     def _composition(self, t, states):
         y = states[0]

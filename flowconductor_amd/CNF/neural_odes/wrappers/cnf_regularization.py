@@ -2,6 +2,8 @@
 import torch
 from torch import nn
 
+from flowconductor_amd import options
+
 from ..util import _get_minibatch_jacobian
 
 
@@ -24,7 +26,8 @@ class RegularizedODEfunc(nn.Module):
         class SharedContext:        # the Jacobian, computed once for the functions that share it
             pass
 
-        with torch.enable_grad():
+        # the regularisers differentiate dx again: the once-differentiable training kernels step aside
+        with torch.enable_grad(), options.override(cnf_training=False):
             x, logp = state[:2]
             if not x.requires_grad:
                 x = x.detach().requires_grad_(True)

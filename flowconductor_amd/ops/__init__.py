@@ -87,6 +87,9 @@ from .cnf import (  # noqa: F401
     CNF_EULER, CNF_KERNEL_MAX_LANES, CNF_LAYER_CONCAT, CNF_LAYER_CONCATSQUASH, CNF_LAYER_CONCAT_V2, CNF_LAYER_IGNORE, CNF_LAYER_SQUASH,
     CNF_MAX_DIM, CNF_MAX_HIDDEN_LAYERS, CNF_MAX_WIDTH, CNF_METHODS, CNF_MIDPOINT, CNF_RK4, CNF_STAGES, _cnf_operands,
     _cnf_pad4, cnf_field, cnf_group_lanes, cnf_image_floats, cnf_integrate, cnf_rows_pay, cnf_supported)
+from .cnf import (  # noqa: F401
+    CNF_BACKWARD_MAX_BLOCKS, CNF_DOUBLE_BACKWARD_MSG, CNF_TRAIN_MAX_HIDDEN_LAYERS, CNF_TRAIN_MAX_LANES, _CnfFieldFunction, cnf_backward_rows,
+    cnf_field_backward, cnf_field_train, cnf_train_lanes, cnf_train_rows_pay, cnf_train_supported)
 from .umnn import (  # noqa: F401
     UMNN_DOUBLE_BACKWARD_MSG, UMNN_MAX_COND, UMNN_MAX_HIDDEN_LAYERS, UMNN_MAX_STEPS, UMNN_MAX_WIDTH, UMNN_POINTS,
     _UMNNFunction, pack_umnn, pack_umnn_backward, umnn, umnn_autograd, umnn_backward, umnn_backward_image, umnn_fits,

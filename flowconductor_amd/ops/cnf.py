@@ -1,4 +1,5 @@
-"""Continuous normalizing flows (eval mode): one ODE-function evaluation, or a whole fixed-step solve, per launch."""
+"""Continuous normalizing flows: one ODE-function evaluation, or a whole fixed-step solve, per launch (eval mode), and
+one evaluation as an autograd node of one forward and one backward launch (training)."""
 import ctypes
 
 import torch
@@ -120,3 +121,136 @@ def cnf_integrate(inputs, logp, image, d, hidden, layer_kind, activation, t0, t1
           int(bool(residual)), float(scale_output), float(p0), image.numel(), float(t0), float(t1), int(steps),
           int(method), _hip.stream_ptr(z.device))
     return z_out, logp_out
+
+
+# ---- training: fc_cnf_field_train / fc_cnf_field_backward ------------------------------------------------------------
+CNF_TRAIN_MAX_HIDDEN_LAYERS = 3
+CNF_BACKWARD_MAX_BLOCKS = 256      # the backward launch's grid cap: beyond it a block walks over several row tiles
+CNF_DOUBLE_BACKWARD_MSG = (
+    "flowconductor_amd: the CNF kernel route (options 'cnf_training') is once differentiable; for a gradient of a "
+    "gradient (create_graph=True, the regularisers) run the solve with options.override(cnf_training=False), the torch "
+    "composition")
+
+# A row occupies 2 lanes under Hutchinson's estimator (the value stream and one tangent) and ``cnf_group_lanes(d)`` with
+# the exact divergence.  The dispatch takes the training kernels up to this many lanes: the largest measured size at
+# which a training step beat the composition in BOTH divergence modes (tools/probe/bench_cnf_training.py; DESIGN.md,
+# "CNF training": every measured shape up to 2^14 lanes won, 1.8x to 2.8x; at 2^15 lanes D = 16 under Hutchinson lost).
+CNF_TRAIN_MAX_LANES = 1 << 14
+
+
+def cnf_train_supported(d, hidden):
+    """Whether ``fc_cnf_field_train`` / ``fc_cnf_field_backward`` take a net ``d -> hidden... -> d``: the forward
+    kernels' limits with at most three hidden layers (the backward keeps every layer's input of a lane in LDS)."""
+    return cnf_supported(d, hidden) and len(hidden) <= CNF_TRAIN_MAX_HIDDEN_LAYERS
+
+
+def cnf_train_lanes(n, d, hutchinson):
+    """Lanes ``n`` rows of ``d`` features occupy in the training kernels."""
+    return n * (2 if hutchinson else cnf_group_lanes(d))
+
+
+def cnf_train_rows_pay(n, d, hutchinson):
+    """Whether ``cnf_training=True`` sends a batch of ``n`` rows to the training kernels."""
+    return cnf_train_lanes(n, d, hutchinson) <= CNF_TRAIN_MAX_LANES
+
+
+def _cnf_train_operands(rows, e, image, d, hidden, layer_kind, activation, evals):
+    y, image, hidden, widths = _cnf_operands(rows, image, d, hidden, layer_kind, activation, evals)
+    if not cnf_train_supported(d, hidden):
+        raise ValueError("flowconductor_amd: the CNF training kernels take at most %d hidden layers"
+                         % CNF_TRAIN_MAX_HIDDEN_LAYERS)
+    if e is not None:
+        if not (isinstance(e, torch.Tensor) and e.dtype == torch.float32 and e.device == y.device
+                and e.shape == y.shape and e.is_contiguous()):
+            raise ValueError("flowconductor_amd: e must be contiguous float32 [N, D] on the device of the rows")
+    return y, image, hidden, widths
+
+
+def _cnf_time(t, y):
+    if isinstance(t, torch.Tensor):
+        if t.numel() != 1 or t.dtype != torch.float32 or t.device != y.device:
+            raise ValueError("flowconductor_amd: t must be a number or one float32 element on the device of the rows")
+        return 0.0, t
+    return float(t), None
+
+
+def cnf_backward_rows(d, hidden, hutchinson):
+    """Rows one block of ``fc_cnf_field_backward`` carries (its sums over rows are per block, then over blocks)."""
+    lib = _hip.load()
+    hidden = tuple(int(h) for h in hidden)
+    widths = (ctypes.c_int32 * max(1, len(hidden)))(*hidden)
+    rows = lib.fc_cnf_field_backward_rows(d, len(hidden) + 1, widths, int(bool(hutchinson)))
+    if rows < 1:
+        raise ValueError("flowconductor_amd: cnf_backward_rows: outside the kernel's limits")
+    return rows
+
+
+def cnf_field_train(t, inputs, e, image, d, hidden, layer_kind, activation, residual=False, scale_output=1.0, p0=1.0,
+                    evals=None):
+    """``(dy [N, d], -div [N])`` as ``cnf_field``, one launch: with ``e`` (float32 ``[N, d]``) the divergence is
+    Hutchinson's estimate ``e^T (df/dy) e``, with None the exact one.  No autograd (``_CnfFieldFunction`` has it)."""
+    _hip.require_no_grad(inputs)
+    lib = _hip.load()
+    y, image, hidden, widths = _cnf_train_operands(inputs, e, image, d, hidden, layer_kind, activation, evals)
+    t_host, t_dev = _cnf_time(t, y)
+    n = y.shape[0]
+    dy = torch.empty_like(y)
+    negdiv = torch.empty(n, dtype=torch.float32, device=y.device)
+    _call("fc_cnf_field_train", lib.fc_cnf_field_train, y.device, _hip.ptr(y), _hip.ptr(e), _hip.ptr(image), _hip.ptr(dy),
+          _hip.ptr(negdiv), _hip.ptr(evals), n, d, len(hidden) + 1, widths, layer_kind, activation, int(bool(residual)),
+          float(scale_output), float(p0), image.numel(), t_host, _hip.ptr(t_dev), _hip.stream_ptr(y.device))
+    return dy, negdiv
+
+
+def cnf_field_backward(t, inputs, e, image, g_dy, g_negdiv, d, hidden, layer_kind, activation, residual=False,
+                       scale_output=1.0, p0=1.0):
+    """The raw ``fc_cnf_field_backward``: ``(g_y [N, d], g_image [image floats])`` of ``sum(g_dy * dy) + sum(g_negdiv *
+    negdiv)`` for the outputs of ``cnf_field_train`` at the same arguments; ``g_image`` in the image's layout, summed
+    over the rows in a fixed order (bitwise reproducible)."""
+    lib = _hip.load()
+    y, image, hidden, widths = _cnf_train_operands(inputs, e, image, d, hidden, layer_kind, activation, None)
+    t_host, t_dev = _cnf_time(t, y)
+    n = y.shape[0]
+    g_dy = _hip.dev_f32(g_dy, "g_dy")
+    g_negdiv = _hip.dev_f32(g_negdiv, "g_negdiv")
+    if g_dy.shape != y.shape or g_negdiv.numel() != n or g_dy.device != y.device or g_negdiv.device != y.device:
+        raise ValueError("flowconductor_amd: cnf_field_backward: g_dy / g_negdiv do not belong to the rows")
+    with torch.cuda.device(y.device):
+        floats = lib.fc_cnf_field_backward_workspace(n, d, len(hidden) + 1, widths, int(e is not None))
+    if floats < 0:
+        raise ValueError("flowconductor_amd: cnf_field_backward: outside the kernel's limits")
+    workspace = torch.empty(max(floats // 2, 1), dtype=torch.float64, device=y.device)
+    g_y = torch.empty_like(y)
+    g_image = torch.empty_like(image)
+    _call("fc_cnf_field_backward", lib.fc_cnf_field_backward, y.device, _hip.ptr(y), _hip.ptr(e), _hip.ptr(image),
+          _hip.ptr(g_dy), _hip.ptr(g_negdiv), _hip.ptr(g_y), _hip.ptr(g_image), _hip.ptr(workspace), n, d,
+          len(hidden) + 1, widths, layer_kind, activation, int(bool(residual)), float(scale_output), float(p0),
+          image.numel(), t_host, _hip.ptr(t_dev), _hip.stream_ptr(y.device))
+    return g_y, g_image
+
+
+class _CnfFieldFunction(torch.autograd.Function):
+    """``fc_cnf_field_train`` with ``fc_cnf_field_backward`` over ``(y, image)``: saves the inputs alone, the backward
+    recomputes the forward in its kernel.  ``e`` and ``t`` get no gradient.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, y, image, e, t, kw):
+        dy, negdiv = cnf_field_train(t, y, e, image=image, **kw)
+        ctx.kw = {k: v for k, v in kw.items() if k != "evals"}
+        ctx.t = t
+        ctx.save_for_backward(_prep_2d(y), image, e)
+        return dy, negdiv
+
+    @staticmethod
+    def backward(ctx, g_dy, g_negdiv):
+        if torch.is_grad_enabled():
+            raise RuntimeError(CNF_DOUBLE_BACKWARD_MSG)
+        return _CnfFieldFunction._backward_once(ctx, g_dy, g_negdiv)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _backward_once(ctx, g_dy, g_negdiv):
+        y, image, e = ctx.saved_tensors
+        g_y, g_image = cnf_field_backward(ctx.t, y, e, image, g_dy.contiguous(), g_negdiv.contiguous(), **ctx.kw)
+        need = ctx.needs_input_grad
+        return g_y if need[0] else None, g_image if need[1] else None, None, None, None

@@ -45,6 +45,17 @@ _DEFAULTS = {
     # fixed-step solves in fc_cnf_integrate (one launch per solve) instead of the torch composition, for batches up to
     # ops.CNF_KERNEL_MAX_LANES lanes; "force" takes them at any batch size (measurements), False never
     "cnf_kernels": True,
+    # continuous normalizing flows in training mode, and any evaluation that needs a gradient: one autograd node of
+    # fc_cnf_field_train + fc_cnf_field_backward per evaluation of the ODE function instead of the torch composition
+    # and its double backward, for batches up to ops.CNF_TRAIN_MAX_LANES lanes; "force" takes them at any batch
+    # size (measurements, tests), False never.  Off by default: tests pin the default training route to the composition
+    # ("CNF training", has the measured training steps).
+    "cnf_training": False,
+}
+
+# options that take a few named values only: anything else is a mistake at the call site
+_CHOICES = {
+    "cnf_training": (False, True, "force"),
 }
 
 _values = dict(_DEFAULTS)
@@ -64,6 +75,10 @@ def override(**kw):
     unknown = set(kw) - set(_DEFAULTS)
     if unknown:
         raise KeyError("unknown option(s): %s" % ", ".join(sorted(unknown)))
+    for name, value in kw.items():
+        if name in _CHOICES and not any(value is choice or (isinstance(value, str) and value == choice)
+                                        for choice in _CHOICES[name]):
+            raise ValueError("option %s takes one of %r, got %r" % (name, _CHOICES[name], value))
     saved = {k: _values[k] for k in kw}
     _values.update(kw)
     try:

@@ -627,6 +627,32 @@ int fc_cnf_integrate(const float* z, const float* logp, const float* image, floa
                      int32_t activation, int32_t residual, float scale_output, float p0, int32_t image_floats,
                      double t0, double t1, int32_t steps, int32_t method, void* stream);
 
+/* Training: one evaluation of the ODE function as an autograd node (same net description as above, at most
+ * FC_CNF_TRAIN_MAX_HIDDEN_LAYERS hidden layers; hipErrorInvalidValue otherwise).
+ * fc_cnf_field_train     e NULL: fc_cnf_field's kernel (the exact divergence).  e float32 [n, d]: Hutchinson's estimate
+ *           negdiv = -(scale_output e^T (d net / dy) e  (- d with residual)) from a group of 2 lanes per row, the
+ *           value stream and one tangent stream seeded with e.  Adds 1 to *evals.
+ * fc_cnf_field_backward  from g_dy [n, d] and g_negdiv [n], the forward recomputed in the kernel: g_y [n, d] and
+ *           g_image [image_floats], the gradient of every image entry in the image's own layout (padding entries
+ *           zero; the vectors a layer kind does not have receive the gradient their zeros would have).  e as in the
+ *           forward call; it gets no gradient.  The sums over rows are float64, in a fixed order inside a block, then
+ *           over the blocks' partial images in block order (a second kernel): no atomics, bitwise reproducible.
+ *           workspace: at least fc_cnf_field_backward_workspace(...) floats, 8-byte aligned.
+ * fc_cnf_field_backward_rows       rows a block of the backward kernel carries (-1 outside the limits)
+ * fc_cnf_field_backward_workspace  floats of workspace for n rows (-1 outside the limits) */
+#define FC_CNF_TRAIN_MAX_HIDDEN_LAYERS 3
+int fc_cnf_field_train(const float* y, const float* e, const float* image, float* dy, float* negdiv, float* evals,
+                       int64_t n, int32_t d, int32_t layers, const int32_t* hidden, int32_t layer_kind,
+                       int32_t activation, int32_t residual, float scale_output, float p0, int32_t image_floats,
+                       float t, const float* t_dev, void* stream);
+int fc_cnf_field_backward(const float* y, const float* e, const float* image, const float* g_dy,
+                          const float* g_negdiv, float* g_y, float* g_image, void* workspace, int64_t n, int32_t d,
+                          int32_t layers, const int32_t* hidden, int32_t layer_kind, int32_t activation,
+                          int32_t residual, float scale_output, float p0, int32_t image_floats, float t,
+                          const float* t_dev, void* stream);
+int fc_cnf_field_backward_rows(int32_t d, int32_t layers, const int32_t* hidden, int32_t with_e);
+int fc_cnf_field_backward_workspace(int64_t n, int32_t d, int32_t layers, const int32_t* hidden, int32_t with_e);
+
 /* ---- batch-shared point-wise affine maps ---------------------------------------------------- */
 /* x, y viewed as [n, m] (m = elements of one batch item); scale/shift have 1 or m entries.
  * mode 0: y = x*scale + shift                    (standard.py:54-60, normalization.py:171-187)
