@@ -36,6 +36,25 @@ struct SoSBwdArgs {
 };
 
 
+// sigmoid(v) and 1 - sigmoid(v) = sigmoid(-v), both to the relative accuracy of sigmoid_lean (s is sigmoid_lean(v) bit for
+// bit).  1.f - s from the rounded s keeps an absolute error of 2^-24: relative 1e-3 at v = 10, and every derivative below
+// is a multiple of s (1 - s).
+__device__ __forceinline__ void sigmoid_both(float v, float& s, float& c) {
+  const float e = exp_lean(-fabsf(v));
+  const float r = div_lean(1.f, 1.f + e);
+  const float er = e * r;
+  s = v >= 0.f ? r : er;
+  c = v >= 0.f ? er : r;
+}
+
+// 1 - tanh(v)^2 = 4 e / (1 + e)^2 with e = exp(-2 |v|), to the relative accuracy of the primitives (1.f - th * th from the
+// rounded th is tens of percent off at |v| = 8).
+__device__ __forceinline__ float sech2_lean(float v) {
+  const float e = exp_lean(-2.f * fabsf(v));
+  const float r = div_lean(1.f, 1.f + e);
+  return 4.f * e * (r * r);
+}
+
 // One element: r -> the P raw values, g -> where the P gradients go (may alias r: every slot is read before it is
 // written, except the softmax logits, whose probabilities are kept in `sm` [S] until the last loop).  Returns grad_x.
 // kSmKept: `sm` is storage of its own (kept to the end); otherwise it IS g's logit slots and the last loop recomputes.
@@ -60,36 +79,41 @@ __device__ __forceinline__ float sos_backward_element(const SoSBwdArgs& a, const
     const float sk = 10.f * tanh_lean(r[k]);
     const float al = 0.1f + 9.9f * sigmoid_lean(r[S + k]);
     const float w = a.post * ((sm[k] * rz + 1e-6f) * rtot);
-    const float sg = sigmoid_lean(al * (x - sk));
+    float sg, cg;
+    sigmoid_both(al * (x - sk), sg, cg);
     ynum += w * sg;
-    dsos += w * al * (sg * (1.f - sg));
+    dsos += w * al * (sg * cg);
     wsum += w;
   }
   const float rw = div_lean(1.f, wsum);
   const float ysos = ynum * rw;
   const float sh = softplus_lean(r[3 * S], 1.f) + 0.1f;
-  const float su = sigmoid_lean(x - sh), sv = sigmoid_lean(-(x + sh));
+  float su, cu, sv, cv;
+  sigmoid_both(x - sh, su, cu);
+  sigmoid_both(-(x + sh), sv, cv);
   const float desp = su + sv;
   const float gD = gl * div_lean(1.f, dsos + desp);       // d lad / d D_sos = d lad / d D_esp
-  const float dsu = su * (1.f - su), dsv = sv * (1.f - sv);
+  const float dsu = su * cu, dsv = sv * cv;
   // pass 3: per-sigmoid adjoints; the gradient of the normalised weight n_k is parked in the logit slot
   float gxs = 0.f, gn_n = 0.f, gn_sm = 0.f;
   for (int k = 0; k < S; ++k) {
     const float th = tanh_lean(r[k]);
     const float sk = 10.f * th;
-    const float sb = sigmoid_lean(r[S + k]);
+    float sb, cb;
+    sigmoid_both(r[S + k], sb, cb);
     const float al = 0.1f + 9.9f * sb;
     const float smk = sm[k] * rz;
     const float nk = (smk + 1e-6f) * rtot;
     const float w = a.post * nk;
-    const float sg = sigmoid_lean(al * (x - sk));
-    const float d1 = sg * (1.f - sg);
-    const float g_pre = gy * (w * d1 * rw) + gD * (w * al * d1 * (1.f - 2.f * sg));
+    float sg, cg;
+    sigmoid_both(al * (x - sk), sg, cg);
+    const float d1 = sg * cg;
+    const float g_pre = gy * (w * d1 * rw) + gD * (w * al * d1 * (cg - sg));
     const float g_al = g_pre * (x - sk) + gD * (w * d1);
     const float g_w = gy * ((sg - ysos) * rw) + gD * (al * d1);
     gxs += g_pre * al;
-    g[k] = (-g_pre * al) * (10.f * (1.f - th * th));           // d s / d a = 10 (1 - tanh^2)
-    g[S + k] = g_al * (9.9f * sb * (1.f - sb));                 // d alpha / d b
+    g[k] = (-g_pre * al) * (10.f * sech2_lean(r[k]));          // d s / d a = 10 (1 - tanh^2)
+    g[S + k] = g_al * (9.9f * sb * cb);                         // d alpha / d b
     const float g_n = a.post * g_w;                             // w = post n
     g[2 * S + k] = g_n;
     gn_n += g_n * nk;
@@ -104,7 +128,7 @@ __device__ __forceinline__ float sos_backward_element(const SoSBwdArgs& a, const
   }
   // extended softplus: y_esp = sp(x - sh) - sp(-(x + sh)),  D_esp = su + sv
   const float g_sh = gy * (sv - su) - gD * (dsu + dsv);
-  g[3 * S] = g_sh * (1.f - exp_lean(-(sh - 0.1f)));              // d sh / d e = sigmoid(e) = 1 - exp(-softplus(e))
+  g[3 * S] = g_sh * sigmoid_lean(r[3 * S]);                       // d sh / d e = sigmoid(e)
   return gxs + gy * desp + gD * (dsu - dsv);
 }
 

@@ -11,6 +11,7 @@ from ._core import LAD_STORE, _as_cols, _call, _err_word, _finish, _prep_2d, rq_
 DEFAULT_MIN_BIN_WIDTH = 1e-3
 DEFAULT_MIN_BIN_HEIGHT = 1e-3
 DEFAULT_MIN_DERIVATIVE = 1e-3
+RQ_BACKWARD_MAX_BINS = 32      # kMaxBinsBwd of csrc/fc_rq_backward_op.h
 
 
 def _rq_config(num_bins, tails, tail_bound, box, min_bin_width, min_bin_height, min_derivative,
@@ -149,6 +150,9 @@ def rq_spline_autograd(inputs, params, cols=None, **kw):
     if kw.get("shared_params"):
         raise RuntimeError("flowconductor_amd: gradients are implemented for the RQ spline with per-sample "
                            "parameters; wrap other calls in torch.no_grad().")
+    if kw["num_bins"] > RQ_BACKWARD_MAX_BINS:
+        raise NotImplementedError("autograd through the RQ spline needs num_bins <= %d (fc_rq_spline_backward); got "
+                                  "num_bins = %d" % (RQ_BACKWARD_MAX_BINS, kw["num_bins"]))
     if kw.get("inverse"):
         fwd_kw = dict(kw, inverse=False)
         return _inverse_through_forward(lambda y, p: _RQSplineFunction.apply(y, p, cols, fwd_kw),

@@ -25,18 +25,25 @@ class _SoSFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_outputs, grad_logabsdet):
         inputs, raw_params = ctx.saved_tensors
-        lib = _hip.load()
-        x = _prep_2d(inputs.detach())
-        p = _hip.dev_f32(raw_params.detach(), "raw_params")
-        gy = _hip.dev_f32(grad_outputs if grad_outputs is not None else torch.zeros_like(x), "grad_outputs")
-        gl = None if grad_logabsdet is None else _hip.dev_f32(grad_logabsdet, "grad_logabsdet")
-        n, d = x.shape
-        gx = torch.empty_like(x)
-        gp = torch.empty_like(p)
-        _call("fc_sum_of_sigmoids_backward", lib.fc_sum_of_sigmoids_backward, x.device, _hip.ptr(x), _hip.ptr(p),
-              _hip.ptr(gy), _hip.ptr(gl), _hip.ptr(gx), _hip.ptr(gp), n, d, ctx.n_sigmoids, float(ctx.log_post),
-              _hip.stream_ptr(x.device))
-        return gx, gp.view_as(raw_params), None, None, None
+        gx, gp = sum_of_sigmoids_backward(inputs, raw_params, grad_outputs, grad_logabsdet, ctx.n_sigmoids, ctx.log_post)
+        return gx, gp, None, None, None
+
+
+def sum_of_sigmoids_backward(inputs, raw_params, grad_outputs, grad_logabsdet, n_sigmoids, log_scale_postact=0.0):
+    """Gradients of ``sum_of_sigmoids(inputs, raw_params, n_sigmoids)`` (forward direction, per-sample rows):
+    ``(grad_inputs [N, D], grad_raw_params)``; ``grad_outputs`` / ``grad_logabsdet`` may be None (zeros)."""
+    lib = _hip.load()
+    x = _prep_2d(inputs.detach())
+    p = _hip.dev_f32(raw_params.detach(), "raw_params")
+    gy = _hip.dev_f32(grad_outputs if grad_outputs is not None else torch.zeros_like(x), "grad_outputs")
+    gl = None if grad_logabsdet is None else _hip.dev_f32(grad_logabsdet, "grad_logabsdet")
+    n, d = x.shape
+    gx = torch.empty_like(x)
+    gp = torch.empty_like(p)
+    _call("fc_sum_of_sigmoids_backward", lib.fc_sum_of_sigmoids_backward, x.device, _hip.ptr(x), _hip.ptr(p),
+          _hip.ptr(gy), _hip.ptr(gl), _hip.ptr(gx), _hip.ptr(gp), n, d, n_sigmoids, float(log_scale_postact),
+          _hip.stream_ptr(x.device))
+    return gx, gp.view_as(raw_params)
 
 
 def sum_of_sigmoids_autograd(inputs, raw_params, n_sigmoids, inverse=False, offset=0.0, iterations=50, lim=120.0,
