@@ -8,12 +8,17 @@ well as in training mode (a fixed-step ``test_solver`` is of little use without 
 Routes of ``CNF.forward`` in eval mode, for an ``odefunc`` the kernels take (see ``ODEfunc``) and two integration
 times:
 * ``test_solver`` in ``euler`` / ``midpoint`` / ``rk4``: the whole solve is one ``fc_cnf_integrate`` launch;
-* ``dopri5``: the host loop of ``odeint`` with one ``fc_cnf_field`` launch per evaluation.
+* ``dopri5``: the host loop of ``odeint`` with one ``fc_cnf_field`` launch per evaluation, the batch judged as one
+  system;
+* ``dopri5`` with options ``cnf_dopri5_kernel`` (off by default), tolerances of at least 1e-6 and a batch within
+  ``ops.cnf_dopri5_rows_pay``: the whole adaptive solve is one ``fc_cnf_dopri5`` launch in which every row controls
+  its own step (a row is judged by its own error, and one that cannot finish within ``max_num_steps``, clipped to
+  4096, attempts returns NaN where the host loop raises).
 Everything else is the torch composition on the tensors' device."""
 import torch
 from torch import nn
 
-from flowconductor_amd import ops
+from flowconductor_amd import ops, options
 from flowconductor_amd.transforms.base import Transform
 
 from .neural_odes.odefunc import ODEfunc
@@ -56,9 +61,12 @@ class CNF(nn.Module):
         return [0.0, value]
 
     def _kernel_solve(self, z, logpz, times):
-        """``(z_t, logp_t)`` from one ``fc_cnf_integrate`` launch, or None when this call is not one for it."""
+        """``(z_t, logp_t)`` from one ``fc_cnf_integrate`` or ``fc_cnf_dopri5`` launch, or None when this call is not
+        one for them."""
         method = ops.CNF_METHODS.get(self.test_solver)
-        if self.training or method is None or len(times) != 2 or any(isinstance(v, torch.Tensor) for v in times):
+        adaptive = method is None and self.test_solver == "dopri5" and bool(options.get("cnf_dopri5_kernel"))
+        if self.training or not (adaptive or method is not None) or len(times) != 2 \
+                or any(isinstance(v, torch.Tensor) for v in times):
             return None
         func = self.odefunc.odefunc if isinstance(self.odefunc, RegularizedODEfunc) else self.odefunc
         if type(func) is not ODEfunc or ops.has_hooks(self):
@@ -70,9 +78,31 @@ class CNF(nn.Module):
         plan = func._use_kernels(z)
         if plan is None:
             return None
+        if adaptive:
+            return self._dopri5_solve(func, plan, z, logpz, times)
         steps = fixed_grid_steps(times[0], times[1], self.solver_options)
         z_t, logp_t = ops.cnf_integrate(z, logpz, t0=times[0], t1=times[1], steps=steps, method=method,
                                         **func._kernel_args(plan))
+        return z_t, logp_t.view(logpz.shape)
+
+    def _dopri5_solve(self, func, plan, z, logpz, times):
+        """The adaptive solve in one ``fc_cnf_dopri5`` launch (options ``cnf_dopri5_kernel``), or None: tolerances
+        below ``ops.CNF_DOPRI5_MIN_TOL``, a batch beyond ``ops.cnf_dopri5_rows_pay`` (unless the option is "force"),
+        or solver options the kernel has no argument for keep the host loop."""
+        tolerances = (self.test_atol, self.test_rtol)
+        if not all(isinstance(v, (int, float)) for v in tolerances) \
+                or not ops.cnf_dopri5_fits(z.shape[1], plan[3], *tolerances):
+            return None
+        if options.get("cnf_dopri5_kernel") != "force" and not ops.cnf_dopri5_rows_pay(z.shape[0], z.shape[1]):
+            return None     # no measured win over the host loop (DESIGN.md, "dopri5 in one launch")
+        first_step = self.solver_options.get("first_step")
+        if first_step is not None and not (isinstance(first_step, (int, float)) and 0.0 < first_step < float("inf")):
+            return None
+        max_attempts = ops.cnf_dopri5_attempts(self.solver_options.get("max_num_steps"))
+        if max_attempts is None:
+            return None
+        z_t, logp_t, _ = ops.cnf_dopri5(z, logpz, t0=times[0], t1=times[1], atol=tolerances[0], rtol=tolerances[1],
+                                        first_step=first_step, max_attempts=max_attempts, **func._kernel_args(plan))
         return z_t, logp_t.view(logpz.shape)
 
     def forward(self, z, logpz=None, integration_times=None, reverse=False):

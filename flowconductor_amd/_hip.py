@@ -168,6 +168,8 @@ SIGNATURES = {
     "fc_cnf_field": [_P] * 5 + [_I64, _I32, _I32, _P, _I32, _I32, _I32, _F, _F, _I32, _F, _P, _P],
     "fc_cnf_integrate": [_P] * 6 + [_I64, _I32, _I32, _P, _I32, _I32, _I32, _F, _F, _I32, ctypes.c_double,
                                     ctypes.c_double, _I32, _I32, _P],
+    "fc_cnf_dopri5": [_P] * 7 + [_I64, _I32, _I32, _P, _I32, _I32, _I32, _F, _F, _I32] + [ctypes.c_double] * 5
+                     + [_I32, _P],
     "fc_cnf_field_train": [_P] * 6 + [_I64, _I32, _I32, _P, _I32, _I32, _I32, _F, _F, _I32, _F, _P, _P],
     "fc_cnf_field_backward": [_P] * 8 + [_I64, _I32, _I32, _P, _I32, _I32, _I32, _F, _F, _I32, _F, _P, _P],
     "fc_cnf_field_backward_rows": [_I32, _I32, _P, _I32],

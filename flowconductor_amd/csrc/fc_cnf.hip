@@ -6,6 +6,8 @@
 //                      Runge-Kutta method, every row on its own                                            one launch
 //   fc_cnf_field_train / fc_cnf_field_backward   one evaluation as an autograd node: the exact divergence or
 //                      Hutchinson's estimate, and the gradients of both outputs (further down)
+// (fc_cnf_dopri5, the adaptive solve with per-row step control, is in fc_cnf_dopri5.hip; what the kernels share --
+// CnfShape, the activations, cnf_time_table, cnf_net, cnf_field_row -- is in fc_cnf.h.)
 //
 // f is an MLP whose layers all reduce to
 //     pre = W x + b + w_t t,   out = pre * gate + w_b t,   gate = sigmoid(w_g t + b_g)  or  1
@@ -28,201 +30,9 @@
 // Numerics: sums in float64 over the float32 weights, a stored activation rounded to float32 once (cnf_net is the
 // one place that decides this); the integrator keeps (z, logp) and the stage slopes in float64 registers and rounds
 // a stage's state to float32 where it enters the net.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "../../include/flowcon_hip.h"
-#include "fc_device.h"
+#include "fc_cnf.h"
 
 namespace fc {
-
-struct CnfShape {
-  int d, layers, act, gated, residual;
-  int w[FC_CNF_MAX_HIDDEN_LAYERS + 2];  // w[0] = d, hidden widths, w[layers] = d
-  double scale, p0;
-};
-
-__host__ __device__ inline int cnf_pad4(int v) { return (v + 3) & ~3; }
-
-__host__ __device__ inline int cnf_image_floats(const CnfShape& sh) {
-  int total = 0;
-  for (int l = 0; l < sh.layers; ++l) total += (5 + sh.w[l]) * cnf_pad4(sh.w[l + 1]);
-  return total;
-}
-
-__host__ __device__ inline int cnf_table_doubles(const CnfShape& sh) {
-  int total = 0;
-  for (int l = 0; l < sh.layers; ++l) total += 3 * cnf_pad4(sh.w[l + 1]);
-  return total;
-}
-
-__host__ __device__ inline int cnf_max_width(const CnfShape& sh) {
-  int m = sh.d;
-  for (int l = 1; l < sh.layers; ++l) m = sh.w[l] > m ? sh.w[l] : m;
-  return m;
-}
-
-// value and derivative of the activation, in float64 on the float64 pre-activation
-__device__ __forceinline__ void cnf_act(int act, double x, double p0, double& f, double& df) {
-  switch (act) {
-    case FC_CNF_ACT_TANH: {
-      const double th = tanh(x);
-      f = th;
-      df = 1.0 - th * th;
-      break;
-    }
-    case FC_CNF_ACT_RELU:
-      f = x > 0.0 ? x : 0.0;
-      df = x > 0.0 ? 1.0 : 0.0;
-      break;
-    case FC_CNF_ACT_SOFTPLUS: {  // beta 1, threshold 20 as torch evaluates it
-      const double sg = 1.0 / (1.0 + exp(-x));
-      f = x > 20.0 ? x : log1p(exp(x));
-      df = x > 20.0 ? 1.0 : sg;
-      break;
-    }
-    case FC_CNF_ACT_ELU:
-      f = x > 0.0 ? x : p0 * expm1(x);
-      df = x > 0.0 ? 1.0 : p0 * exp(x);
-      break;
-    case FC_CNF_ACT_SWISH: {
-      const double sg = 1.0 / (1.0 + exp(-x));
-      f = x * sg;
-      df = sg + x * sg * (1.0 - sg);
-      break;
-    }
-    case FC_CNF_ACT_SQUARE:
-      f = x * x;
-      df = 2.0 * x;
-      break;
-    default:
-      f = x;
-      df = 1.0;
-      break;
-  }
-}
-
-// What depends on t alone, per layer [b + w_t t | gate | w_b t], each op doubles.  The whole block takes part; the
-// caller puts barriers round it.
-__device__ __forceinline__ void cnf_time_table(const float* img, double* tab, const CnfShape& sh, double t, int tid,
-                                               int T) {
-  const float* p = img;
-  double* q = tab;
-  for (int l = 0; l < sh.layers; ++l) {
-    const int op = cnf_pad4(sh.w[l + 1]);
-    for (int o = tid; o < op; o += T) {
-      q[o] = (double)p[o] + (double)p[op + o] * t;
-      q[op + o] = sh.gated ? 1.0 / (1.0 + exp(-((double)p[2 * op + o] * t + (double)p[3 * op + o]))) : 1.0;
-      q[2 * op + o] = (double)p[4 * op + o] * t;
-    }
-    p += (5 + sh.w[l]) * op;
-    q += 3 * op;
-  }
-}
-
-// ---- the net on one stream -------------------------------------------------------------------------------------------
-
-// Runs the layers on the state column `mine` (stride T, the second buffer `half` floats further on), whose first d
-// entries the caller has set: the input (value stream, s == 0) or a unit tangent (s >= 1).  out[i], i < DP: the last
-// layer in unrounded float64 -- f in the value stream, column s - 1 of df/dy in stream s.  This is the one place that
-// fixes where float32 roundings happen: a stored activation, once.
-template <int G, int DP>
-__device__ __forceinline__ void cnf_net(const float* img, const double* tab, float* mine, int T, int half,
-                                        const CnfShape& sh, int s, double (&out)[DP]) {
-  const bool value = s == 0;
-  const float* p = img;
-  const double* q = tab;
-  float* cur = mine;
-  float* nxt = mine + half;
-  for (int l = 0; l + 1 < sh.layers; ++l) {
-    const int in = sh.w[l], width = sh.w[l + 1], op = cnf_pad4(width);
-    const float* wt = p + 5 * op;
-    for (int o = 0; o < op; o += 4) {
-      double sum[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) sum[c] = value ? q[o + c] : 0.0;  // a tangent has no bias and no time terms
-      for (int k = 0; k < in; ++k) {
-        const double v = (double)cur[k * T];
-        const float4 w4 = *reinterpret_cast<const float4*>(wt + k * op + o);
-        sum[0] = fma((double)w4.x, v, sum[0]);
-        sum[1] = fma((double)w4.y, v, sum[1]);
-        sum[2] = fma((double)w4.z, v, sum[2]);
-        sum[3] = fma((double)w4.w, v, sum[3]);
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        double lin = sum[c] * q[op + o + c];
-        if (value) lin += q[2 * op + o + c];
-        const double pre = __shfl(lin, 0, G);  // the value stream's
-        if (o + c < width) {
-          double f, df;
-          cnf_act(sh.act, pre, sh.p0, f, df);
-          nxt[(o + c) * T] = (float)(value ? f : df * lin);
-        }
-      }
-    }
-    float* swap = cur;
-    cur = nxt;
-    nxt = swap;
-    p = wt + in * op;
-    q += 3 * op;
-  }
-  const int in = sh.w[sh.layers - 1], dp = cnf_pad4(sh.d);
-  const float* wt = p + 5 * dp;
-#pragma unroll
-  for (int i = 0; i < DP; ++i) out[i] = (value && i < dp) ? q[i] : 0.0;
-  for (int k = 0; k < in; ++k) {
-    const double v = (double)cur[k * T];
-#pragma unroll
-    for (int c = 0; c < DP / 4; ++c) {
-      if (4 * c < dp) {
-        const float4 w4 = *reinterpret_cast<const float4*>(wt + k * dp + 4 * c);
-        out[4 * c + 0] = fma((double)w4.x, v, out[4 * c + 0]);
-        out[4 * c + 1] = fma((double)w4.y, v, out[4 * c + 1]);
-        out[4 * c + 2] = fma((double)w4.z, v, out[4 * c + 2]);
-        out[4 * c + 3] = fma((double)w4.w, v, out[4 * c + 3]);
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < DP; ++i) {
-    if (i < dp) {
-      out[i] *= q[dp + i];
-      if (value) out[i] += q[2 * dp + i];
-    }
-  }
-}
-
-// One evaluation of the ODE function for the row of this group at the float32 state xin: k[i] = dy_i (meaningful in
-// the value lane), negdiv = -div (the same in every lane of the group), scale_output and residual folded in.
-template <int G, int DP>
-__device__ __forceinline__ void cnf_field_row(const float* img, const double* tab, float* mine, int T, int half,
-                                              const CnfShape& sh, int s, const float (&xin)[DP], double (&k)[DP],
-                                              double& negdiv) {
-#pragma unroll
-  for (int i = 0; i < DP; ++i)
-    if (i < sh.d) mine[i * T] = s == 0 ? xin[i] : (i == s - 1 ? 1.f : 0.f);
-  cnf_net<G, DP>(img, tab, mine, T, half, sh, s, k);
-  double diag = 0.0;
-#pragma unroll
-  for (int i = 0; i < DP; ++i)
-    if (i == s - 1 && i < sh.d) diag = k[i];
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) diag += __shfl_xor(diag, off, G);
-  double div = diag * sh.scale;
-#pragma unroll
-  for (int i = 0; i < DP; ++i) {
-    k[i] *= sh.scale;
-    if (sh.residual) k[i] -= (double)xin[i];
-  }
-  if (sh.residual) div -= (double)sh.d;
-  negdiv = -div;
-}
-
-template <int G>
-struct CnfGroup {
-  static constexpr int DMAX = G == 32 ? 16 : G - 1;
-  static constexpr int DP = (DMAX + 3) & ~3;
-};
 
 // ---- one evaluation -------------------------------------------------------------------------------------------------
 
@@ -255,7 +65,7 @@ __global__ __launch_bounds__(256) void cnf_field_kernel(const float* __restrict_
 #pragma unroll
     for (int i = 0; i < DP; ++i) xin[i] = i < d ? y[row * d + i] : 0.f;
     double k[DP], nd;
-    cnf_field_row<G, DP>(img, tab, mine, T, half, sh, s, xin, k, nd);
+    cnf_field_row<G, DP>(img, CnfBlockTime{tab}, mine, T, half, sh, s, xin, k, nd);
     if (s == 0 && live) {
 #pragma unroll
       for (int i = 0; i < DP; ++i)
@@ -341,7 +151,7 @@ __global__ __launch_bounds__(256) void cnf_integrate_kernel(const float* __restr
         const double ah = node * h;
 #pragma unroll
         for (int i = 0; i < DP; ++i) xin[i] = (float)(stage == 0 ? yv[i] : yv[i] + ah * k[i]);
-        cnf_field_row<G, DP>(img, tab, mine, T, half, sh, s, xin, k, lk);
+        cnf_field_row<G, DP>(img, CnfBlockTime{tab}, mine, T, half, sh, s, xin, k, lk);
 #pragma unroll
         for (int i = 0; i < DP; ++i) acc[i] += weight * k[i];
         lacc += weight * lk;
@@ -360,31 +170,6 @@ __global__ __launch_bounds__(256) void cnf_integrate_kernel(const float* __restr
 }
 
 // ---- launch ---------------------------------------------------------------------------------------------------------
-
-constexpr int kCnfLdsLimit = 128 * 1024;
-constexpr int kCnfMaxBlocks = 2048;
-
-static bool cnf_shape(int d, int layers, const int32_t* hidden, int kind, int act, int residual, float scale, float p0,
-                      int image_floats, CnfShape* sh) {
-  if (d < 1 || d > FC_CNF_MAX_DIM || layers < 1 || layers > FC_CNF_MAX_HIDDEN_LAYERS + 1) return false;
-  if (kind < 0 || kind > FC_CNF_LAYER_CONCATSQUASH || act < 0 || act > FC_CNF_ACT_IDENTITY) return false;
-  if (layers > 1 && !hidden) return false;
-  sh->d = d;
-  sh->layers = layers;
-  sh->act = act;
-  sh->gated = (kind == FC_CNF_LAYER_SQUASH || kind == FC_CNF_LAYER_CONCATSQUASH) ? 1 : 0;
-  sh->residual = residual ? 1 : 0;
-  sh->scale = (double)scale;
-  sh->p0 = (double)p0;
-  for (int l = 0; l < FC_CNF_MAX_HIDDEN_LAYERS + 2; ++l) sh->w[l] = 0;
-  sh->w[0] = d;
-  for (int l = 1; l < layers; ++l) {
-    if (hidden[l - 1] < 1 || hidden[l - 1] > FC_CNF_MAX_WIDTH) return false;
-    sh->w[l] = hidden[l - 1];
-  }
-  sh->w[layers] = d;
-  return cnf_image_floats(*sh) == image_floats;
-}
 
 // the largest block (256, 128, 64 threads) whose image + table + state fits 64 KiB, else 64 threads
 static int cnf_threads(const CnfShape& sh, int image_floats, int min_threads, size_t* lds) {
@@ -536,7 +321,7 @@ __global__ __launch_bounds__(256) void cnf_field_hutchinson_kernel(
       if (i < d) mine[i * T] = s == 0 ? xin[i] : ein[i];
     }
     double k[DP];
-    cnf_net<G, DP>(img, tab, mine, T, half, sh, s, k);
+    cnf_net<G, DP>(img, CnfBlockTime{tab}, mine, T, half, sh, s, k);
     double dot = 0.0;  // e^T (J e), in the tangent lane
 #pragma unroll
     for (int i = 0; i < DP; ++i)

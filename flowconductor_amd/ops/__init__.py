@@ -88,6 +88,9 @@ from .cnf import (  # noqa: F401
     CNF_MAX_DIM, CNF_MAX_HIDDEN_LAYERS, CNF_MAX_WIDTH, CNF_METHODS, CNF_MIDPOINT, CNF_RK4, CNF_STAGES, _cnf_operands,
     _cnf_pad4, cnf_field, cnf_group_lanes, cnf_image_floats, cnf_integrate, cnf_rows_pay, cnf_supported)
 from .cnf import (  # noqa: F401
+    CNF_DOPRI5_MAX_ATTEMPTS, CNF_DOPRI5_MAX_LANES, CNF_DOPRI5_MIN_TOL, cnf_dopri5, cnf_dopri5_attempts, cnf_dopri5_fits,
+    cnf_dopri5_rows_pay)
+from .cnf import (  # noqa: F401
     CNF_BACKWARD_MAX_BLOCKS, CNF_DOUBLE_BACKWARD_MSG, CNF_TRAIN_MAX_HIDDEN_LAYERS, CNF_TRAIN_MAX_LANES, _CnfFieldFunction, cnf_backward_rows,
     cnf_field_backward, cnf_field_train, cnf_train_lanes, cnf_train_rows_pay, cnf_train_supported)
 from .umnn import (  # noqa: F401

@@ -123,6 +123,74 @@ def cnf_integrate(inputs, logp, image, d, hidden, layer_kind, activation, t0, t1
     return z_out, logp_out
 
 
+# ---- the adaptive solve: fc_cnf_dopri5 -------------------------------------------------------------------------------
+CNF_DOPRI5_MAX_ATTEMPTS = 4096
+# A stage state enters the net rounded to float32 (6e-8 relative): below this tolerance that rounding is of the size of
+# the error the step controller is asked to resolve, and the call keeps the float32 host loop it had.
+CNF_DOPRI5_MIN_TOL = 1e-6
+# The dispatch (options ``cnf_dopri5_kernel=True``) takes the one-launch solve up to this many lanes ``N * G``: the
+# largest power of two at which it measured faster than both the host loop over ``fc_cnf_field`` and the torch
+# composition on both nets of tools/probe/bench_cnf_dopri5.py by more than the spread of the rounds (DESIGN.md,
+# "dopri5 in one launch": at 2^17 lanes it was still ahead, within the composition's spread).  It is
+# ``CNF_KERNEL_MAX_LANES`` as well, up to which ``ODEfunc`` takes the kernels at all.
+CNF_DOPRI5_MAX_LANES = 1 << 16
+
+
+def cnf_dopri5_fits(d, hidden, atol, rtol):
+    """Whether ``fc_cnf_dopri5`` takes a net ``d -> hidden... -> d`` at these tolerances: the limits of the other CNF
+    kernels, and both tolerances at least ``CNF_DOPRI5_MIN_TOL``."""
+    return cnf_supported(d, hidden) and float(atol) >= CNF_DOPRI5_MIN_TOL and float(rtol) >= CNF_DOPRI5_MIN_TOL
+
+
+def cnf_dopri5_rows_pay(n, d):
+    """Whether ``cnf_dopri5_kernel=True`` sends a batch of ``n`` rows of ``d`` features to the one-launch solve."""
+    return n * cnf_group_lanes(d) <= CNF_DOPRI5_MAX_LANES
+
+
+def cnf_dopri5_attempts(max_num_steps):
+    """``max_attempts`` of the kernel for the solver option ``max_num_steps`` (None: not set): clipped to
+    ``CNF_DOPRI5_MAX_ATTEMPTS``; None for a bound below 1, which only the host loop can answer (it raises)."""
+    if max_num_steps is None:
+        return CNF_DOPRI5_MAX_ATTEMPTS
+    limit = int(max_num_steps)
+    return None if limit < 1 else min(limit, CNF_DOPRI5_MAX_ATTEMPTS)
+
+
+def cnf_dopri5(inputs, logp, image, d, hidden, layer_kind, activation, t0, t1, atol, rtol, first_step=None,
+               max_attempts=CNF_DOPRI5_MAX_ATTEMPTS, residual=False, scale_output=1.0, p0=1.0, evals=None):
+    """``(z(t1) [N, d], logp(t1) [N], attempts [N] int32)`` from ``z(t0) = inputs`` and ``logp(t0) = logp`` (None:
+    zeros) with the Dormand-Prince 5(4) pair, one launch, no host sync.  Every row on its own: its own time, step size,
+    decisions and attempt count, judged by the RMS of its own ``d + 1`` scaled errors.  ``first_step`` (> 0) replaces
+    the initial-step heuristic.  A row that has made ``max_attempts`` attempts without reaching ``t1``, or whose error
+    estimate is not finite, or whose step no longer moves ``t``, returns NaN (the host loop raises instead).
+    ``evals``: a float32 device word the launch max-reduces ``2 + 6 * attempts`` into (``1 + ...`` with
+    ``first_step``)."""
+    _hip.require_no_grad(inputs, logp)
+    lib = _hip.load()
+    z, image, hidden, widths = _cnf_operands(inputs, image, d, hidden, layer_kind, activation, evals)
+    n = z.shape[0]
+    if not 1 <= int(max_attempts) <= CNF_DOPRI5_MAX_ATTEMPTS:
+        raise ValueError("flowconductor_amd: fc_cnf_dopri5 takes max_attempts in 1 .. %d" % CNF_DOPRI5_MAX_ATTEMPTS)
+    atol, rtol = float(atol), float(rtol)
+    if not (atol >= 0.0 and rtol >= 0.0 and atol + rtol > 0.0):
+        raise ValueError("flowconductor_amd: fc_cnf_dopri5 takes atol, rtol >= 0, not both 0")
+    step = 0.0 if first_step is None else float(first_step)
+    if first_step is not None and not 0.0 < step < float("inf"):
+        raise ValueError("flowconductor_amd: fc_cnf_dopri5 takes a positive finite first_step")
+    if logp is not None:
+        logp = _hip.dev_f32(logp, "logp")
+        if logp.numel() != n or logp.device != z.device:
+            raise ValueError("flowconductor_amd: logp of %d entries for %d rows" % (logp.numel(), n))
+    z_out = torch.empty_like(z)
+    logp_out = torch.empty(n, dtype=torch.float32, device=z.device)
+    attempts = torch.empty(n, dtype=torch.int32, device=z.device)
+    _call("fc_cnf_dopri5", lib.fc_cnf_dopri5, z.device, _hip.ptr(z), _hip.ptr(logp), _hip.ptr(image), _hip.ptr(z_out),
+          _hip.ptr(logp_out), _hip.ptr(attempts), _hip.ptr(evals), n, d, len(hidden) + 1, widths, layer_kind, activation,
+          int(bool(residual)), float(scale_output), float(p0), image.numel(), float(t0), float(t1), atol, rtol, step,
+          int(max_attempts), _hip.stream_ptr(z.device))
+    return z_out, logp_out, attempts
+
+
 # ---- training: fc_cnf_field_train / fc_cnf_field_backward ------------------------------------------------------------
 CNF_TRAIN_MAX_HIDDEN_LAYERS = 3
 CNF_BACKWARD_MAX_BLOCKS = 256      # the backward launch's grid cap: beyond it a block walks over several row tiles

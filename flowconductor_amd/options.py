@@ -51,11 +51,19 @@ _DEFAULTS = {
     # size (measurements, tests), False never.  Off by default: tests pin the default training route to the composition
     # ("CNF training", has the measured training steps).
     "cnf_training": False,
+    # eval-mode continuous normalizing flows under dopri5: the whole adaptive solve in one fc_cnf_dopri5 launch with
+    # per-row step control instead of the host loop of odeint over fc_cnf_field, for tolerances of at least 1e-6 and
+    # batches up to ops.CNF_DOPRI5_MAX_LANES lanes; "force" takes it at any batch size (measurements, tests), False
+    # never.  A row is judged by its own error there (the host loop judges the batch as one system) and a row that
+    # cannot finish returns NaN where the host loop raises, so the results differ within the tolerance: off by default
+    # ("dopri5 in one launch").
+    "cnf_dopri5_kernel": False,
 }
 
 # options that take a few named values only: anything else is a mistake at the call site
 _CHOICES = {
     "cnf_training": (False, True, "force"),
+    "cnf_dopri5_kernel": (False, True, "force"),
 }
 
 _values = dict(_DEFAULTS)

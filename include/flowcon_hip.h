@@ -54,7 +54,7 @@ extern "C" {
  * sum-of-sigmoids and sibling-spline layers fc_made_inverse_sos / fc_made_inverse_spline, and for the Sylvester
  * back substitution fc_sylvester_inverse, and for the per-sample backward entries fc_linear_per_sample_backward,
  * fc_householder_backward_per_sample and fc_planar_backward_per_sample, and for the continuous-normalizing-flow
- * entries fc_cnf_field / fc_cnf_integrate). */
+ * entries fc_cnf_field / fc_cnf_integrate / fc_cnf_dopri5). */
 #define FC_ABI_VERSION 3
 
 int fc_abi_version(void);
@@ -626,6 +626,30 @@ int fc_cnf_integrate(const float* z, const float* logp, const float* image, floa
                      float* evals, int64_t n, int32_t d, int32_t layers, const int32_t* hidden, int32_t layer_kind,
                      int32_t activation, int32_t residual, float scale_output, float p0, int32_t image_floats,
                      double t0, double t1, int32_t steps, int32_t method, void* stream);
+
+/* fc_cnf_dopri5  (z_out [n, d], logp_out [n]) = (z, logp) + int_{t0}^{t1} (f, -div f) dt with the Dormand-Prince 5(4)
+ *           pair, one launch, no host sync, the same net description and limits as above.  EVERY ROW ON ITS OWN: a
+ *           row has its own t, step size, accept / reject decisions and attempt count, and its error ratio is the
+ *           root mean square over its own d + 1 entries (z and logp) of
+ *               h sum_j e_j k_j / (atol + rtol max(|y0|, |y1|)),
+ *           accepted when <= 1; step factor clip(0.9 ratio^(-1/5), 0.2, 10) (10 at ratio 0, at most 1 after a
+ *           rejection); first same as last; the last step is shortened to end on t1; t1 < t0 integrates backwards.
+ *           first_step > 0 is the first step size (one evaluation before the first attempt); 0 selects the initial
+ *           step of Hairer, Norsett & Wanner II.4 in the row's own norm (two evaluations).  t, h, the state, the
+ *           slopes, the error and the controller are float64; a stage state is rounded to float32 where it enters
+ *           the net.
+ *   attempts      int32 [n]: the attempts the row made, accepted plus rejected
+ *   max_attempts  1 .. FC_CNF_DOPRI5_MAX_ATTEMPTS (hipErrorInvalidValue otherwise).  A row that has made
+ *           max_attempts attempts without reaching t1, whose error ratio is not finite, or whose step no longer
+ *           moves t stops at once and returns NaN in z_out and logp_out: the kernel cannot raise.
+ *   evals         max-reduces (2 + 6 attempts) over the rows (1 + 6 attempts with first_step) into *evals.
+ *           logp NULL means zeros.  atol, rtol >= 0, not both 0; t0, t1 finite.  z != z_out. */
+#define FC_CNF_DOPRI5_MAX_ATTEMPTS 4096
+int fc_cnf_dopri5(const float* z, const float* logp, const float* image, float* z_out, float* logp_out,
+                  int32_t* attempts, float* evals, int64_t n, int32_t d, int32_t layers, const int32_t* hidden,
+                  int32_t layer_kind, int32_t activation, int32_t residual, float scale_output, float p0,
+                  int32_t image_floats, double t0, double t1, double atol, double rtol, double first_step,
+                  int32_t max_attempts, void* stream);
 
 /* Training: one evaluation of the ODE function as an autograd node (same net description as above, at most
  * FC_CNF_TRAIN_MAX_HIDDEN_LAYERS hidden layers; hipErrorInvalidValue otherwise).
