@@ -91,7 +91,7 @@ class CNF(nn.Module):
         or solver options the kernel has no argument for keep the host loop."""
         tolerances = (self.test_atol, self.test_rtol)
         if not all(isinstance(v, (int, float)) for v in tolerances) \
-                or not ops.cnf_dopri5_fits(z.shape[1], plan[3], *tolerances):
+                or not ops.cnf_dopri5_fits(plan.d, plan.hidden, *tolerances):
             return None
         if options.get("cnf_dopri5_kernel") != "force" and not ops.cnf_dopri5_rows_pay(z.shape[0], z.shape[1]):
             return None     # no measured win over the host loop (DESIGN.md, "dopri5 in one launch")

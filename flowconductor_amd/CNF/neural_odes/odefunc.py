@@ -19,6 +19,7 @@ Three routes for ``ODEfunc.forward``:
 Only ``conv=False`` nets are built."""
 import contextlib
 import weakref
+from typing import NamedTuple
 
 import torch
 from torch import nn
@@ -29,6 +30,15 @@ from . import diffeq_layers
 from .util import Lambda, divergence_approx, divergence_bf, sample_gaussian_like, sample_rademacher_like
 
 __all__ = ["ODEnet", "ODEfunc"]
+
+
+class _KernelPlan(NamedTuple):
+    """What is fixed by how the net is built, as the CNF kernels take it (``ODEfunc._kernel_plan``)."""
+    d: int              # width of the rows: the first layer's inputs without the time column of a concat layer
+    hidden: tuple
+    layer_kind: int
+    activation: int
+    p0: float
 
 
 def _square(x):
@@ -150,7 +160,7 @@ class ODEfunc(nn.Module):
     # ---- the kernel ---------------------------------------------------------------------------------------------------
 
     def _kernel_plan(self):
-        """What is fixed by how the net is built: ``(layer kind, activation id, p0, hidden widths)`` or None."""
+        """What is fixed by how the net is built, a ``_KernelPlan``, or None."""
         net = self.diffeq
         if type(net) is not ODEnet or net.act_norm or net.num_squeeze:
             return None
@@ -171,7 +181,7 @@ class ODEfunc(nn.Module):
         act = _kernel_activation(net.activation_fns[0]) if len(layers) > 1 else (ops.CNF_ACT_IDENTITY, 1.0)
         if act is None:
             return None
-        return kind, act[0], act[1], tuple(widths[1:-1])
+        return _KernelPlan(widths[0], tuple(widths[1:-1]), kind, act[0], act[1])
 
     def _use_kernels(self, y):
         """The plan when this call can run on the eval-mode kernels, else None."""
@@ -215,7 +225,7 @@ class ODEfunc(nn.Module):
                 and e.shape == y.shape and e.is_contiguous() and not e.requires_grad):
             return None
         plan = self._plan_for(y)
-        if plan is None or not ops.cnf_train_supported(y.shape[1], plan[3]):
+        if plan is None or not ops.cnf_train_supported(plan.d, plan.hidden):
             return None
         return plan, hutchinson
 
@@ -231,7 +241,7 @@ class ODEfunc(nn.Module):
         structure = (id(net), len(getattr(net, "layers", ())), id(getattr(net, "activation_fns", None)),
                      getattr(net, "act_norm", None), getattr(net, "num_squeeze", None))
         plan = ops.static_memo(self, "cnf_plan", structure, self._kernel_plan)
-        if plan is None or y.shape[1] != net.layers[0]._layer.in_features - (plan[0] == ops.CNF_LAYER_CONCAT):
+        if plan is None or y.shape[1] != plan.d:
             return None
         scale = net.scale_output
         if isinstance(scale, torch.Tensor) or not isinstance(self.residual, (bool, int)):
@@ -265,7 +275,7 @@ class ODEfunc(nn.Module):
         self.__dict__.get("_fc_cache", {}).pop("cnf_training_image", None)
 
     def _pack_image(self, plan, differentiable=False):
-        kind, pieces = plan[0], []
+        kind, pieces = plan.layer_kind, []
         with (contextlib.nullcontext() if differentiable else torch.no_grad()):
             for layer in self.diffeq.layers:
                 weight, bias = layer._layer.weight, layer._layer.bias
@@ -290,17 +300,14 @@ class ODEfunc(nn.Module):
                 wt[:, :out] = weight.t()
                 pieces += [padded(bias), w_t, w_g, b_g, w_b, wt.reshape(-1)]
             image = torch.cat(pieces).contiguous()
-        width = self.diffeq.layers[0]._layer.in_features - (kind == ops.CNF_LAYER_CONCAT)
-        assert image.numel() == ops.cnf_image_floats(width, plan[3]), image.numel()
+        assert image.numel() == ops.cnf_image_floats(plan.d, plan.hidden), image.numel()
         return image
 
     def _kernel_args(self, plan):
         """The arguments ``ops.cnf_field`` / ``ops.cnf_integrate`` share, as keywords."""
-        kind, act, p0, hidden = plan
-        width = self.diffeq.layers[0]._layer.in_features - (kind == ops.CNF_LAYER_CONCAT)
-        return dict(image=self._image(plan), d=width, hidden=hidden, layer_kind=kind, activation=act,
-                    residual=bool(self.residual), scale_output=float(self.diffeq.scale_output), p0=p0,
-                    evals=self._num_evals)
+        return dict(image=self._image(plan), d=plan.d, hidden=plan.hidden, layer_kind=plan.layer_kind,
+                    activation=plan.activation, residual=bool(self.residual),
+                    scale_output=float(self.diffeq.scale_output), p0=plan.p0, evals=self._num_evals)
 
     # ---- one evaluation -----------------------------------------------------------------------------------------------
 

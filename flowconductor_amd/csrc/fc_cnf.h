@@ -1,9 +1,11 @@
 // What the continuous-normalizing-flow kernels share (fc_cnf.hip, fc_cnf_dopri5.hip): the description of a net, the
-// activations, the source of the terms that depend on t alone, and cnf_net / cnf_field_row -- the one copy of the layer
-// arithmetic.  The image layout and the lane layout are described at the top of fc_cnf.hip.
+// activations, the source of the terms that depend on t alone, the block set-up (CnfBlock), cnf_hidden_layers / cnf_net /
+// cnf_field_row -- the one copy of the layer arithmetic, which the backward kernel's recompute runs too -- and the host
+// side's launch plan.  The image layout and the lane layout are described at the top of fc_cnf.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/flowcon_hip.h"
 #include "fc_device.h"
 
@@ -29,19 +31,24 @@ __host__ __device__ inline int cnf_table_doubles(const CnfShape& sh) {
   return total;
 }
 
+// the widest column a layer reads or writes
 __host__ __device__ inline int cnf_max_width(const CnfShape& sh) {
   int m = sh.d;
   for (int l = 1; l < sh.layers; ++l) m = sh.w[l] > m ? sh.w[l] : m;
   return m;
 }
 
-// value and derivative of the activation, in float64 on the float64 pre-activation
-__device__ __forceinline__ void cnf_act(int act, double x, double p0, double& f, double& df) {
+// Value, derivative and (Second) second derivative of the activation, in float64 on the float64 pre-activation (what
+// torch's double backward gives).  What a caller does not read is not computed.
+template <bool Second>
+__device__ __forceinline__ void cnf_act_eval(int act, double x, double p0, double& f, double& df, double& d2f) {
+  d2f = 0.0;
   switch (act) {
     case FC_CNF_ACT_TANH: {
       const double th = tanh(x);
       f = th;
       df = 1.0 - th * th;
+      if (Second) d2f = -2.0 * th * df;
       break;
     }
     case FC_CNF_ACT_RELU:
@@ -52,27 +59,44 @@ __device__ __forceinline__ void cnf_act(int act, double x, double p0, double& f,
       const double sg = 1.0 / (1.0 + exp(-x));
       f = x > 20.0 ? x : log1p(exp(x));
       df = x > 20.0 ? 1.0 : sg;
+      if (Second) d2f = x > 20.0 ? 0.0 : sg * (1.0 - sg);
       break;
     }
     case FC_CNF_ACT_ELU:
       f = x > 0.0 ? x : p0 * expm1(x);
       df = x > 0.0 ? 1.0 : p0 * exp(x);
+      if (Second) d2f = x > 0.0 ? 0.0 : p0 * exp(x);
       break;
     case FC_CNF_ACT_SWISH: {
       const double sg = 1.0 / (1.0 + exp(-x));
+      const double ds = sg * (1.0 - sg);
       f = x * sg;
-      df = sg + x * sg * (1.0 - sg);
+      // the one derivative whose product the backward walk has always associated the other way; both kept bit for bit
+      df = Second ? sg + x * ds : sg + x * sg * (1.0 - sg);
+      if (Second) d2f = ds * (2.0 + x * (1.0 - 2.0 * sg));
       break;
     }
     case FC_CNF_ACT_SQUARE:
       f = x * x;
       df = 2.0 * x;
+      if (Second) d2f = 2.0;
       break;
     default:
       f = x;
       df = 1.0;
       break;
   }
+}
+
+__device__ __forceinline__ void cnf_act(int act, double x, double p0, double& f, double& df) {
+  double d2f;
+  cnf_act_eval<false>(act, x, p0, f, df, d2f);
+}
+
+// first and second derivative, for the backward walk
+__device__ __forceinline__ void cnf_act2(int act, double x, double p0, double& df, double& d2f) {
+  double f;
+  cnf_act_eval<true>(act, x, p0, f, df, d2f);
 }
 
 // What depends on t alone, per layer [b + w_t t | gate | w_b t], each op doubles.  The whole block takes part; the
@@ -91,6 +115,47 @@ __device__ __forceinline__ void cnf_time_table(const float* img, double* tab, co
     p += (5 + sh.w[l]) * op;
     q += 3 * op;
   }
+}
+
+// ---- the block ------------------------------------------------------------------------------------------------------
+
+// Dynamic LDS of every kernel: the image | `mid`, the doubles between (the block's time table, or a gate strip per row)
+// | the state columns st[k][thread].  A row is carried by the G lanes of a group: lane s of row r of the block.
+struct CnfBlock {
+  float* img;
+  double* mid;
+  float* st;
+  float* mine;  // st + tid: this lane's entry of a column, the columns T apart
+  int T, tid, s, r, rows, half;  // half: the second ping-pong buffer, that many floats after the first
+  int64_t tiles;
+};
+
+// Carves the LDS and starts the image copy; it ends WITHOUT a barrier, which the caller owes before the image is read.
+template <int G>
+__device__ __forceinline__ CnfBlock cnf_block(float* lds, const float* __restrict__ image, int image_floats,
+                                              int block_doubles, int row_doubles, int64_t n, const CnfShape& sh) {
+  CnfBlock b;
+  b.T = blockDim.x;
+  b.tid = threadIdx.x;
+  b.s = b.tid % G;
+  b.r = b.tid / G;
+  b.rows = b.T / G;
+  b.half = cnf_max_width(sh) * b.T;
+  b.img = lds;
+  b.mid = reinterpret_cast<double*>(lds + image_floats);
+  b.st = lds + image_floats + 2 * (block_doubles + b.rows * row_doubles);
+  b.mine = b.st + b.tid;
+  b.tiles = (n + b.rows - 1) / b.rows;
+  for (int i = b.tid; i < image_floats; i += b.T) b.img[i] = image[i];
+  return b;
+}
+
+// The row of this lane's group in `tile`.  A group past the end runs along on the last row (the shuffles, and the
+// barriers where a kernel has them, need every lane); only live rows are stored.
+__device__ __forceinline__ int64_t cnf_tile_row(const CnfBlock& b, int64_t tile, int64_t n, bool& live) {
+  const int64_t row = tile * b.rows + b.r;
+  live = row < n;
+  return live ? row : n - 1;
 }
 
 // ---- where cnf_net takes the time terms of a layer from ---------------------------------------------------------------
@@ -138,40 +203,80 @@ struct CnfRowTime {
   }
 };
 
+// ---- where a hidden layer's columns live ------------------------------------------------------------------------------
+//
+// in(): the column (stride T) layer l reads, out(w): the one it writes, w its input width.
+
+// two buffers, swapped per layer: all the forward kernels need
+struct CnfPingPong {
+  float* cur;
+  float* nxt;
+  __device__ __forceinline__ const float* in(int) const { return cur; }
+  __device__ __forceinline__ float* out(int, int) const { return nxt; }
+  __device__ __forceinline__ void advance(int) {
+    float* swap = cur;
+    cur = nxt;
+    nxt = swap;
+  }
+};
+
+// every layer's input kept, slot on slot: what the backward walk reads again
+struct CnfStacked {
+  float* mine;
+  int off;  // floats of the slots below the current layer's input
+  __device__ __forceinline__ const float* in(int T) const { return mine + off * T; }
+  __device__ __forceinline__ float* out(int w, int T) const { return mine + (off + w) * T; }
+  __device__ __forceinline__ void advance(int w) { off += w; }
+};
+
 // ---- the net on one stream -------------------------------------------------------------------------------------------
 
-// Runs the layers on the state column `mine` (stride T, the second buffer `half` floats further on), whose first d
-// entries the caller has set: the input (value stream, s == 0) or a unit tangent (s >= 1).  out[i], i < DP: the last
-// layer in unrounded float64 -- f in the value stream, column s - 1 of df/dy in stream s.  This is the one place that
-// fixes where float32 roundings happen: a stored activation, once.
-template <int G, int DP, class Time>
-__device__ __forceinline__ void cnf_net(const float* img, Time tm, float* mine, int T, int half, const CnfShape& sh,
-                                        int s, double (&out)[DP]) {
-  const bool value = s == 0;
+// sum[c] = (value ? b + w_t t : 0) + sum_k W[o + c][k] x[k]: a tangent has no bias and no time terms
+template <class Time>
+__device__ __forceinline__ void cnf_sum4(const float* wt, const Time& tm, const float* p, const float* x, int T, int in,
+                                         int op, int o, bool value, double (&sum)[4]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) sum[c] = value ? tm.bias(p, op, o + c) : 0.0;
+  for (int k = 0; k < in; ++k) {
+    const double v = (double)x[k * T];
+    const float4 w4 = *reinterpret_cast<const float4*>(wt + k * op + o);
+    sum[0] = fma((double)w4.x, v, sum[0]);
+    sum[1] = fma((double)w4.y, v, sum[1]);
+    sum[2] = fma((double)w4.z, v, sum[2]);
+    sum[3] = fma((double)w4.w, v, sum[3]);
+  }
+}
+
+// From cnf_sum4's sum of output o: lin, this stream's gated product, and pre, the value stream's, which is the
+// pre-activation every stream of the group differentiates at.
+template <int G, class Time>
+__device__ __forceinline__ void cnf_lin_pre(const Time& tm, const float* p, int op, int o, bool value, double sum,
+                                            double& lin, double& pre) {
+  lin = sum * tm.gate(p, op, o);
+  if (value) lin += tm.shift(p, op, o);
+  pre = __shfl(lin, 0, G);
+}
+
+// The hidden layers on this lane's stream, whose first column the caller has set; returns the last layer's piece of the
+// image, with `tm` and `at` standing at that layer.  This is the one place that fixes where float32 roundings happen:
+// a stored activation, once.  The forward kernels and the backward kernel's recompute all run it.
+template <int G, class Time, class Store>
+__device__ __forceinline__ const float* cnf_hidden_layers(const float* img, Time& tm, Store& at, int T,
+                                                          const CnfShape& sh, bool value) {
   const float* p = img;
-  float* cur = mine;
-  float* nxt = mine + half;
   for (int l = 0; l + 1 < sh.layers; ++l) {
     const int in = sh.w[l], width = sh.w[l + 1], op = cnf_pad4(width);
     const float* wt = p + 5 * op;
+    const float* cur = at.in(T);
+    float* nxt = at.out(in, T);
     tm.begin_layer(p, op);
     for (int o = 0; o < op; o += 4) {
       double sum[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) sum[c] = value ? tm.bias(p, op, o + c) : 0.0;  // a tangent: no bias, no time terms
-      for (int k = 0; k < in; ++k) {
-        const double v = (double)cur[k * T];
-        const float4 w4 = *reinterpret_cast<const float4*>(wt + k * op + o);
-        sum[0] = fma((double)w4.x, v, sum[0]);
-        sum[1] = fma((double)w4.y, v, sum[1]);
-        sum[2] = fma((double)w4.z, v, sum[2]);
-        sum[3] = fma((double)w4.w, v, sum[3]);
-      }
+      cnf_sum4(wt, tm, p, cur, T, in, op, o, value, sum);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        double lin = sum[c] * tm.gate(p, op, o + c);
-        if (value) lin += tm.shift(p, op, o + c);
-        const double pre = __shfl(lin, 0, G);  // the value stream's
+        double lin, pre;
+        cnf_lin_pre<G>(tm, p, op, o + c, value, sum[c], lin, pre);
         if (o + c < width) {
           double f, df;
           cnf_act(sh.act, pre, sh.p0, f, df);
@@ -179,12 +284,23 @@ __device__ __forceinline__ void cnf_net(const float* img, Time tm, float* mine, 
         }
       }
     }
-    float* swap = cur;
-    cur = nxt;
-    nxt = swap;
+    at.advance(in);
     p = wt + in * op;
     tm.end_layer(op);
   }
+  return p;
+}
+
+// Runs the layers on the state column `mine` (stride T, the second buffer `half` floats further on), whose first d
+// entries the caller has set: the input (value stream, s == 0) or a tangent's seed (s >= 1).  out[i], i < DP: the last
+// layer in unrounded float64 -- f in the value stream, J times the seed in a tangent stream.
+template <int G, int DP, class Time>
+__device__ __forceinline__ void cnf_net(const float* img, Time tm, float* mine, int T, int half, const CnfShape& sh,
+                                        int s, double (&out)[DP]) {
+  const bool value = s == 0;
+  CnfPingPong at{mine, mine + half};
+  const float* p = cnf_hidden_layers<G>(img, tm, at, T, sh, value);
+  const float* cur = at.in(T);
   const int in = sh.w[sh.layers - 1], dp = cnf_pad4(sh.d);
   const float* wt = p + 5 * dp;
   tm.begin_layer(p, dp);
@@ -213,27 +329,62 @@ __device__ __forceinline__ void cnf_net(const float* img, Time tm, float* mine, 
   tm.end_layer(dp);
 }
 
+// ---- what the tangent lanes carry, and how their results become the divergence ------------------------------------------
+
+// The exact divergence: lane j + 1 carries d/dy_j and ends with column j of the Jacobian, of which the diagonal entry
+// is summed over the group.  Empty, so that handing it on costs no register.
+struct CnfExactDiv {
+  __device__ __forceinline__ void load(const float*, int64_t, int) {}
+  __device__ __forceinline__ float seed(int i, int s) const { return i == s - 1 ? 1.f : 0.f; }
+  template <int G, int DP>
+  __device__ __forceinline__ double reduce(const double (&k)[DP], int s, int d) const {
+    double diag = 0.0;
+#pragma unroll
+    for (int i = 0; i < DP; ++i)
+      if (i == s - 1 && i < d) diag = k[i];
+#pragma unroll
+    for (int off = G / 2; off > 0; off >>= 1) diag += __shfl_xor(diag, off, G);
+    return diag;
+  }
+};
+
+// Hutchinson's estimate e^T (J e): a group of 2 lanes, the one tangent lane seeded with the row's noise e.
+template <int DP>
+struct CnfHutchinsonDiv {
+  float e[DP];
+  __device__ __forceinline__ void load(const float* __restrict__ noise, int64_t row, int d) {
+#pragma unroll
+    for (int i = 0; i < DP; ++i) e[i] = i < d ? noise[row * d + i] : 0.f;
+  }
+  __device__ __forceinline__ float seed(int i, int) const { return e[i]; }
+  template <int G, int>
+  __device__ __forceinline__ double reduce(const double (&k)[DP], int s, int d) const {
+    static_assert(G == 2, "one tangent lane");
+    double dot = 0.0;
+#pragma unroll
+    for (int i = 0; i < DP; ++i)
+      if (s == 1 && i < d) dot += (double)e[i] * k[i];
+    return dot + __shfl_xor(dot, 1, G);
+  }
+};
+
 // One evaluation of the ODE function for the row of this group at the float32 state xin: k[i] = dy_i (meaningful in
 // the value lane), negdiv = -div (the same in every lane of the group), scale_output and residual folded in.
-template <int G, int DP, class Time>
-__device__ __forceinline__ void cnf_field_row(const float* img, Time tm, float* mine, int T, int half,
+template <int G, int DP, class Time, class Div>
+__device__ __forceinline__ void cnf_field_row(const float* img, Time tm, Div dv, float* mine, int T, int half,
                                               const CnfShape& sh, int s, const float (&xin)[DP], double (&k)[DP],
                                               double& negdiv) {
 #pragma unroll
   for (int i = 0; i < DP; ++i)
-    if (i < sh.d) mine[i * T] = s == 0 ? xin[i] : (i == s - 1 ? 1.f : 0.f);
+    if (i < sh.d) mine[i * T] = s == 0 ? xin[i] : dv.seed(i, s);
   cnf_net<G, DP>(img, tm, mine, T, half, sh, s, k);
-  double diag = 0.0;
-#pragma unroll
-  for (int i = 0; i < DP; ++i)
-    if (i == s - 1 && i < sh.d) diag = k[i];
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) diag += __shfl_xor(diag, off, G);
-  double div = diag * sh.scale;
+  double div = dv.template reduce<G, DP>(k, s, sh.d) * sh.scale;
 #pragma unroll
   for (int i = 0; i < DP; ++i) {
-    k[i] *= sh.scale;
-    if (sh.residual) k[i] -= (double)xin[i];
+    if (i < sh.d) {  // nobody reads the padding
+      k[i] *= sh.scale;
+      if (sh.residual) k[i] -= (double)xin[i];
+    }
   }
   if (sh.residual) div -= (double)sh.d;
   negdiv = -div;
@@ -245,13 +396,10 @@ struct CnfGroup {
   static constexpr int DP = (DMAX + 3) & ~3;
 };
 
-// ---- launch ---------------------------------------------------------------------------------------------------------
-
-constexpr int kCnfLdsLimit = 128 * 1024;
-constexpr int kCnfMaxBlocks = 2048;
+// ---- entry: the net a call describes -----------------------------------------------------------------------------------
 
 inline bool cnf_shape(int d, int layers, const int32_t* hidden, int kind, int act, int residual, float scale, float p0,
-                      int image_floats, CnfShape* sh) {
+                      CnfShape* sh) {
   if (d < 1 || d > FC_CNF_MAX_DIM || layers < 1 || layers > FC_CNF_MAX_HIDDEN_LAYERS + 1) return false;
   if (kind < 0 || kind > FC_CNF_LAYER_CONCATSQUASH || act < 0 || act > FC_CNF_ACT_IDENTITY) return false;
   if (layers > 1 && !hidden) return false;
@@ -269,7 +417,89 @@ inline bool cnf_shape(int d, int layers, const int32_t* hidden, int kind, int ac
     sh->w[l] = hidden[l - 1];
   }
   sh->w[layers] = d;
-  return cnf_image_floats(*sh) == image_floats;
+  return true;
+}
+
+// What every launching entry point starts with: a row count, a net of at most max_layers layers, the image it says.
+inline bool cnf_entry(int64_t n, int d, int layers, const int32_t* hidden, int kind, int act, int residual, float scale,
+                      float p0, int image_floats, int max_layers, CnfShape* sh) {
+  return n >= 0 && layers <= max_layers && cnf_shape(d, layers, hidden, kind, act, residual, scale, p0, sh) &&
+         cnf_image_floats(*sh) == image_floats;
+}
+
+// rows in, the image, rows out and the per-row output: all there, and not in place
+inline bool cnf_operands(const void* in, const void* image, const void* out, const void* out1) {
+  return in && image && out && out1 && in != out;
+}
+
+// ---- launch ---------------------------------------------------------------------------------------------------------
+
+constexpr int kCnfLdsLimit = 128 * 1024;
+constexpr int kCnfMaxBlocks = 2048;
+
+// The smallest power of two >= d + 1 lanes carry a row; under Hutchinson's estimator 2 lanes do.
+inline int cnf_group(const CnfShape& sh, bool hutchinson = false) {
+  if (hutchinson || sh.d < 2) return 2;
+  return sh.d < 4 ? 4 : sh.d < 8 ? 8 : sh.d < 16 ? 16 : 32;
+}
+
+// f(std::integral_constant<int, N>) for the N of the list that v equals
+template <int... Ns, class F>
+inline int cnf_with_constant(int v, F&& f) {
+  int result = hipErrorInvalidConfiguration;
+  (void)((v == Ns && ((result = f(std::integral_constant<int, Ns>{})), true)) || ...);
+  return result;
+}
+
+// What a kernel keeps in dynamic LDS besides the image.
+struct CnfLds {
+  size_t block_bytes;  // once per block
+  int thread_floats;   // per thread: the state columns
+  int row_doubles;     // per row
+};
+
+// the forward kernels' time table and two ping-pong columns
+inline CnfLds cnf_forward_lds(const CnfShape& sh) {
+  return {sizeof(double) * (size_t)cnf_table_doubles(sh), 2 * cnf_max_width(sh), 0};
+}
+
+enum CnfFit {
+  kCnfPrefer64K,     // the largest block within 64 KiB, else the smallest block if it fits the limit
+  kCnfLargestBlock,  // the largest block that fits the limit
+};
+
+struct CnfLaunch {
+  int threads;  // 0: not even the smallest block fits kCnfLdsLimit
+  size_t lds;
+  int64_t grid;
+};
+
+// Blocks of 256, 128 or 64 threads, a block per tile of threads / group rows up to max_blocks.
+inline CnfLaunch cnf_launch_plan(int image_floats, int group, const CnfLds& need, CnfFit fit, int64_t n,
+                                 int max_blocks) {
+  const size_t aim = fit == kCnfPrefer64K ? 64 * 1024 : (size_t)kCnfLdsLimit;
+  CnfLaunch plan{256, 0, 0};
+  for (;; plan.threads >>= 1) {
+    plan.lds = sizeof(float) * ((size_t)image_floats + (size_t)need.thread_floats * plan.threads) + need.block_bytes +
+               sizeof(double) * (size_t)need.row_doubles * (size_t)(plan.threads / group);
+    if (plan.lds <= aim || plan.threads <= 64) break;
+  }
+  if (plan.lds > (size_t)kCnfLdsLimit) plan.threads = 0;
+  const int rows = plan.threads ? plan.threads / group : 1;
+  const int64_t tiles = (n + rows - 1) / rows;
+  plan.grid = tiles < max_blocks ? tiles : max_blocks;
+  return plan;
+}
+
+// Raises the kernel's dynamic-LDS limit once per device and launches it.
+template <auto Kernel, class... Args>
+inline int cnf_launch(const CnfLaunch& plan, hipStream_t s, Args... args) {
+  if (!plan.threads) return hipErrorInvalidConfiguration;
+  static PerDeviceOnce once;
+  const hipError_t e = ensure_max_dynamic_lds(once, reinterpret_cast<const void*>(Kernel), kCnfLdsLimit);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)plan.grid), dim3(plan.threads), plan.lds, s, args...);
+  return hipGetLastError();
 }
 
 }  // namespace fc

@@ -7,7 +7,8 @@
 //   fc_cnf_field_train / fc_cnf_field_backward   one evaluation as an autograd node: the exact divergence or
 //                      Hutchinson's estimate, and the gradients of both outputs (further down)
 // (fc_cnf_dopri5, the adaptive solve with per-row step control, is in fc_cnf_dopri5.hip; what the kernels share --
-// CnfShape, the activations, cnf_time_table, cnf_net, cnf_field_row -- is in fc_cnf.h.)
+// CnfShape, the activations, cnf_time_table, CnfBlock, cnf_hidden_layers, cnf_net, cnf_field_row and the launch plan --
+// is in fc_cnf.h.)
 //
 // f is an MLP whose layers all reduce to
 //     pre = W x + b + w_t t,   out = pre * gate + w_b t,   gate = sigmoid(w_g t + b_g)  or  1
@@ -27,46 +28,42 @@
 // evaluation into an LDS table, in float64.  In the integrator all rows of a launch share the step sequence, so the
 // table is rebuilt per stage behind a barrier.
 //
-// Numerics: sums in float64 over the float32 weights, a stored activation rounded to float32 once (cnf_net is the
-// one place that decides this); the integrator keeps (z, logp) and the stage slopes in float64 registers and rounds
-// a stage's state to float32 where it enters the net.
+// Numerics: sums in float64 over the float32 weights, a stored activation rounded to float32 once (cnf_hidden_layers
+// is the one place that decides this); the integrator keeps (z, logp) and the stage slopes in float64 registers and
+// rounds a stage's state to float32 where it enters the net.
 #include "fc_cnf.h"
 
 namespace fc {
 
 // ---- one evaluation -------------------------------------------------------------------------------------------------
 
-template <int G>
-__global__ __launch_bounds__(256) void cnf_field_kernel(const float* __restrict__ y, const float* __restrict__ image,
-                                                        float* __restrict__ dy, float* __restrict__ negdiv,
-                                                        float* __restrict__ evals, int64_t n, CnfShape sh,
-                                                        int image_floats, int table_doubles, float t_host,
-                                                        const float* __restrict__ t_dev) {
-  constexpr int DP = CnfGroup<G>::DP;
+// Div = CnfExactDiv: the exact divergence, G lanes a row.  Div = CnfHutchinsonDiv<DP>: G = 2, the value stream and one
+// tangent stream seeded with the row of e, div = scale e^T (J e).
+template <int G, int DP, class Div>
+__global__ __launch_bounds__(256) void cnf_field_kernel(const float* __restrict__ y, const float* __restrict__ e,
+                                                        const float* __restrict__ image, float* __restrict__ dy,
+                                                        float* __restrict__ negdiv, float* __restrict__ evals,
+                                                        int64_t n, CnfShape sh, int image_floats, int table_doubles,
+                                                        float t_host, const float* __restrict__ t_dev) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* img = lds;
-  double* tab = reinterpret_cast<double*>(lds + image_floats);
-  float* st = lds + image_floats + 2 * table_doubles;
-  const int T = blockDim.x, tid = threadIdx.x;
-  for (int i = tid; i < image_floats; i += T) img[i] = image[i];
+  const CnfBlock b = cnf_block<G>(lds, image, image_floats, table_doubles, 0, n, sh);
   __syncthreads();
-  cnf_time_table(img, tab, sh, t_dev ? (double)t_dev[0] : (double)t_host, tid, T);
+  cnf_time_table(b.img, b.mid, sh, t_dev ? (double)t_dev[0] : (double)t_host, b.tid, b.T);
   __syncthreads();
-  const int d = sh.d, s = tid % G, rows_per_block = T / G, half = cnf_max_width(sh) * T;
-  const int64_t tiles = (n + rows_per_block - 1) / rows_per_block;
-  float* mine = st + tid;
-  if (evals && blockIdx.x == 0 && tid == 0) atomicAdd(evals, 1.f);
+  const int d = sh.d;
+  if (evals && blockIdx.x == 0 && b.tid == 0) atomicAdd(evals, 1.f);
 
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    int64_t row = tile * rows_per_block + tid / G;
-    const bool live = row < n;
-    if (!live) row = n - 1;  // every lane runs (the shuffles need them); only live rows are stored
+  for (int64_t tile = blockIdx.x; tile < b.tiles; tile += gridDim.x) {
+    bool live;
+    const int64_t row = cnf_tile_row(b, tile, n, live);
     float xin[DP];
 #pragma unroll
     for (int i = 0; i < DP; ++i) xin[i] = i < d ? y[row * d + i] : 0.f;
+    Div dv;
+    dv.load(e, row, d);
     double k[DP], nd;
-    cnf_field_row<G, DP>(img, CnfBlockTime{tab}, mine, T, half, sh, s, xin, k, nd);
-    if (s == 0 && live) {
+    cnf_field_row<G, DP>(b.img, CnfBlockTime{b.mid}, dv, b.mine, b.T, b.half, sh, b.s, xin, k, nd);
+    if (b.s == 0 && live) {
 #pragma unroll
       for (int i = 0; i < DP; ++i)
         if (i < d) dy[row * d + i] = (float)k[i];
@@ -105,26 +102,19 @@ __global__ __launch_bounds__(256) void cnf_integrate_kernel(const float* __restr
                                                             int method) {
   constexpr int DP = CnfGroup<G>::DP;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* img = lds;
-  double* tab = reinterpret_cast<double*>(lds + image_floats);
-  float* st = lds + image_floats + 2 * table_doubles;
-  const int T = blockDim.x, tid = threadIdx.x;
-  for (int i = tid; i < image_floats; i += T) img[i] = image[i];
-  const int d = sh.d, s = tid % G, rows_per_block = T / G, half = cnf_max_width(sh) * T;
-  const int64_t tiles = (n + rows_per_block - 1) / rows_per_block;
-  float* mine = st + tid;
+  const CnfBlock b = cnf_block<G>(lds, image, image_floats, table_doubles, 0, n, sh);
+  const int d = sh.d;
   const int stages = cnf_stages(method);
   const double h = (t1 - t0) / (double)steps;
   bool have_table = false;
   double table_t = 0.0;
-  if (evals && blockIdx.x == 0 && tid == 0)  // non-negative floats order like their bit patterns
+  if (evals && blockIdx.x == 0 && b.tid == 0)  // non-negative floats order like their bit patterns
     atomicMax(reinterpret_cast<int*>(evals), __float_as_int((float)steps * (float)stages));
 
   // the tile loop's trip count depends on the block alone, so the barriers below are met by every thread
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    int64_t row = tile * rows_per_block + tid / G;
-    const bool live = row < n;
-    if (!live) row = n - 1;
+  for (int64_t tile = blockIdx.x; tile < b.tiles; tile += gridDim.x) {
+    bool live;
+    const int64_t row = cnf_tile_row(b, tile, n, live);
     double yv[DP], acc[DP], k[DP];
 #pragma unroll
     for (int i = 0; i < DP; ++i) {
@@ -142,7 +132,7 @@ __global__ __launch_bounds__(256) void cnf_integrate_kernel(const float* __restr
         const double tt = ts + node * h;
         if (!have_table || tt != table_t) {
           __syncthreads();  // the image copy, and the readers of the previous table
-          cnf_time_table(img, tab, sh, tt, tid, T);
+          cnf_time_table(b.img, b.mid, sh, tt, b.tid, b.T);
           __syncthreads();
           have_table = true;
           table_t = tt;
@@ -151,7 +141,7 @@ __global__ __launch_bounds__(256) void cnf_integrate_kernel(const float* __restr
         const double ah = node * h;
 #pragma unroll
         for (int i = 0; i < DP; ++i) xin[i] = (float)(stage == 0 ? yv[i] : yv[i] + ah * k[i]);
-        cnf_field_row<G, DP>(img, CnfBlockTime{tab}, mine, T, half, sh, s, xin, k, lk);
+        cnf_field_row<G, DP>(b.img, CnfBlockTime{b.mid}, CnfExactDiv{}, b.mine, b.T, b.half, sh, b.s, xin, k, lk);
 #pragma unroll
         for (int i = 0; i < DP; ++i) acc[i] += weight * k[i];
         lacc += weight * lk;
@@ -160,7 +150,7 @@ __global__ __launch_bounds__(256) void cnf_integrate_kernel(const float* __restr
       for (int i = 0; i < DP; ++i) yv[i] += h * acc[i];
       lp += h * lacc;
     }
-    if (s == 0 && live) {
+    if (b.s == 0 && live) {
 #pragma unroll
       for (int i = 0; i < DP; ++i)
         if (i < d) z_out[row * d + i] = (float)yv[i];
@@ -169,64 +159,10 @@ __global__ __launch_bounds__(256) void cnf_integrate_kernel(const float* __restr
   }
 }
 
-// ---- launch ---------------------------------------------------------------------------------------------------------
-
-// the largest block (256, 128, 64 threads) whose image + table + state fits 64 KiB, else 64 threads
-static int cnf_threads(const CnfShape& sh, int image_floats, int min_threads, size_t* lds) {
-  int threads = 256;
-  for (;; threads >>= 1) {
-    *lds = sizeof(float) * ((size_t)image_floats + 2 * (size_t)cnf_max_width(sh) * threads) +
-           sizeof(double) * (size_t)cnf_table_doubles(sh);
-    if (*lds <= 64 * 1024 || threads <= 64 || threads <= min_threads) break;
-  }
-  return threads;
-}
-
-template <int G>
-static int launch_cnf(const float* y, const float* logp, const float* image, float* out, float* out1, float* evals,
-                      int64_t n, const CnfShape& sh, int image_floats, bool integrate, float t_host, const float* t_dev,
-                      double t0, double t1, int steps, int method, hipStream_t s) {
-  size_t lds;
-  const int threads = cnf_threads(sh, image_floats, G, &lds);
-  if (lds > (size_t)kCnfLdsLimit) return hipErrorInvalidConfiguration;
-  static PerDeviceOnce once_field, once_integrate;
-  const hipError_t e =
-      integrate ? ensure_max_dynamic_lds(once_integrate, reinterpret_cast<const void*>(&cnf_integrate_kernel<G>),
-                                         kCnfLdsLimit)
-                : ensure_max_dynamic_lds(once_field, reinterpret_cast<const void*>(&cnf_field_kernel<G>), kCnfLdsLimit);
-  if (e != hipSuccess) return e;
-  const int rows = threads / G;
-  int64_t grid = (n + rows - 1) / rows;
-  if (grid > kCnfMaxBlocks) grid = kCnfMaxBlocks;
-  const int table = cnf_table_doubles(sh);
-  if (integrate)
-    hipLaunchKernelGGL((cnf_integrate_kernel<G>), dim3((unsigned)grid), dim3(threads), lds, s, y, logp, image, out,
-                       out1, evals, n, sh, image_floats, table, t0, t1, steps, method);
-  else
-    hipLaunchKernelGGL((cnf_field_kernel<G>), dim3((unsigned)grid), dim3(threads), lds, s, y, image, out, out1, evals,
-                       n, sh, image_floats, table, t_host, t_dev);
-  return hipGetLastError();
-}
-
-static int dispatch_cnf(const float* y, const float* logp, const float* image, float* out, float* out1, float* evals,
-                        int64_t n, const CnfShape& sh, int image_floats, bool integrate, float t_host,
-                        const float* t_dev, double t0, double t1, int steps, int method, hipStream_t s) {
-#define FC_CNF_GO(G) \
-  return launch_cnf<G>(y, logp, image, out, out1, evals, n, sh, image_floats, integrate, t_host, t_dev, t0, t1, steps, \
-                       method, s)
-  if (sh.d < 2) FC_CNF_GO(2);
-  if (sh.d < 4) FC_CNF_GO(4);
-  if (sh.d < 8) FC_CNF_GO(8);
-  if (sh.d < 16) FC_CNF_GO(16);
-  FC_CNF_GO(32);
-#undef FC_CNF_GO
-}
-
 // ---- training: one evaluation as an autograd node -----------------------------------------------------------------------
 //
-// fc_cnf_field_train is the forward: without a noise row it IS cnf_field_kernel (the exact divergence); with one, a row
-// is a group of 2 lanes, the value stream and one tangent stream seeded with e, and div = scale e^T (J e)
-// (Hutchinson's estimate).  Both run cnf_net.
+// fc_cnf_field_train is the forward: cnf_field_kernel, without a noise row with the exact divergence, with one with
+// Hutchinson's estimate.
 //
 // fc_cnf_field_backward recomputes the forward and walks the layers back.  S tangent streams, a_l the value
 // stream's pre-activation, m_{l,s} a tangent's gated product, u_{l,s} = act'(a_l) m_{l,s}:
@@ -238,137 +174,22 @@ static int dispatch_cnf(const float* y, const float* logp, const float* image, f
 // sum over the group and, with ab the adjoint a lane holds (o_bar or J_bar_s) and x its stored input (h or u_s), the
 // weight gradient is one sum over ALL lanes of a block: W_bar[k][o] = g[o] sum_lanes ab[o] x[k].
 //
-// LDS per lane: the stored inputs of every layer (slot l, w[l] floats: what cnf_net rounds to float32, so the
-// recomputed pre-activations are the forward's unrounded float64 ones), a slot of d floats for the seeds, and one
-// of the widest layer for the gate products.  An adjoint overwrites the slot it belongs to once the layer above has
-// consumed the input in it: slot l + 1 holds ab of layer l, slot l receives h_bar / u_bar.
+// LDS per lane: the stored inputs of every layer (slot l, w[l] floats: cnf_hidden_layers itself writes them, CnfStacked
+// in place of the forward's ping-pong, so the recomputed pre-activations are the forward's unrounded float64 ones), a
+// slot of d floats for the seeds, and one of the widest layer for the gate products.  An adjoint overwrites the slot
+// it belongs to once the layer above has consumed the input in it: slot l + 1 holds ab of layer l, slot l receives
+// h_bar / u_bar.
 //
 // The sums over rows: inside a block every entry of the gradient image is owned by one thread that adds the lanes in
 // a fixed (rotated, bank-conflict-free) order in float64 and accumulates its tiles in the block's float64 partial
 // image in global memory; cnf_backward_sum_kernel adds the blocks' partials in block order and rounds once.  No
 // atomics: bitwise reproducible.  scale_output multiplies the results, not the seeds.
 
-// first and second derivative of the activation, in float64 (what torch's double backward gives)
-__device__ __forceinline__ void cnf_act2(int act, double x, double p0, double& df, double& d2f) {
-  switch (act) {
-    case FC_CNF_ACT_TANH: {
-      const double th = tanh(x);
-      df = 1.0 - th * th;
-      d2f = -2.0 * th * df;
-      break;
-    }
-    case FC_CNF_ACT_RELU:
-      df = x > 0.0 ? 1.0 : 0.0;
-      d2f = 0.0;
-      break;
-    case FC_CNF_ACT_SOFTPLUS: {
-      const double sg = 1.0 / (1.0 + exp(-x));
-      df = x > 20.0 ? 1.0 : sg;
-      d2f = x > 20.0 ? 0.0 : sg * (1.0 - sg);
-      break;
-    }
-    case FC_CNF_ACT_ELU:
-      df = x > 0.0 ? 1.0 : p0 * exp(x);
-      d2f = x > 0.0 ? 0.0 : p0 * exp(x);
-      break;
-    case FC_CNF_ACT_SWISH: {
-      const double sg = 1.0 / (1.0 + exp(-x));
-      const double ds = sg * (1.0 - sg);
-      df = sg + x * ds;
-      d2f = ds * (2.0 + x * (1.0 - 2.0 * sg));
-      break;
-    }
-    case FC_CNF_ACT_SQUARE:
-      df = 2.0 * x;
-      d2f = 2.0;
-      break;
-    default:
-      df = 1.0;
-      d2f = 0.0;
-      break;
-  }
-}
-
-template <int DP>
-__global__ __launch_bounds__(256) void cnf_field_hutchinson_kernel(
-    const float* __restrict__ y, const float* __restrict__ e, const float* __restrict__ image, float* __restrict__ dy,
-    float* __restrict__ negdiv, float* __restrict__ evals, int64_t n, CnfShape sh, int image_floats, int table_doubles,
-    float t_host, const float* __restrict__ t_dev) {
-  constexpr int G = 2;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* img = lds;
-  double* tab = reinterpret_cast<double*>(lds + image_floats);
-  float* st = lds + image_floats + 2 * table_doubles;
-  const int T = blockDim.x, tid = threadIdx.x;
-  for (int i = tid; i < image_floats; i += T) img[i] = image[i];
-  __syncthreads();
-  cnf_time_table(img, tab, sh, t_dev ? (double)t_dev[0] : (double)t_host, tid, T);
-  __syncthreads();
-  const int d = sh.d, s = tid % G, rows_per_block = T / G, half = cnf_max_width(sh) * T;
-  const int64_t tiles = (n + rows_per_block - 1) / rows_per_block;
-  float* mine = st + tid;
-  if (evals && blockIdx.x == 0 && tid == 0) atomicAdd(evals, 1.f);
-
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    int64_t row = tile * rows_per_block + tid / G;
-    const bool live = row < n;
-    if (!live) row = n - 1;
-    float xin[DP], ein[DP];
-#pragma unroll
-    for (int i = 0; i < DP; ++i) {
-      xin[i] = i < d ? y[row * d + i] : 0.f;
-      ein[i] = i < d ? e[row * d + i] : 0.f;
-      if (i < d) mine[i * T] = s == 0 ? xin[i] : ein[i];
-    }
-    double k[DP];
-    cnf_net<G, DP>(img, CnfBlockTime{tab}, mine, T, half, sh, s, k);
-    double dot = 0.0;  // e^T (J e), in the tangent lane
-#pragma unroll
-    for (int i = 0; i < DP; ++i)
-      if (s == 1 && i < d) dot += (double)ein[i] * k[i];
-    dot += __shfl_xor(dot, 1, G);
-    double div = dot * sh.scale;
-    if (sh.residual) div -= (double)d;
-    if (s == 0 && live) {
-#pragma unroll
-      for (int i = 0; i < DP; ++i) {
-        if (i < d) {
-          double v = k[i] * sh.scale;
-          if (sh.residual) v -= (double)xin[i];
-          dy[row * d + i] = (float)v;
-        }
-      }
-      negdiv[row] = (float)(-div);
-    }
-  }
-}
-
-// sum[c] = (value ? b + w_t t : 0) + sum_k W[o + c][k] x[k], as cnf_net adds it
-__device__ __forceinline__ void cnf_sum4(const float* wt, const double* q, const float* x, int T, int in, int op,
-                                         int o, bool value, double (&sum)[4]) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c) sum[c] = value ? q[o + c] : 0.0;
-  for (int k = 0; k < in; ++k) {
-    const double v = (double)x[k * T];
-    const float4 w4 = *reinterpret_cast<const float4*>(wt + k * op + o);
-    sum[0] = fma((double)w4.x, v, sum[0]);
-    sum[1] = fma((double)w4.y, v, sum[1]);
-    sum[2] = fma((double)w4.z, v, sum[2]);
-    sum[3] = fma((double)w4.w, v, sum[3]);
-  }
-}
-
-__host__ __device__ inline int cnf_out_max_width(const CnfShape& sh) {
-  int m = sh.d;
-  for (int l = 1; l < sh.layers; ++l) m = sh.w[l] > m ? sh.w[l] : m;
-  return m;
-}
-
 // floats of LDS a lane of the backward kernel owns: the inputs of every layer, the seeds, the gate products
 __host__ __device__ inline int cnf_backward_lane_floats(const CnfShape& sh) {
   int total = 0;
   for (int l = 0; l < sh.layers; ++l) total += sh.w[l];
-  return total + sh.d + cnf_out_max_width(sh);
+  return total + sh.d + cnf_max_width(sh);
 }
 
 template <int G>
@@ -378,59 +199,34 @@ __global__ __launch_bounds__(256) void cnf_backward_kernel(
     double* __restrict__ partial, int64_t n, CnfShape sh, int image_floats, int table_doubles, int lane_floats,
     float t_host, const float* __restrict__ t_dev) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* img = lds;
-  double* tab = reinterpret_cast<double*>(lds + image_floats);
-  float* st = lds + image_floats + 2 * table_doubles;
-  const int T = blockDim.x, tid = threadIdx.x;
-  for (int i = tid; i < image_floats; i += T) img[i] = image[i];
+  const CnfBlock b = cnf_block<G>(lds, image, image_floats, table_doubles, 0, n, sh);
+  const float* img = b.img;
+  float* st = b.st;
+  float* mine = b.mine;
+  const int T = b.T, tid = b.tid, s = b.s;
   __syncthreads();
   const double t = t_dev ? (double)t_dev[0] : (double)t_host;
-  cnf_time_table(img, tab, sh, t, tid, T);
+  cnf_time_table(img, b.mid, sh, t, tid, T);
   __syncthreads();
-  const int d = sh.d, s = tid % G, rows_per_block = T / G;
+  const int d = sh.d;
   const bool value = s == 0;
-  const int64_t tiles = (n + rows_per_block - 1) / rows_per_block;
-  float* mine = st + tid;
-  const int gate_slot = lane_floats - cnf_out_max_width(sh);
+  const int gate_slot = lane_floats - cnf_max_width(sh);
   double* mypart = partial + (size_t)blockIdx.x * (size_t)image_floats;
   bool first = true;
 
   // the trip count depends on the block alone, so every thread meets the barriers below
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    int64_t row = tile * rows_per_block + tid / G;
-    const bool live = row < n;
-    if (!live) row = n - 1;  // runs along for the shuffles and the barriers, with zero seeds
+  for (int64_t tile = blockIdx.x; tile < b.tiles; tile += gridDim.x) {
+    bool live;  // a row past the end runs along with zero seeds
+    const int64_t row = cnf_tile_row(b, tile, n, live);
 
-    // forward: the inputs of every layer, rounded where cnf_net rounds them
+    // forward: the inputs of every layer, as the forward kernel computed and rounded them
     for (int i = 0; i < d; ++i)
       mine[i * T] = value ? y[row * d + i] : (e ? e[row * d + i] : (i == s - 1 ? 1.f : 0.f));
-    int off = 0;
-    const float* p = img;
-    const double* q = tab;
-    for (int l = 0; l + 1 < sh.layers; ++l) {
-      const int in = sh.w[l], width = sh.w[l + 1], op = cnf_pad4(width);
-      const float* wt = p + 5 * op;
-      const float* cur = mine + off * T;
-      float* nxt = mine + (off + in) * T;
-      for (int o = 0; o < op; o += 4) {
-        double sum[4];
-        cnf_sum4(wt, q, cur, T, in, op, o, value, sum);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          double lin = sum[c] * q[op + o + c];
-          if (value) lin += q[2 * op + o + c];
-          const double pre = __shfl(lin, 0, G);
-          if (o + c < width) {
-            double f, df;
-            cnf_act(sh.act, pre, sh.p0, f, df);
-            nxt[(o + c) * T] = (float)(value ? f : df * lin);
-          }
-        }
-      }
-      off += in;
-      p = wt + in * op;
-      q += 3 * op;
-    }
+    CnfBlockTime tm{b.mid};
+    CnfStacked slots{mine, 0};
+    const float* p = cnf_hidden_layers<G>(img, tm, slots, T, sh, value);
+    int off = slots.off;
+    const double* q = tm.q;
 
     // seeds, in the slot above the last layer's input
     {
@@ -447,19 +243,19 @@ __global__ __launch_bounds__(256) void cnf_backward_kernel(
       const bool last = l == sh.layers - 1;
       const int in = sh.w[l], width = sh.w[l + 1], op = cnf_pad4(width);
       const float* wt = p + 5 * op;
+      const CnfBlockTime here{q};          // the layer's time terms
       float* x = mine + off * T;           // this lane's input of the layer
       float* adj = mine + (off + in) * T;  // in: the adjoint of the layer's activated output; out: ab
       float* gp = mine + gate_slot * T;    // ab * (W x + c): the gate's share of this lane
 
       for (int o = 0; o < op; o += 4) {
         double sum[4];
-        cnf_sum4(wt, q, x, T, in, op, o, value, sum);
+        cnf_sum4(wt, here, p, x, T, in, op, o, value, sum);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           const bool real = o + c < width;
-          double lin = sum[c] * q[op + o + c];
-          if (value) lin += q[2 * op + o + c];
-          const double pre = __shfl(lin, 0, G);
+          double lin, pre;
+          cnf_lin_pre<G>(here, p, op, o + c, value, sum[c], lin, pre);
           const double xb = real ? (double)adj[(o + c) * T] : 0.0;
           double ab = xb;
           if (!last) {
@@ -596,77 +392,42 @@ __global__ __launch_bounds__(256) void cnf_backward_sum_kernel(const double* __r
   g_image[i] = (float)(sum * scale);
 }
 
+// ---- launch ---------------------------------------------------------------------------------------------------------
+
 constexpr int kCnfBackwardMaxBlocks = 256;
+constexpr int kCnfTrainMaxLayers = FC_CNF_TRAIN_MAX_HIDDEN_LAYERS + 1;
 
-template <int DP>
-static int launch_cnf_hutchinson(const float* y, const float* e, const float* image, float* dy, float* negdiv,
-                                 float* evals, int64_t n, const CnfShape& sh, int image_floats, float t_host,
-                                 const float* t_dev, hipStream_t s) {
-  size_t lds;
-  const int threads = cnf_threads(sh, image_floats, 2, &lds);
-  if (lds > (size_t)kCnfLdsLimit) return hipErrorInvalidConfiguration;
-  static PerDeviceOnce once;
-  const hipError_t err =
-      ensure_max_dynamic_lds(once, reinterpret_cast<const void*>(&cnf_field_hutchinson_kernel<DP>), kCnfLdsLimit);
-  if (err != hipSuccess) return err;
-  const int rows = threads / 2;
-  int64_t grid = (n + rows - 1) / rows;
-  if (grid > kCnfMaxBlocks) grid = kCnfMaxBlocks;
-  hipLaunchKernelGGL((cnf_field_hutchinson_kernel<DP>), dim3((unsigned)grid), dim3(threads), lds, s, y, e, image, dy,
-                     negdiv, evals, n, sh, image_floats, cnf_table_doubles(sh), t_host, t_dev);
-  return hipGetLastError();
+// the exact divergence by the group of d, Hutchinson's estimate (e) in 2 lanes by the padded d
+static int launch_cnf_field(const float* y, const float* e, const float* image, float* dy, float* negdiv, float* evals,
+                            int64_t n, const CnfShape& sh, int image_floats, float t_host, const float* t_dev,
+                            hipStream_t s) {
+  const int group = cnf_group(sh, e != nullptr), table = cnf_table_doubles(sh);
+  const CnfLaunch plan = cnf_launch_plan(image_floats, group, cnf_forward_lds(sh), kCnfPrefer64K, n, kCnfMaxBlocks);
+  if (e)
+    return cnf_with_constant<4, 8, 16>(sh.d <= 4 ? 4 : sh.d <= 8 ? 8 : 16, [&](auto dp) {
+      constexpr int DP = decltype(dp)::value;
+      return cnf_launch<&cnf_field_kernel<2, DP, CnfHutchinsonDiv<DP>>>(plan, s, y, e, image, dy, negdiv, evals, n, sh,
+                                                                        image_floats, table, t_host, t_dev);
+    });
+  return cnf_with_constant<2, 4, 8, 16, 32>(group, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    return cnf_launch<&cnf_field_kernel<G, CnfGroup<G>::DP, CnfExactDiv>>(plan, s, y, e, image, dy, negdiv, evals, n,
+                                                                          sh, image_floats, table, t_host, t_dev);
+  });
 }
 
-static int cnf_backward_group(const CnfShape& sh, bool with_e) {
-  if (with_e || sh.d < 2) return 2;
-  return sh.d < 4 ? 4 : sh.d < 8 ? 8 : sh.d < 16 ? 16 : 32;
+// the backward kernel's table and a lane's slots: the largest block that fits, a block per tile up to the cap
+static CnfLaunch cnf_backward_plan(const CnfShape& sh, int image_floats, bool with_e, int64_t n) {
+  const CnfLds need{sizeof(double) * (size_t)cnf_table_doubles(sh), cnf_backward_lane_floats(sh), 0};
+  return cnf_launch_plan(image_floats, cnf_group(sh, with_e), need, kCnfLargestBlock, n, kCnfBackwardMaxBlocks);
 }
 
-// the largest block (256, 128, 64 threads) whose image + table + lanes fit; 0 when 64 threads do not
-static int cnf_backward_threads(const CnfShape& sh, int image_floats, size_t* lds) {
-  for (int threads = 256; threads >= 64; threads >>= 1) {
-    *lds = sizeof(float) * ((size_t)image_floats + (size_t)cnf_backward_lane_floats(sh) * threads) +
-           sizeof(double) * (size_t)cnf_table_doubles(sh);
-    if (*lds <= (size_t)kCnfLdsLimit) return threads;
-  }
-  return 0;
-}
-
-static int64_t cnf_backward_blocks(const CnfShape& sh, int image_floats, bool with_e, int64_t n, int* threads,
-                                   size_t* lds) {
-  *threads = cnf_backward_threads(sh, image_floats, lds);
-  if (!*threads) return 0;
-  const int rows = *threads / cnf_backward_group(sh, with_e);
-  const int64_t tiles = (n + rows - 1) / rows;
-  return tiles < kCnfBackwardMaxBlocks ? tiles : kCnfBackwardMaxBlocks;
-}
-
-template <int G>
-static int launch_cnf_backward(const float* y, const float* e, const float* image, const float* g_dy,
-                               const float* g_negdiv, float* g_y, float* g_image, double* partial, int64_t n,
-                               const CnfShape& sh, int image_floats, float t_host, const float* t_dev, hipStream_t s) {
-  int threads;
-  size_t lds;
-  const int64_t grid = cnf_backward_blocks(sh, image_floats, e != nullptr, n, &threads, &lds);
-  if (grid < 1) return hipErrorInvalidConfiguration;
-  static PerDeviceOnce once;
-  const hipError_t err =
-      ensure_max_dynamic_lds(once, reinterpret_cast<const void*>(&cnf_backward_kernel<G>), kCnfLdsLimit);
-  if (err != hipSuccess) return err;
-  hipLaunchKernelGGL((cnf_backward_kernel<G>), dim3((unsigned)grid), dim3(threads), lds, s, y, e, image, g_dy,
-                     g_negdiv, g_y, partial, n, sh, image_floats, cnf_table_doubles(sh), cnf_backward_lane_floats(sh),
-                     t_host, t_dev);
-  hipError_t launched = hipGetLastError();
-  if (launched != hipSuccess) return launched;
-  hipLaunchKernelGGL(cnf_backward_sum_kernel, dim3((unsigned)((image_floats + 255) / 256)), dim3(256), 0, s, partial,
-                     g_image, (int)grid, image_floats, sh.scale);
-  return hipGetLastError();
-}
-
-static bool cnf_train_shape(int d, int layers, const int32_t* hidden, int kind, int act, int residual, float scale,
-                            float p0, int image_floats, CnfShape* sh) {
-  return layers <= FC_CNF_TRAIN_MAX_HIDDEN_LAYERS + 1 &&
-         cnf_shape(d, layers, hidden, kind, act, residual, scale, p0, image_floats, sh);
+// The plan of the backward launch for n rows of a net known by its widths alone; false outside the kernel's limits.
+static bool cnf_backward_query(int64_t n, int d, int layers, const int32_t* hidden, bool with_e, CnfShape* sh,
+                               CnfLaunch* plan) {
+  if (n < 0 || layers > kCnfTrainMaxLayers || !cnf_shape(d, layers, hidden, 0, 0, 0, 1.f, 1.f, sh)) return false;
+  *plan = cnf_backward_plan(*sh, cnf_image_floats(*sh), with_e, n);
+  return plan->threads != 0;
 }
 
 }  // namespace fc
@@ -676,49 +437,28 @@ extern "C" int fc_cnf_field_train(const float* y, const float* e, const float* i
                                   int32_t layer_kind, int32_t activation, int32_t residual, float scale_output,
                                   float p0, int32_t image_floats, float t, const float* t_dev, void* stream) {
   fc::CnfShape sh;
-  if (n < 0 || !fc::cnf_train_shape(d, layers, hidden, layer_kind, activation, residual, scale_output, p0, image_floats,
-                                    &sh))
+  if (!fc::cnf_entry(n, d, layers, hidden, layer_kind, activation, residual, scale_output, p0, image_floats,
+                     fc::kCnfTrainMaxLayers, &sh))
     return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
-  if (!y || !image || !dy || !negdiv || y == dy) return hipErrorInvalidValue;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (!e)
-    return fc::dispatch_cnf(y, nullptr, image, dy, negdiv, evals, n, sh, image_floats, false, t, t_dev, 0.0, 0.0, 0, 0,
-                            s);
-  if (d <= 4) return fc::launch_cnf_hutchinson<4>(y, e, image, dy, negdiv, evals, n, sh, image_floats, t, t_dev, s);
-  if (d <= 8) return fc::launch_cnf_hutchinson<8>(y, e, image, dy, negdiv, evals, n, sh, image_floats, t, t_dev, s);
-  return fc::launch_cnf_hutchinson<16>(y, e, image, dy, negdiv, evals, n, sh, image_floats, t, t_dev, s);
+  if (!fc::cnf_operands(y, image, dy, negdiv)) return hipErrorInvalidValue;
+  return fc::launch_cnf_field(y, e, image, dy, negdiv, evals, n, sh, image_floats, t, t_dev,
+                              static_cast<hipStream_t>(stream));
 }
 
 extern "C" int fc_cnf_field_backward_rows(int32_t d, int32_t layers, const int32_t* hidden, int32_t with_e) {
   fc::CnfShape sh;
-  if (d < 1 || d > FC_CNF_MAX_DIM || layers < 1 || layers > FC_CNF_TRAIN_MAX_HIDDEN_LAYERS + 1) return -1;
-  if (layers > 1 && !hidden) return -1;
-  int floats = 0, below = d;
-  for (int l = 1; l <= layers; ++l) {
-    const int width = l < layers ? hidden[l - 1] : d;
-    floats += (5 + below) * fc::cnf_pad4(width);
-    below = width;
-  }
-  if (!fc::cnf_train_shape(d, layers, hidden, 0, 0, 0, 1.f, 1.f, floats, &sh)) return -1;
-  size_t lds;
-  const int threads = fc::cnf_backward_threads(sh, floats, &lds);
-  return threads ? threads / fc::cnf_backward_group(sh, with_e != 0) : -1;
+  fc::CnfLaunch plan;
+  if (!fc::cnf_backward_query(0, d, layers, hidden, with_e != 0, &sh, &plan)) return -1;
+  return plan.threads / fc::cnf_group(sh, with_e != 0);
 }
 
 extern "C" int fc_cnf_field_backward_workspace(int64_t n, int32_t d, int32_t layers, const int32_t* hidden,
                                                int32_t with_e) {
-  const int rows = fc_cnf_field_backward_rows(d, layers, hidden, with_e);
-  if (rows < 1 || n < 0) return -1;
-  int64_t blocks = (n + rows - 1) / rows;
-  if (blocks > fc::kCnfBackwardMaxBlocks) blocks = fc::kCnfBackwardMaxBlocks;
-  int floats = 0, below = d;
-  for (int l = 1; l <= layers; ++l) {
-    const int width = l < layers ? hidden[l - 1] : d;
-    floats += (5 + below) * fc::cnf_pad4(width);
-    below = width;
-  }
-  return (int)(2 * blocks * floats);
+  fc::CnfShape sh;
+  fc::CnfLaunch plan;
+  if (!fc::cnf_backward_query(n, d, layers, hidden, with_e != 0, &sh, &plan)) return -1;
+  return (int)(2 * plan.grid * fc::cnf_image_floats(sh));
 }
 
 extern "C" int fc_cnf_field_backward(const float* y, const float* e, const float* image, const float* g_dy,
@@ -727,8 +467,8 @@ extern "C" int fc_cnf_field_backward(const float* y, const float* e, const float
                                      int32_t activation, int32_t residual, float scale_output, float p0,
                                      int32_t image_floats, float t, const float* t_dev, void* stream) {
   fc::CnfShape sh;
-  if (n < 0 || !fc::cnf_train_shape(d, layers, hidden, layer_kind, activation, residual, scale_output, p0, image_floats,
-                                    &sh))
+  if (!fc::cnf_entry(n, d, layers, hidden, layer_kind, activation, residual, scale_output, p0, image_floats,
+                     fc::kCnfTrainMaxLayers, &sh))
     return hipErrorInvalidValue;
   if (!g_image) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -736,16 +476,16 @@ extern "C" int fc_cnf_field_backward(const float* y, const float* e, const float
   if (!y || !image || !g_dy || !g_negdiv || !g_y || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 7))
     return hipErrorInvalidValue;
   double* partial = static_cast<double*>(workspace);
-#define FC_CNF_BACK(G) \
-  return fc::launch_cnf_backward<G>(y, e, image, g_dy, g_negdiv, g_y, g_image, partial, n, sh, image_floats, t, t_dev, s)
-  switch (fc::cnf_backward_group(sh, e != nullptr)) {
-    case 2: FC_CNF_BACK(2);
-    case 4: FC_CNF_BACK(4);
-    case 8: FC_CNF_BACK(8);
-    case 16: FC_CNF_BACK(16);
-    default: FC_CNF_BACK(32);
-  }
-#undef FC_CNF_BACK
+  const fc::CnfLaunch plan = fc::cnf_backward_plan(sh, image_floats, e != nullptr, n);
+  const int launched = fc::cnf_with_constant<2, 4, 8, 16, 32>(fc::cnf_group(sh, e != nullptr), [&](auto g) {
+    return fc::cnf_launch<&fc::cnf_backward_kernel<decltype(g)::value>>(
+        plan, s, y, e, image, g_dy, g_negdiv, g_y, partial, n, sh, image_floats, fc::cnf_table_doubles(sh),
+        fc::cnf_backward_lane_floats(sh), t, t_dev);
+  });
+  if (launched != hipSuccess) return launched;
+  hipLaunchKernelGGL(fc::cnf_backward_sum_kernel, dim3((unsigned)((image_floats + 255) / 256)), dim3(256), 0, s,
+                     partial, g_image, (int)plan.grid, image_floats, sh.scale);
+  return hipGetLastError();
 }
 
 extern "C" int fc_cnf_field(const float* y, const float* image, float* dy, float* negdiv, float* evals, int64_t n,
@@ -753,12 +493,13 @@ extern "C" int fc_cnf_field(const float* y, const float* image, float* dy, float
                             int32_t residual, float scale_output, float p0, int32_t image_floats, float t,
                             const float* t_dev, void* stream) {
   fc::CnfShape sh;
-  if (n < 0 || !fc::cnf_shape(d, layers, hidden, layer_kind, activation, residual, scale_output, p0, image_floats, &sh))
+  if (!fc::cnf_entry(n, d, layers, hidden, layer_kind, activation, residual, scale_output, p0, image_floats,
+                     FC_CNF_MAX_HIDDEN_LAYERS + 1, &sh))
     return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
-  if (!y || !image || !dy || !negdiv || y == dy) return hipErrorInvalidValue;
-  return fc::dispatch_cnf(y, nullptr, image, dy, negdiv, evals, n, sh, image_floats, false, t, t_dev, 0.0, 0.0, 0, 0,
-                          static_cast<hipStream_t>(stream));
+  if (!fc::cnf_operands(y, image, dy, negdiv)) return hipErrorInvalidValue;
+  return fc::launch_cnf_field(y, nullptr, image, dy, negdiv, evals, n, sh, image_floats, t, t_dev,
+                              static_cast<hipStream_t>(stream));
 }
 
 extern "C" int fc_cnf_integrate(const float* z, const float* logp, const float* image, float* z_out, float* logp_out,
@@ -767,12 +508,18 @@ extern "C" int fc_cnf_integrate(const float* z, const float* logp, const float* 
                                 int32_t image_floats, double t0, double t1, int32_t steps, int32_t method,
                                 void* stream) {
   fc::CnfShape sh;
-  if (n < 0 || steps < 1 || method < FC_CNF_EULER || method > FC_CNF_RK4 || !(t0 == t0) || !(t1 == t1))
+  if (steps < 1 || method < FC_CNF_EULER || method > FC_CNF_RK4 || !(t0 == t0) || !(t1 == t1))
     return hipErrorInvalidValue;
-  if (!fc::cnf_shape(d, layers, hidden, layer_kind, activation, residual, scale_output, p0, image_floats, &sh))
+  if (!fc::cnf_entry(n, d, layers, hidden, layer_kind, activation, residual, scale_output, p0, image_floats,
+                     FC_CNF_MAX_HIDDEN_LAYERS + 1, &sh))
     return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
-  if (!z || !image || !z_out || !logp_out || z == z_out) return hipErrorInvalidValue;
-  return fc::dispatch_cnf(z, logp, image, z_out, logp_out, evals, n, sh, image_floats, true, 0.f, nullptr, t0, t1,
-                          steps, method, static_cast<hipStream_t>(stream));
+  if (!fc::cnf_operands(z, image, z_out, logp_out)) return hipErrorInvalidValue;
+  const fc::CnfLaunch plan = fc::cnf_launch_plan(image_floats, fc::cnf_group(sh), fc::cnf_forward_lds(sh),
+                                                 fc::kCnfPrefer64K, n, fc::kCnfMaxBlocks);
+  return fc::cnf_with_constant<2, 4, 8, 16, 32>(fc::cnf_group(sh), [&](auto g) {
+    return fc::cnf_launch<&fc::cnf_integrate_kernel<decltype(g)::value>>(
+        plan, static_cast<hipStream_t>(stream), z, logp, image, z_out, logp_out, evals, n, sh, image_floats,
+        fc::cnf_table_doubles(sh), t0, t1, steps, method);
+  });
 }

@@ -72,7 +72,7 @@ __device__ __forceinline__ double dopri5_slope(const float* img, double* strip, 
     xin[i] = i < sh.d ? v : 0.f;
   }
   double k[DP], negdiv;
-  cnf_field_row<G, DP>(img, CnfRowTime<G>{t, strip, s, sh.gated}, mine, T, half, sh, s, xin, k, negdiv);
+  cnf_field_row<G, DP>(img, CnfRowTime<G>{t, strip, s, sh.gated}, CnfExactDiv{}, mine, T, half, sh, s, xin, k, negdiv);
   double slope = s == sh.d ? negdiv : 0.0;
 #pragma unroll
   for (int i = 0; i < DP; ++i) {
@@ -92,25 +92,21 @@ __global__ __launch_bounds__(256) void cnf_dopri5_kernel(const float* __restrict
                                                          int max_attempts) {
   constexpr int DP = CnfGroup<G>::DP;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int T = blockDim.x, tid = threadIdx.x;
-  const int d = sh.d, s = tid % G, rows_per_block = T / G, half = cnf_max_width(sh) * T;
-  float* img = lds;
-  double* strip = reinterpret_cast<double*>(lds + image_floats) + (size_t)(tid / G) * strip_doubles;
-  float* st = lds + image_floats + 2 * rows_per_block * strip_doubles;
-  for (int i = tid; i < image_floats; i += T) img[i] = image[i];
-  __syncthreads();  // the only barrier: the tile loop below has none
-  const int64_t tiles = (n + rows_per_block - 1) / rows_per_block;
-  float* mine = st + tid;
+  const CnfBlock b = cnf_block<G>(lds, image, image_floats, 0, strip_doubles, n, sh);
+  __syncthreads();  // the only barrier (cnf_block has none): the tile loop below has none
+  const float* img = b.img;
+  double* strip = b.mid + (size_t)b.r * strip_doubles;  // this row's
+  float* mine = b.mine;
+  const int T = b.T, tid = b.tid, d = sh.d, s = b.s, half = b.half;
   const bool owner = s <= d;
   const double span = t1 - t0, aspan = fabs(span), direction = span > 0.0 ? 1.0 : -1.0;
   const double reach = 1e-12 * fmax(1.0, aspan);
   const bool probe = !(first_step > 0.0);
   int most = -1;  // the largest attempt count of this lane's live rows
 
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    int64_t row = tile * rows_per_block + tid / G;
-    const bool live = row < n;
-    if (!live) row = n - 1;  // every lane runs (the shuffles need them); only live rows are stored
+  for (int64_t tile = blockIdx.x; tile < b.tiles; tile += gridDim.x) {
+    bool live;
+    const int64_t row = cnf_tile_row(b, tile, n, live);
     double y = 0.0;
     if (s < d) y = (double)z[row * d + s];
     if (s == d && logp) y = (double)logp[row];
@@ -216,43 +212,8 @@ __global__ __launch_bounds__(256) void cnf_dopri5_kernel(const float* __restrict
   }
 }
 
-// the largest block (256, 128, 64 threads) whose image + strips + state fits 64 KiB, else 64 threads (as cnf_threads
-// of fc_cnf.hip, with a strip per row in place of the block's time table)
-static int cnf_dopri5_strip(const CnfShape& sh) {
-  int m = cnf_pad4(sh.d);
-  for (int l = 1; l < sh.layers; ++l) m = cnf_pad4(sh.w[l]) > m ? cnf_pad4(sh.w[l]) : m;
-  return m;
-}
-
-static int cnf_dopri5_threads(const CnfShape& sh, int image_floats, int group, size_t* lds) {
-  int threads = 256;
-  for (;; threads >>= 1) {
-    *lds = sizeof(float) * ((size_t)image_floats + 2 * (size_t)cnf_max_width(sh) * threads) +
-           sizeof(double) * (size_t)cnf_dopri5_strip(sh) * (size_t)(threads / group);
-    if (*lds <= 64 * 1024 || threads <= 64 || threads <= group) break;
-  }
-  return threads;
-}
-
-template <int G>
-static int launch_cnf_dopri5(const float* z, const float* logp, const float* image, float* z_out, float* logp_out,
-                             int32_t* attempts, float* evals, int64_t n, const CnfShape& sh, int image_floats,
-                             double t0, double t1, double atol, double rtol, double first_step, int max_attempts,
-                             hipStream_t s) {
-  size_t lds;
-  const int threads = cnf_dopri5_threads(sh, image_floats, G, &lds);
-  if (lds > (size_t)kCnfLdsLimit) return hipErrorInvalidConfiguration;
-  static PerDeviceOnce once;
-  const hipError_t e = ensure_max_dynamic_lds(once, reinterpret_cast<const void*>(&cnf_dopri5_kernel<G>), kCnfLdsLimit);
-  if (e != hipSuccess) return e;
-  const int rows = threads / G;
-  int64_t grid = (n + rows - 1) / rows;
-  if (grid > kCnfMaxBlocks) grid = kCnfMaxBlocks;
-  hipLaunchKernelGGL((cnf_dopri5_kernel<G>), dim3((unsigned)grid), dim3(threads), lds, s, z, logp, image, z_out,
-                     logp_out, attempts, evals, n, sh, image_floats, cnf_dopri5_strip(sh), t0, t1, atol, rtol,
-                     first_step, max_attempts);
-  return hipGetLastError();
-}
+// a strip of the widest layer's gates per row in place of the block's time table, and the two ping-pong columns
+static CnfLds cnf_dopri5_lds(const CnfShape& sh) { return {0, 2 * cnf_max_width(sh), cnf_pad4(cnf_max_width(sh))}; }
 
 }  // namespace fc
 
@@ -262,22 +223,21 @@ extern "C" int fc_cnf_dopri5(const float* z, const float* logp, const float* ima
                              float scale_output, float p0, int32_t image_floats, double t0, double t1, double atol,
                              double rtol, double first_step, int32_t max_attempts, void* stream) {
   fc::CnfShape sh;
-  if (n < 0 || max_attempts < 1 || max_attempts > FC_CNF_DOPRI5_MAX_ATTEMPTS) return hipErrorInvalidValue;
+  if (max_attempts < 1 || max_attempts > FC_CNF_DOPRI5_MAX_ATTEMPTS) return hipErrorInvalidValue;
   if (!(t0 - t0 == 0.0) || !(t1 - t1 == 0.0) || !(atol >= 0.0) || !(rtol >= 0.0) || !(atol + rtol > 0.0) ||
       !(first_step >= 0.0) || !(first_step - first_step == 0.0))
     return hipErrorInvalidValue;
-  if (!fc::cnf_shape(d, layers, hidden, layer_kind, activation, residual, scale_output, p0, image_floats, &sh))
+  if (!fc::cnf_entry(n, d, layers, hidden, layer_kind, activation, residual, scale_output, p0, image_floats,
+                     FC_CNF_MAX_HIDDEN_LAYERS + 1, &sh))
     return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
-  if (!z || !image || !z_out || !logp_out || !attempts || z == z_out) return hipErrorInvalidValue;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-#define FC_CNF_GO(G) \
-  return fc::launch_cnf_dopri5<G>(z, logp, image, z_out, logp_out, attempts, evals, n, sh, image_floats, t0, t1, atol, \
-                                  rtol, first_step, max_attempts, s)
-  if (d < 2) FC_CNF_GO(2);
-  if (d < 4) FC_CNF_GO(4);
-  if (d < 8) FC_CNF_GO(8);
-  if (d < 16) FC_CNF_GO(16);
-  FC_CNF_GO(32);
-#undef FC_CNF_GO
+  if (!fc::cnf_operands(z, image, z_out, logp_out) || !attempts) return hipErrorInvalidValue;
+  const fc::CnfLds need = fc::cnf_dopri5_lds(sh);
+  const fc::CnfLaunch plan =
+      fc::cnf_launch_plan(image_floats, fc::cnf_group(sh), need, fc::kCnfPrefer64K, n, fc::kCnfMaxBlocks);
+  return fc::cnf_with_constant<2, 4, 8, 16, 32>(fc::cnf_group(sh), [&](auto g) {
+    return fc::cnf_launch<&fc::cnf_dopri5_kernel<decltype(g)::value>>(
+        plan, static_cast<hipStream_t>(stream), z, logp, image, z_out, logp_out, attempts, evals, n, sh, image_floats,
+        need.row_doubles, t0, t1, atol, rtol, first_step, max_attempts);
+  });
 }

@@ -53,7 +53,15 @@ def cnf_image_floats(d, hidden):
     return sum((5 + widths[l]) * _cnf_pad4(widths[l + 1]) for l in range(len(widths) - 1))
 
 
-def _cnf_operands(rows, image, d, hidden, layer_kind, activation, evals):
+def _cnf_net(d, hidden):
+    """``(d, layers, hidden widths as an int32 array)``, as every C entry point takes a net."""
+    hidden = tuple(int(h) for h in hidden)
+    return d, len(hidden) + 1, (ctypes.c_int32 * max(1, len(hidden)))(*hidden)
+
+
+def _cnf_operands(rows, image, d, hidden, layer_kind, activation, residual, scale_output, p0, evals):
+    """The checked rows and image, and the ten arguments from ``n`` to the image length that follow the pointers in
+    every launching entry point."""
     y = _prep_2d(rows)
     if y.shape[1] != d:
         raise ValueError("flowconductor_amd: rows of %d features for a net of dimension %d" % (y.shape[1], d))
@@ -71,8 +79,31 @@ def _cnf_operands(rows, image, d, hidden, layer_kind, activation, evals):
         raise RuntimeError("flowconductor_amd: image on %s, rows on %s" % (image.device, y.device))
     if evals is not None and (evals.dtype != torch.float32 or evals.device != y.device or evals.numel() != 1):
         raise ValueError("flowconductor_amd: evals must be one float32 word on the device of the rows")
-    widths = (ctypes.c_int32 * max(1, len(hidden)))(*hidden)
-    return y, image, hidden, widths
+    tail = (y.shape[0],) + _cnf_net(d, hidden) + (layer_kind, activation, int(bool(residual)), float(scale_output),
+                                                  float(p0), image.numel())
+    return y, image, tail
+
+
+def _cnf_outputs(y):
+    """``(out [N, d], out1 [N])`` for the rows ``y``."""
+    return torch.empty_like(y), torch.empty(y.shape[0], dtype=torch.float32, device=y.device)
+
+
+def _cnf_time(t, y):
+    if isinstance(t, torch.Tensor):
+        if t.numel() != 1 or t.dtype != torch.float32 or t.device != y.device:
+            raise ValueError("flowconductor_amd: t must be a number or one float32 element on the device of the rows")
+        return 0.0, t
+    return float(t), None
+
+
+def _cnf_logp(logp, z):
+    if logp is None:
+        return None
+    logp = _hip.dev_f32(logp, "logp")
+    if logp.numel() != z.shape[0] or logp.device != z.device:
+        raise ValueError("flowconductor_amd: logp of %d entries for %d rows" % (logp.numel(), z.shape[0]))
+    return logp
 
 
 def cnf_field(t, inputs, image, d, hidden, layer_kind, activation, residual=False, scale_output=1.0, p0=1.0,
@@ -82,20 +113,11 @@ def cnf_field(t, inputs, image, d, hidden, layer_kind, activation, residual=Fals
     No autograd."""
     _hip.require_no_grad(inputs)
     lib = _hip.load()
-    y, image, hidden, widths = _cnf_operands(inputs, image, d, hidden, layer_kind, activation, evals)
-    t_host, t_dev = 0.0, None
-    if isinstance(t, torch.Tensor):
-        if t.numel() != 1 or t.dtype != torch.float32 or t.device != y.device:
-            raise ValueError("flowconductor_amd: t must be a number or one float32 element on the device of the rows")
-        t_dev = t
-    else:
-        t_host = float(t)
-    n = y.shape[0]
-    dy = torch.empty_like(y)
-    negdiv = torch.empty(n, dtype=torch.float32, device=y.device)
+    y, image, tail = _cnf_operands(inputs, image, d, hidden, layer_kind, activation, residual, scale_output, p0, evals)
+    t_host, t_dev = _cnf_time(t, y)
+    dy, negdiv = _cnf_outputs(y)
     _call("fc_cnf_field", lib.fc_cnf_field, y.device, _hip.ptr(y), _hip.ptr(image), _hip.ptr(dy), _hip.ptr(negdiv),
-          _hip.ptr(evals), n, d, len(hidden) + 1, widths, layer_kind, activation, int(bool(residual)),
-          float(scale_output), float(p0), image.numel(), t_host, _hip.ptr(t_dev), _hip.stream_ptr(y.device))
+          _hip.ptr(evals), *tail, t_host, _hip.ptr(t_dev), _hip.stream_ptr(y.device))
     return dy, negdiv
 
 
@@ -106,20 +128,14 @@ def cnf_integrate(inputs, logp, image, d, hidden, layer_kind, activation, t0, t1
     one launch, no host sync.  ``evals``: a float32 device word the launch max-reduces ``steps * stages`` into."""
     _hip.require_no_grad(inputs, logp)
     lib = _hip.load()
-    z, image, hidden, widths = _cnf_operands(inputs, image, d, hidden, layer_kind, activation, evals)
-    n = z.shape[0]
+    z, image, tail = _cnf_operands(inputs, image, d, hidden, layer_kind, activation, residual, scale_output, p0, evals)
     if method not in CNF_STAGES or int(steps) < 1:
         raise ValueError("flowconductor_amd: fc_cnf_integrate takes euler / midpoint / rk4 and at least one step")
-    if logp is not None:
-        logp = _hip.dev_f32(logp, "logp")
-        if logp.numel() != n or logp.device != z.device:
-            raise ValueError("flowconductor_amd: logp of %d entries for %d rows" % (logp.numel(), n))
-    z_out = torch.empty_like(z)
-    logp_out = torch.empty(n, dtype=torch.float32, device=z.device)
+    logp = _cnf_logp(logp, z)
+    z_out, logp_out = _cnf_outputs(z)
     _call("fc_cnf_integrate", lib.fc_cnf_integrate, z.device, _hip.ptr(z), _hip.ptr(logp), _hip.ptr(image),
-          _hip.ptr(z_out), _hip.ptr(logp_out), _hip.ptr(evals), n, d, len(hidden) + 1, widths, layer_kind, activation,
-          int(bool(residual)), float(scale_output), float(p0), image.numel(), float(t0), float(t1), int(steps),
-          int(method), _hip.stream_ptr(z.device))
+          _hip.ptr(z_out), _hip.ptr(logp_out), _hip.ptr(evals), *tail, float(t0), float(t1), int(steps), int(method),
+          _hip.stream_ptr(z.device))
     return z_out, logp_out
 
 
@@ -167,8 +183,7 @@ def cnf_dopri5(inputs, logp, image, d, hidden, layer_kind, activation, t0, t1, a
     ``first_step``)."""
     _hip.require_no_grad(inputs, logp)
     lib = _hip.load()
-    z, image, hidden, widths = _cnf_operands(inputs, image, d, hidden, layer_kind, activation, evals)
-    n = z.shape[0]
+    z, image, tail = _cnf_operands(inputs, image, d, hidden, layer_kind, activation, residual, scale_output, p0, evals)
     if not 1 <= int(max_attempts) <= CNF_DOPRI5_MAX_ATTEMPTS:
         raise ValueError("flowconductor_amd: fc_cnf_dopri5 takes max_attempts in 1 .. %d" % CNF_DOPRI5_MAX_ATTEMPTS)
     atol, rtol = float(atol), float(rtol)
@@ -177,16 +192,11 @@ def cnf_dopri5(inputs, logp, image, d, hidden, layer_kind, activation, t0, t1, a
     step = 0.0 if first_step is None else float(first_step)
     if first_step is not None and not 0.0 < step < float("inf"):
         raise ValueError("flowconductor_amd: fc_cnf_dopri5 takes a positive finite first_step")
-    if logp is not None:
-        logp = _hip.dev_f32(logp, "logp")
-        if logp.numel() != n or logp.device != z.device:
-            raise ValueError("flowconductor_amd: logp of %d entries for %d rows" % (logp.numel(), n))
-    z_out = torch.empty_like(z)
-    logp_out = torch.empty(n, dtype=torch.float32, device=z.device)
-    attempts = torch.empty(n, dtype=torch.int32, device=z.device)
+    logp = _cnf_logp(logp, z)
+    z_out, logp_out = _cnf_outputs(z)
+    attempts = torch.empty(z.shape[0], dtype=torch.int32, device=z.device)
     _call("fc_cnf_dopri5", lib.fc_cnf_dopri5, z.device, _hip.ptr(z), _hip.ptr(logp), _hip.ptr(image), _hip.ptr(z_out),
-          _hip.ptr(logp_out), _hip.ptr(attempts), _hip.ptr(evals), n, d, len(hidden) + 1, widths, layer_kind, activation,
-          int(bool(residual)), float(scale_output), float(p0), image.numel(), float(t0), float(t1), atol, rtol, step,
+          _hip.ptr(logp_out), _hip.ptr(attempts), _hip.ptr(evals), *tail, float(t0), float(t1), atol, rtol, step,
           int(max_attempts), _hip.stream_ptr(z.device))
     return z_out, logp_out, attempts
 
@@ -222,8 +232,8 @@ def cnf_train_rows_pay(n, d, hutchinson):
     return cnf_train_lanes(n, d, hutchinson) <= CNF_TRAIN_MAX_LANES
 
 
-def _cnf_train_operands(rows, e, image, d, hidden, layer_kind, activation, evals):
-    y, image, hidden, widths = _cnf_operands(rows, image, d, hidden, layer_kind, activation, evals)
+def _cnf_train_operands(rows, e, image, d, hidden, layer_kind, activation, residual, scale_output, p0, evals):
+    y, image, tail = _cnf_operands(rows, image, d, hidden, layer_kind, activation, residual, scale_output, p0, evals)
     if not cnf_train_supported(d, hidden):
         raise ValueError("flowconductor_amd: the CNF training kernels take at most %d hidden layers"
                          % CNF_TRAIN_MAX_HIDDEN_LAYERS)
@@ -231,23 +241,12 @@ def _cnf_train_operands(rows, e, image, d, hidden, layer_kind, activation, evals
         if not (isinstance(e, torch.Tensor) and e.dtype == torch.float32 and e.device == y.device
                 and e.shape == y.shape and e.is_contiguous()):
             raise ValueError("flowconductor_amd: e must be contiguous float32 [N, D] on the device of the rows")
-    return y, image, hidden, widths
-
-
-def _cnf_time(t, y):
-    if isinstance(t, torch.Tensor):
-        if t.numel() != 1 or t.dtype != torch.float32 or t.device != y.device:
-            raise ValueError("flowconductor_amd: t must be a number or one float32 element on the device of the rows")
-        return 0.0, t
-    return float(t), None
+    return y, image, tail
 
 
 def cnf_backward_rows(d, hidden, hutchinson):
     """Rows one block of ``fc_cnf_field_backward`` carries (its sums over rows are per block, then over blocks)."""
-    lib = _hip.load()
-    hidden = tuple(int(h) for h in hidden)
-    widths = (ctypes.c_int32 * max(1, len(hidden)))(*hidden)
-    rows = lib.fc_cnf_field_backward_rows(d, len(hidden) + 1, widths, int(bool(hutchinson)))
+    rows = _hip.load().fc_cnf_field_backward_rows(*_cnf_net(d, hidden), int(bool(hutchinson)))
     if rows < 1:
         raise ValueError("flowconductor_amd: cnf_backward_rows: outside the kernel's limits")
     return rows
@@ -259,14 +258,12 @@ def cnf_field_train(t, inputs, e, image, d, hidden, layer_kind, activation, resi
     Hutchinson's estimate ``e^T (df/dy) e``, with None the exact one.  No autograd (``_CnfFieldFunction`` has it)."""
     _hip.require_no_grad(inputs)
     lib = _hip.load()
-    y, image, hidden, widths = _cnf_train_operands(inputs, e, image, d, hidden, layer_kind, activation, evals)
+    y, image, tail = _cnf_train_operands(inputs, e, image, d, hidden, layer_kind, activation, residual, scale_output,
+                                         p0, evals)
     t_host, t_dev = _cnf_time(t, y)
-    n = y.shape[0]
-    dy = torch.empty_like(y)
-    negdiv = torch.empty(n, dtype=torch.float32, device=y.device)
+    dy, negdiv = _cnf_outputs(y)
     _call("fc_cnf_field_train", lib.fc_cnf_field_train, y.device, _hip.ptr(y), _hip.ptr(e), _hip.ptr(image), _hip.ptr(dy),
-          _hip.ptr(negdiv), _hip.ptr(evals), n, d, len(hidden) + 1, widths, layer_kind, activation, int(bool(residual)),
-          float(scale_output), float(p0), image.numel(), t_host, _hip.ptr(t_dev), _hip.stream_ptr(y.device))
+          _hip.ptr(negdiv), _hip.ptr(evals), *tail, t_host, _hip.ptr(t_dev), _hip.stream_ptr(y.device))
     return dy, negdiv
 
 
@@ -276,7 +273,8 @@ def cnf_field_backward(t, inputs, e, image, g_dy, g_negdiv, d, hidden, layer_kin
     negdiv)`` for the outputs of ``cnf_field_train`` at the same arguments; ``g_image`` in the image's layout, summed
     over the rows in a fixed order (bitwise reproducible)."""
     lib = _hip.load()
-    y, image, hidden, widths = _cnf_train_operands(inputs, e, image, d, hidden, layer_kind, activation, None)
+    y, image, tail = _cnf_train_operands(inputs, e, image, d, hidden, layer_kind, activation, residual, scale_output,
+                                         p0, None)
     t_host, t_dev = _cnf_time(t, y)
     n = y.shape[0]
     g_dy = _hip.dev_f32(g_dy, "g_dy")
@@ -284,16 +282,15 @@ def cnf_field_backward(t, inputs, e, image, g_dy, g_negdiv, d, hidden, layer_kin
     if g_dy.shape != y.shape or g_negdiv.numel() != n or g_dy.device != y.device or g_negdiv.device != y.device:
         raise ValueError("flowconductor_amd: cnf_field_backward: g_dy / g_negdiv do not belong to the rows")
     with torch.cuda.device(y.device):
-        floats = lib.fc_cnf_field_backward_workspace(n, d, len(hidden) + 1, widths, int(e is not None))
+        floats = lib.fc_cnf_field_backward_workspace(*tail[:4], int(e is not None))
     if floats < 0:
         raise ValueError("flowconductor_amd: cnf_field_backward: outside the kernel's limits")
     workspace = torch.empty(max(floats // 2, 1), dtype=torch.float64, device=y.device)
     g_y = torch.empty_like(y)
     g_image = torch.empty_like(image)
     _call("fc_cnf_field_backward", lib.fc_cnf_field_backward, y.device, _hip.ptr(y), _hip.ptr(e), _hip.ptr(image),
-          _hip.ptr(g_dy), _hip.ptr(g_negdiv), _hip.ptr(g_y), _hip.ptr(g_image), _hip.ptr(workspace), n, d,
-          len(hidden) + 1, widths, layer_kind, activation, int(bool(residual)), float(scale_output), float(p0),
-          image.numel(), t_host, _hip.ptr(t_dev), _hip.stream_ptr(y.device))
+          _hip.ptr(g_dy), _hip.ptr(g_negdiv), _hip.ptr(g_y), _hip.ptr(g_image), _hip.ptr(workspace), *tail, t_host,
+          _hip.ptr(t_dev), _hip.stream_ptr(y.device))
     return g_y, g_image
 
 
