@@ -108,6 +108,7 @@ SIGNATURES = {
     "fc_deep_sigmoid_backward": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _F, _I32, _P],
     "fc_deep_sigmoid_backward_rows": [_I64, _I32, _I32],
     "fc_tile_route": [_I64, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_I64)],
+    "fc_hidden_route": [_I32, _I64, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_I64)],
     "fc_planar_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P],
     "fc_sylvester_mid_backward": [_P, _P, _P, _P, _P, _P, _I64, _I32, _P],
     "fc_householder_backward": [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P],

@@ -39,6 +39,7 @@
 #include "fc_lane.h"
 #include "fc_math.h"
 #include "fc_device.h"
+#include "fc_hidden_route.h"
 #include "../../include/flowcon_hip.h"
 
 #ifndef FC_HIDDEN_PREFETCH_X
@@ -95,6 +96,7 @@ struct HiddenLds {
   static constexpr int kFragsMain = kFrag0 + (2 * NB + kTail) * kFragL;
   static constexpr int kFrags = kFragsMain + kCtxLayers * kFragG;
   static constexpr size_t kBytes = (size_t)kFrags * 64 * 16 + kLayers * 64 * 4 + 16 * 4 + 32 * K0S * 4 + 16 * 8 * 4;
+  static_assert(kBytes == hidden_image_bytes(NB, K0S, kCtx, kTail), "the launch decision counts another image");
   static_assert(kLayers <= 16, "wun holds 16 entries");
   static_assert(kBytes <= 160 * 1024, "weight fragments exceed the CU's LDS");
 };
@@ -727,8 +729,9 @@ hipError_t launch_hidden(const HiddenArgs& a, int64_t grid, hipStream_t s) {
   if (ea != hipSuccess) return ea;
   if (kTail && a.D > 16 * XVT) return hipErrorInvalidValue;
   // (tail kernels: + a [16][D | 1] float tile per wave)
-  const size_t lds = kTail ? ((L::kBytes + 15) & ~size_t(15)) + (size_t)(kHidThreads / 64) * BPW * 16 * (a.D | 1) * 4 : L::kBytes;
-  if (lds > 160 * 1024) return hipErrorInvalidConfiguration;
+  static_assert(kHidThreads / 64 == kHidWaves, "fc_hidden_route.h counts the waves of this workgroup");
+  const size_t lds = kTail ? tail_lds_bytes(L::kBytes, BPW, a.D) : L::kBytes;
+  if (lds > kLdsPerCu) return hipErrorInvalidConfiguration;
   hipLaunchKernelGGL((resnet_hidden_kernel<NB, K0S, kCtx, kAct, BPW, kTail, XVT>), dim3((unsigned)grid), dim3(kHidThreads), lds,
                      s, a);
   return hipGetLastError();
@@ -738,20 +741,12 @@ hipError_t launch_hidden(const HiddenArgs& a, int64_t grid, hipStream_t s) {
 // would not fit in LDS), one workgroup per CU
 template <int NB, int K0S>
 inline hipError_t launch_coupling_tail(const HiddenArgs& a, hipStream_t s) {
-  // two blocks per wave when there is work for them (>= two rounds of single blocks over the chip) and the second row
-  // tile fits next to the weight image; the last group of an odd block count computes its block twice
-  using L = HiddenLds<NB, K0S, 0, 1>;
-  const int64_t cus = device_cu_count();
-  const size_t lds2 = ((L::kBytes + 15) & ~size_t(15)) + (size_t)(kHidThreads / 64) * 2 * 16 * (a.D | 1) * 4;
-  const bool pairs = a.blocks16 >= 2 * cus * 8 && lds2 <= 160 * 1024 && a.D <= 64;   // (wider rows: the second block's pieces spill)
-  const int64_t units = pairs ? (a.blocks16 + 1) / 2 : a.blocks16;
-  int64_t grid = cus;
-  const int64_t need = (units + 7) / 8;
-  if (grid > need) grid = need;
-  if (!pairs) return launch_hidden<NB, K0S, 0, 0, 1, 1>(a, grid, s);
-  // (the two-block kernels carry 2 x XVT row pieces per lane across the layers: instantiated per input width)
-  if (a.D <= 32) return launch_hidden<NB, K0S, 0, 0, 2, 1, 2>(a, grid, s);
-  return launch_hidden<NB, K0S, 0, 0, 2, 1, 4>(a, grid, s);
+  // coupling_tail_route (fc_hidden_route.h) decides: one or two blocks per wave (the last group of an odd block count
+  // computes its block twice), the row pieces per lane of the two-block kernels, the grid
+  const HiddenRoute r = coupling_tail_route(a.blocks16, a.D, NB, K0S, device_cu_count());
+  if (r.bpw == 1) return launch_hidden<NB, K0S, 0, 0, 1, 1>(a, r.grid, s);
+  if (r.xvt == 2) return launch_hidden<NB, K0S, 0, 0, 2, 1, 2>(a, r.grid, s);
+  return launch_hidden<NB, K0S, 0, 0, 2, 1, 4>(a, r.grid, s);
 }
 
 // the affine coupling layer in one kernel: ReLU conditioner, <= 3 blocks (the image of 4 blocks + the final layer
@@ -785,10 +780,7 @@ hipError_t dispatch_hidden(const HiddenArgs& a, int num_blocks, hipStream_t s) {
 #else
   const bool pairs = false;
 #endif
-  const size_t frags = (size_t)(wide ? 16 : 8) + (size_t)num_blocks * (2 * 16 + (kCtx ? 8 : 0));   // 1 KB each
-  int64_t grid = (int64_t)cus * (!pairs && !kCtx && frags * 1024 + 2048 <= 80 * 1024 ? 2 : 1);
-  const int64_t need = ((pairs ? (a.blocks16 + 1) / 2 : a.blocks16) + 7) / 8;
-  if (grid > need) grid = need;
+  const int64_t grid = hidden_stack_route(kCtx, a.blocks16, a.k0 + (kCtx == 1 ? a.C : 0), num_blocks, cus, pairs).grid;
 #ifdef FC_HID_FORCE_BPW
 #define FC_HIDDEN_CASE(NB_, K0S_)                                                            \
   do {                                                                                       \

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fc_device.h"
+#include "fc_hidden_route.h"
 #include "fc_lane.h"
 #include "fc_math.h"
 #include "fc_split.h"
@@ -266,15 +267,14 @@ __global__ __launch_bounds__(kWThreads, FC_WIDE_WAVES) void resnet_hidden_wide_k
 template <int HQ, bool kRelu>
 static hipError_t launch_wide(const WideArgs& a, hipStream_t s) {
   constexpr int H = 64 * HQ;
-  const size_t lds = (size_t)2 * kWR * (H + 8) * 2 + kWR * 4 + 2 * kWR * 4 + 64 * 4;
+  static_assert(kWR == 64, "wide_lds_bytes (fc_hidden_route.h) counts 64-row tiles");
+  const HiddenRoute r = wide_route(a.tiles, H, device_cu_count());
   static PerDeviceOnce attr;
   const hipError_t ea = ensure_max_dynamic_lds(attr, reinterpret_cast<const void*>(&resnet_hidden_wide_kernel<HQ, kRelu>),
                                                160 * 1024);
   if (ea != hipSuccess) return ea;
   // two workgroups per CU where two activation images fit (H = 128: 35 KB each; H = 256: 68 KB each)
-  int64_t grid = (int64_t)device_cu_count() * 2;
-  if (grid > a.tiles) grid = a.tiles;
-  hipLaunchKernelGGL((resnet_hidden_wide_kernel<HQ, kRelu>), dim3((unsigned)grid), dim3(kWThreads), lds, s, a);
+  hipLaunchKernelGGL((resnet_hidden_wide_kernel<HQ, kRelu>), dim3((unsigned)r.grid), dim3(kWThreads), r.lds, s, a);
   return hipGetLastError();
 }
 

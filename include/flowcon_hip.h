@@ -801,6 +801,32 @@ int fc_deep_sigmoid_backward_rows(int64_t n, int32_t d, int32_t n_sigmoids);
 int fc_tile_route(int64_t n, int32_t d, int32_t d_t, int32_t rowlen, int32_t shared_params, int32_t aligned16,
                   int64_t* out);
 
+/* ---- launch route of the hidden-stack kernels ----------------------------------------------------- */
+/* What fc_resnet_hidden / fc_resnet_hidden_packed (FC_ROUTE_HIDDEN), fc_resnet_hidden_context (FC_ROUTE_HIDDEN_GLU,
+ * FC_ROUTE_HIDDEN_ADDITIVE), fc_affine_coupling_resnet (FC_ROUTE_COUPLING_TAIL) and fc_resnet_hidden_wide
+ * (FC_ROUTE_HIDDEN_WIDE) launch for n rows of d floats, decided by the very host functions those entries call.  The
+ * arguments are those of the entry: in_features identity columns, context_features (0 for the kinds without a context),
+ * num_blocks, hidden (64; 128 or 256 for the wide kernel).  No kernel runs; the only device query is the CU count of the
+ * current device (256 without one).  out[8]:
+ *   out[0]  16-row blocks a wave pushes through the layers together: 1 or 2 (wide kernel: the 4 blocks of a 64-row tile)
+ *   out[1]  coupling tail: 16-byte pieces of a 16-row chunk of x per lane (8 at one block per wave; 2 at d <= 32 and 4 at
+ *           d <= 64 at two), 0 for the other kinds
+ *   out[2]  grid (512-thread workgroups)      out[3]  waves = 8 grid
+ *   out[4]  dynamic LDS bytes per workgroup
+ *   out[5]  passes: the largest number of groups of out[0] blocks any wave walks (wide kernel: tiles any workgroup walks)
+ *   out[6]  1 where the last group repeats a block (two blocks per wave, odd number of blocks)
+ *   out[7]  the return value
+ * Returns 0, hipErrorInvalidValue for a shape the entry refuses, or hipErrorInvalidConfiguration where the LDS of the
+ * route exceeds 160 KB -- what the entry returns for that shape before it launches.  n == 0: 0 with nothing to launch.
+ * Added under ABI version 3 (it changes no existing entry). */
+#define FC_ROUTE_HIDDEN 0
+#define FC_ROUTE_HIDDEN_GLU 1
+#define FC_ROUTE_HIDDEN_ADDITIVE 2
+#define FC_ROUTE_COUPLING_TAIL 3
+#define FC_ROUTE_HIDDEN_WIDE 4
+int fc_hidden_route(int32_t kind, int64_t n, int32_t d, int32_t in_features, int32_t context_features,
+                    int32_t num_blocks, int32_t hidden, int64_t* out);
+
 /* ---- unconstrained monotonic neural networks (Clenshaw-Curtis integral of an MLP) --------------- */
 /* z[n, j] = h[n, j, 0] + int_0^x f(t, h[n, j, :]) dt with f = ELU(MLP(t, h)) + 1 and the quadrature
  *   z = h_0 + (x / 2) sum_i w_i f((x / 2)(s_i + 1), h),  s_i = cos(i pi / nb_steps), i = 0..nb_steps,

@@ -158,12 +158,17 @@ def _f64(t):
     return t.detach().cpu().double()
 
 
+def row_error(got, ref64):
+    """Per-row error of one quantity, ``[N, H]`` or ``[N]``, relative to the row's own scale (float64, on the CPU)."""
+    got, ref64 = _f64(got), _f64(ref64)
+    if ref64.dim() == 1:
+        return (got - ref64).abs() / ref64.abs().clamp(min=1.0)
+    return (got - ref64).abs().amax(dim=1) / ref64.abs().amax(dim=1).clamp(min=1.0)
+
+
 def row_errors(y, lad, y64, lad64):
     """``(e_y, e_l)``: per-row errors relative to the row's own scale (float64, on the CPU)."""
-    y, lad, y64, lad64 = _f64(y), _f64(lad), _f64(y64), _f64(lad64)
-    e_y = (y - y64).abs().amax(dim=1) / y64.abs().amax(dim=1).clamp(min=1.0)
-    e_l = (lad - lad64).abs() / lad64.abs().clamp(min=1.0)
-    return e_y, e_l
+    return row_error(y, y64), row_error(lad, lad64)
 
 
 def summary(e):
@@ -180,27 +185,33 @@ def check_fixture(y64, lad64):
     assert share <= LARGE_ROW_SHARE, "fixture: %.2f %% of the rows exceed %g in float64" % (100 * share, LARGE_ROW)
 
 
+def quantity_violations(what, got, ref32, ref64):
+    """The bound on ONE quantity (``[N, H]`` or ``[N]``, the float64 reference finite): ``(messages of the violated
+    conditions, (got's summary, float32 oracle's summary))``."""
+    se, sf = summary(row_error(got, ref64)), summary(row_error(ref32, ref64))
+    bad = []
+    if not bool(torch.isfinite(_f64(got)).all()):
+        bad.append("%s: non-finite output where the float64 oracle is finite" % what)
+    for name, e, f in zip(("p50", "p90", "p99"), se, sf):
+        if not e <= MULTIPLE * f + ULP:
+            bad.append("%s %s: %.3g > 4 x %.3g + 2^-23" % (what, name, e, f))
+    if not se[3] <= MULTIPLE * sf[3] + MAX_SLACK:
+        bad.append("%s max: %.3g > 4 x %.3g + 1e-5" % (what, se[3], sf[3]))
+    return bad, (se, sf)
+
+
 def violations(got_y, got_lad, y32, lad32, y64, lad64):
     """``(messages of the violated conditions, {what: (got's summary, float32 oracle's summary)})``."""
-    e = dict(zip(("y", "lad"), row_errors(got_y, got_lad, y64, lad64)))
-    f = dict(zip(("y", "lad"), row_errors(y32, lad32, y64, lad64)))
     bad, stats = [], {}
-    if not (bool(torch.isfinite(_f64(got_y)).all()) and bool(torch.isfinite(_f64(got_lad)).all())):
-        bad.append("non-finite output where the float64 oracle is finite")
-    for what in ("y", "lad"):
-        se, sf = summary(e[what]), summary(f[what])
-        stats[what] = (se, sf)
-        for name, got, ref in zip(("p50", "p90", "p99"), se, sf):
-            if not got <= MULTIPLE * ref + ULP:
-                bad.append("%s %s: %.3g > 4 x %.3g + 2^-23" % (what, name, got, ref))
-        if not se[3] <= MULTIPLE * sf[3] + MAX_SLACK:
-            bad.append("%s max: %.3g > 4 x %.3g + 1e-5" % (what, se[3], sf[3]))
+    for what, got, ref32, ref64 in (("y", got_y, y32, y64), ("lad", got_lad, lad32, lad64)):
+        b, stats[what] = quantity_violations(what, got, ref32, ref64)
+        bad += b
     return bad, stats
 
 
 def format_stats(label, stats):
     return "  ".join("%s %s p50 %.2e p90 %.2e p99 %.2e max %.2e (f32 oracle %.2e %.2e %.2e %.2e)"
-                     % ((label, what) + stats[what][0] + stats[what][1]) for what in ("y", "lad"))
+                     % ((label, what) + stats[what][0] + stats[what][1]) for what in stats)
 
 
 def check_routes(label, routes, y32, lad32, y64, lad64):
