@@ -9,11 +9,12 @@ extern "C" int fc_made_inverse_spline(const float* z, float* y, float* logabsdet
                                       uint32_t* err_flag, int64_t n, int32_t d, int32_t num_blocks, const fc_spline_config* cfg,
                                       int32_t lad_flags, void* stream) {
   if (!cfg || cfg->num_bins < 1 || cfg->num_bins > 48) return hipErrorInvalidValue;
-  const int32_t k = cfg->num_bins;
+  const int32_t per_dim = fc::spline_params_per_dim(cfg->kind, cfg->num_bins, cfg->tails);
+  if (per_dim < 0) return hipErrorInvalidValue;
   fc::SplineParams q = fc::spline_params_from_config(*cfg);
   q.inverse = 1;
-  // the form's parameters per dim and its unit's dispatcher, behind the shared checks
-  auto run = [&](int32_t per_dim, auto op, auto dispatch) -> int {
+  // the form's unit's dispatcher, behind the shared checks
+  auto run = [&](auto op, auto dispatch) -> int {
     fc::MadeFormArgs<decltype(op)> a{{}, op};
     bool rows;
     const hipError_t e = fc::made_args_prepare(a, z, y, logabsdet, hidden_frag, hidden_unscale, hidden_bias, final_frag, final_unscale,
@@ -22,9 +23,9 @@ extern "C" int fc_made_inverse_spline(const float* z, float* y, float* logabsdet
     return (e != hipSuccess || !rows) ? e : dispatch(a, num_blocks, static_cast<hipStream_t>(stream));
   };
   switch (cfg->kind) {
-    case FC_SPLINE_LINEAR: return run(k, fc::LinearSplineOp{q}, fc::dispatch_made_spline_linear);
-    case FC_SPLINE_QUADRATIC: return run(cfg->tails ? 2 * k - 1 : 2 * k + 1, fc::QuadraticSplineOp{q}, fc::dispatch_made_spline_quadratic);
-    case FC_SPLINE_CUBIC: return run(2 * k + 2, fc::CubicSplineOp{q}, fc::dispatch_made_spline_cubic);
+    case FC_SPLINE_LINEAR: return run(fc::LinearSplineOp{q}, fc::dispatch_made_spline_linear);
+    case FC_SPLINE_QUADRATIC: return run(fc::QuadraticSplineOp{q}, fc::dispatch_made_spline_quadratic);
+    case FC_SPLINE_CUBIC: return run(fc::CubicSplineOp{q}, fc::dispatch_made_spline_cubic);
     default: return hipErrorInvalidValue;
   }
 }

@@ -19,40 +19,21 @@ extern "C" int fc_piecewise_spline(const float* x, float* y, const float* params
                                    void* stream) {
   if (!cfg || n < 0 || d <= 0 || d_t <= 0 || d_t > d || cfg->num_bins <= 0) return hipErrorInvalidValue;
   if (n > 0 && (!x || !y || !params)) return hipErrorInvalidValue;
-  fc::SplineParams q;
-  q.K = cfg->num_bins;
-  q.tails = cfg->tails;
-  q.inverse = cfg->inverse;
-  q.left = cfg->left; q.right = cfg->right; q.bottom = cfg->bottom; q.top = cfg->top;
-  q.min_w = (float)cfg->min_bin_width;
-  q.min_h = (float)cfg->min_bin_height;
-  q.cw = (float)(1.0 - cfg->min_bin_width * q.K);
-  q.ch = (float)(1.0 - cfg->min_bin_height * q.K);
-  q.w_div = cfg->width_divisor > 0.f ? cfg->width_divisor : 1.f;
-  q.h_div = cfg->height_divisor > 0.f ? cfg->height_divisor : 1.f;
-  q.eps = cfg->cubic_eps;
-  q.quad_thresh = cfg->cubic_quadratic_threshold;
+  const int per_dim = fc::spline_params_per_dim(cfg->kind, cfg->num_bins, cfg->tails);
+  if (per_dim < 0) return hipErrorInvalidValue;
+  const fc::SplineParams q = fc::spline_params_from_config(*cfg);
 
   fc::TileArgs a{};
   a.x = x; a.y = y; a.params = params; a.cols = cols; a.logabsdet = logabsdet; a.err = err_flag;
   a.N = n; a.D = d; a.d_t = d_t;
+  a.rowlen = d_t * per_dim;
   a.shared_params = shared_params;
   a.lad_mode = lad_mode;
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (cfg->kind) {
-    case FC_SPLINE_LINEAR: {
-      a.rowlen = d_t * q.K;
-      return fc::launch_tile(fc::LinearSplineOp{q}, a, s);
-    }
-    case FC_SPLINE_QUADRATIC: {
-      a.rowlen = d_t * (q.tails ? 2 * q.K - 1 : 2 * q.K + 1);
-      return fc::launch_tile(fc::QuadraticSplineOp{q}, a, s);
-    }
-    case FC_SPLINE_CUBIC: {
-      a.rowlen = d_t * (2 * q.K + 2);
-      return fc::launch_tile(fc::CubicSplineOp{q}, a, s);
-    }
-    default:
-      return hipErrorInvalidValue;
+    case FC_SPLINE_LINEAR: return fc::launch_tile(fc::LinearSplineOp{q}, a, s);
+    case FC_SPLINE_QUADRATIC: return fc::launch_tile(fc::QuadraticSplineOp{q}, a, s);
+    case FC_SPLINE_CUBIC: return fc::launch_tile(fc::CubicSplineOp{q}, a, s);
+    default: return hipErrorInvalidValue;
   }
 }

@@ -14,7 +14,7 @@ from flowconductor_amd.transforms import fused_rq
 from flowconductor_amd.transforms import made as made_module
 from flowconductor_amd.transforms.adaptive_sigmoids import DeepSigmoidModule
 from flowconductor_amd.transforms.UMNN import MonotonicNormalizer
-from flowconductor_amd.transforms.base import Transform
+from flowconductor_amd.transforms.base import Transform, divisor_if_hidden_features
 
 
 class AutoregressiveTransform(Transform):
@@ -537,10 +537,6 @@ class MaskedUMNNAutoregressiveTransform(AutoregressiveTransform):
                                                      inverse=True)
 
 
-def _ar_divisor(net):
-    return float(np.sqrt(net.hidden_features)) if hasattr(net, "hidden_features") else 1.0
-
-
 class MaskedPiecewiseLinearAutoregressiveTransform(AutoregressiveTransform):
     """Piecewise-linear AR layer on [0, 1] (autoregressive.py:321-372)."""
 
@@ -554,7 +550,7 @@ class MaskedPiecewiseLinearAutoregressiveTransform(AutoregressiveTransform):
         super().__init__(made)
 
     def _output_dim_multiplier(self):
-        return self.num_bins
+        return ops.spline_multiplier(ops.SPLINE_LINEAR, self.num_bins, None)
 
     def _elementwise(self, inputs, autoregressive_params, inverse=False):
         return ops.piecewise_spline_autograd(inputs, autoregressive_params, None, kind=ops.SPLINE_LINEAR,
@@ -590,9 +586,7 @@ class MaskedPiecewiseQuadraticAutoregressiveTransform(AutoregressiveTransform):
         super().__init__(made)
 
     def _output_dim_multiplier(self):
-        if self.tails == "linear":
-            return self.num_bins * 2 - 1
-        return self.num_bins * 2 + 1
+        return ops.spline_multiplier(ops.SPLINE_QUADRATIC, self.num_bins, self.tails)
 
     def _elementwise(self, inputs, autoregressive_params, inverse=False):
         if self.tails not in (None, "linear"):
@@ -600,7 +594,7 @@ class MaskedPiecewiseQuadraticAutoregressiveTransform(AutoregressiveTransform):
         return ops.piecewise_spline_autograd(inputs, autoregressive_params, None, kind=ops.SPLINE_QUADRATIC,
                                     num_bins=self.num_bins, tails=self.tails, tail_bound=self.tail_bound,
                                     min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
-                                    width_divisor=_ar_divisor(self.autoregressive_net), inverse=inverse)
+                                    width_divisor=divisor_if_hidden_features(self.autoregressive_net), inverse=inverse)
 
     def _device_loop_form(self):
         if self.tails not in (None, "linear"):
@@ -608,7 +602,7 @@ class MaskedPiecewiseQuadraticAutoregressiveTransform(AutoregressiveTransform):
         return (ops.MADE_SPLINE, self._output_dim_multiplier(),
                 dict(kind=ops.SPLINE_QUADRATIC, num_bins=self.num_bins, tails=self.tails, tail_bound=self.tail_bound,
                      min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
-                     width_divisor=_ar_divisor(self.autoregressive_net)))
+                     width_divisor=divisor_if_hidden_features(self.autoregressive_net)))
 
     def _elementwise_forward(self, inputs, autoregressive_params):
         return self._elementwise(inputs, autoregressive_params)
@@ -630,16 +624,16 @@ class MaskedPiecewiseCubicAutoregressiveTransform(AutoregressiveTransform):
         super().__init__(made)
 
     def _output_dim_multiplier(self):
-        return self.num_bins * 2 + 2
+        return ops.spline_multiplier(ops.SPLINE_CUBIC, self.num_bins, None)
 
     def _elementwise(self, inputs, autoregressive_params, inverse=False):
-        div = _ar_divisor(self.autoregressive_net)
+        div = divisor_if_hidden_features(self.autoregressive_net)
         return ops.piecewise_spline_autograd(inputs, autoregressive_params, None, kind=ops.SPLINE_CUBIC,
                                     num_bins=self.num_bins, width_divisor=div, height_divisor=div,
                                     inverse=inverse)
 
     def _device_loop_form(self):
-        div = _ar_divisor(self.autoregressive_net)
+        div = divisor_if_hidden_features(self.autoregressive_net)
         return (ops.MADE_SPLINE, self._output_dim_multiplier(),
                 dict(kind=ops.SPLINE_CUBIC, num_bins=self.num_bins, width_divisor=div, height_divisor=div))
 

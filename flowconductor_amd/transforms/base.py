@@ -33,6 +33,12 @@ def own_autograd_check(fn):
     return fn
 
 
+def divisor_if_hidden_features(net):
+    """sqrt(hidden_features) of a conditioner that exposes it, else 1: only ``hidden_features`` triggers the scaling of the
+    unnormalised widths / heights in the sibling-spline layers (coupling.py:438-440, :483-485; autoregressive.py:375-526)."""
+    return float(np.sqrt(net.hidden_features)) if hasattr(net, "hidden_features") else 1.0
+
+
 class Transform(nn.Module):
     """Base class for all transform objects."""
 

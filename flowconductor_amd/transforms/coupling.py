@@ -14,7 +14,7 @@ import torch
 
 from flowconductor_amd import ops, options
 from flowconductor_amd.transforms import fused_rq
-from flowconductor_amd.transforms.base import Transform
+from flowconductor_amd.transforms.base import Transform, divisor_if_hidden_features
 from flowconductor_amd.transforms.UMNN import MonotonicNormalizer
 
 
@@ -655,11 +655,6 @@ class _FusedRQCouplingFunction(torch.autograd.Function):
         return (None, g[:n]) + grads
 
 
-def _divisor_if_hidden_features(net):
-    """Only ``hidden_features`` triggers the scaling in the linear-tailed siblings (coupling.py:438-440, :483-485)."""
-    return float(np.sqrt(net.hidden_features)) if hasattr(net, "hidden_features") else 1.0
-
-
 class PiecewiseLinearCouplingTransform(PiecewiseCouplingTransform):
     """Piecewise-linear CDF coupling (Mueller et al. 2018; coupling.py:299-353)."""
 
@@ -679,7 +674,7 @@ class PiecewiseLinearCouplingTransform(PiecewiseCouplingTransform):
         super().__init__(mask, transform_net_create_fn, unconditional_transform=unconditional_transform)
 
     def _transform_dim_multiplier(self):
-        return self.num_bins
+        return ops.spline_multiplier(ops.SPLINE_LINEAR, self.num_bins, self.tails)
 
     def _coupling_kernel(self, inputs, transform_params, inverse):
         return ops.piecewise_spline_autograd(inputs, transform_params, self._cols(inputs.device), kind=ops.SPLINE_LINEAR,
@@ -713,7 +708,7 @@ class PiecewiseQuadraticCouplingTransform(PiecewiseCouplingTransform):
         return ops.spline_multiplier(ops.SPLINE_QUADRATIC, self.num_bins, self.tails)
 
     def _coupling_kernel(self, inputs, transform_params, inverse):
-        div = _divisor_if_hidden_features(self.transform_net)
+        div = divisor_if_hidden_features(self.transform_net)
         return ops.piecewise_spline_autograd(inputs, transform_params, self._cols(inputs.device),
                                     kind=ops.SPLINE_QUADRATIC, num_bins=self.num_bins, tails=self.tails,
                                     tail_bound=self.tail_bound, min_bin_width=self.min_bin_width,
@@ -744,10 +739,10 @@ class PiecewiseCubicCouplingTransform(PiecewiseCouplingTransform):
         super().__init__(mask, transform_net_create_fn, unconditional_transform=unconditional_transform)
 
     def _transform_dim_multiplier(self):
-        return self.num_bins * 2 + 2
+        return ops.spline_multiplier(ops.SPLINE_CUBIC, self.num_bins, self.tails)
 
     def _coupling_kernel(self, inputs, transform_params, inverse):
-        div = _divisor_if_hidden_features(self.transform_net)
+        div = divisor_if_hidden_features(self.transform_net)
         return ops.piecewise_spline_autograd(inputs, transform_params, self._cols(inputs.device), kind=ops.SPLINE_CUBIC,
                                     num_bins=self.num_bins, tails=self.tails, tail_bound=self.tail_bound,
                                     min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,

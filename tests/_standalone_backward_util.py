@@ -138,7 +138,7 @@ def sos_route(total, s, cus):
 
 
 def splines_trips(total_threads, cus):
-    """``fc_piecewise_spline_backward`` (csrc/fc_splines_backward.hip:248-250, :193): trips of the grid-stride loop."""
+    """``fc_piecewise_spline_backward`` (csrc/fc_splines_backward.hip:106-108, :50): trips of the grid-stride loop."""
     grid = min(_ceil(total_threads, 256), cus * 8)
     return _ceil(total_threads, grid * 256)
 
@@ -787,6 +787,94 @@ def check(cs, gx_t, gp):
         out.append((kind, compare(slices(kind, cs, gx_t, gp, keep), slices(kind, cs, r64[0], r64[1], keep),
                                   slices(kind, cs, r32[0], r32[1], keep), C[cs.entry], cond[kind])))
     return out
+
+
+# ---- gradients at the knots ------------------------------------------------------------------------------------------------
+# The elements every case above leaves out: x on an interior knot of its own spline and within a few float32 ulps of it.  On
+# which side of the knot the kernel puts such an element is its own business (the spline is C1, the gradient of logabsdet
+# with respect to the parameters is not), so an element passes if it agrees with the float64 gradient taken a little to the
+# left of the knot OR a little to the right.  These cases are not part of SPECS: C and COND_MEDIAN are measured without them.
+
+KNOT_SHIFT = 2.0 ** -16          # delta, as a share of the interval: far outside the few-ulp disagreement, well inside a bin
+KNOT_NEIGHBOURS = 4              # float32 neighbours of the rounded knot on either side
+KNOT_K = 8
+KNOT_CASES = collections.OrderedDict([("quadratic-box", ("quadratic", False)), ("cubic-box", ("cubic", False)),
+                                      ("quadratic-tails", ("quadratic", True))])
+
+
+@functools.lru_cache(maxsize=None)
+def knot_case(name):
+    """d = d_t = 2, one parameter row ~ N(0, 1) shared by all rows; row 9 k + o holds, per dim, the float32 rounding of that
+    dim's interior knot k stepped by o - 4 float32 neighbours (``torch.nextafter``): 7 knots x 9 values = 63 rows."""
+    kind, tails = KNOT_CASES[name]
+    cfg = dict(kind=kind, k=KNOT_K, tails=tails)
+    rows = (KNOT_K - 1) * (2 * KNOT_NEIGHBOURS + 1)
+    spec = Spec("spline", "spline-knots-" + name, cfg, 2, 2, rows, rows, "knots", ())
+    gen = torch.Generator().manual_seed(seed_of(spec))
+    p = params_per_dim(spec)
+    params = torch.randn(1, 2 * p, generator=gen).expand(rows, 2 * p).contiguous()
+    gy, gl = torch.randn(rows, 2, generator=gen), torch.randn(rows, generator=gen)
+    cs = Case(spec, "spline", spec.id, cfg, rows, 2, 2, torch.zeros(rows, 2), params, None, gy, gl, None, rows, 0)
+    knots = inner_knots(cs)[0].float()                                  # [d_t, K - 1]
+    up, down = torch.tensor(float("inf")), torch.tensor(float("-inf"))
+    steps = {0: knots}
+    for o in range(1, KNOT_NEIGHBOURS + 1):
+        steps[o], steps[-o] = torch.nextafter(steps[o - 1], up), torch.nextafter(steps[1 - o], down)
+    x = torch.stack([steps[o] for o in range(-KNOT_NEIGHBOURS, KNOT_NEIGHBOURS + 1)], dim=-1)      # [d_t, K - 1, 9]
+    return cs._replace(x=x.reshape(2, rows).t().contiguous())
+
+
+def narrowest_bin(cs):
+    """The narrowest bin of a spline case on the x axis, as a share of the interval (float64)."""
+    lo, hi = interval(cs.spec)
+    r = cs.x.shape[0]
+    edges = torch.cat([torch.full((r, cs.d_t, 1), lo, dtype=torch.float64), inner_knots(cs),
+                       torch.full((r, cs.d_t, 1), hi, dtype=torch.float64)], dim=-1)
+    return float((edges[..., 1:] - edges[..., :-1]).min()) / (hi - lo)
+
+
+def element_slices(cs, gx_t, gp):
+    """[R d_t, 1 + P] float64: per transformed element its gx and its own parameters' gp."""
+    gx_t, gp = gx_t.detach().double().cpu(), param_view(cs, gp.detach().double().cpu())
+    return torch.cat([gx_t.unsqueeze(-1), gp], dim=-1).reshape(gx_t.numel(), -1)
+
+
+@functools.lru_cache(maxsize=None)
+def knot_reference(name):
+    """Per side ("left", "right") of the knots: (float64 gradient slices at x -+ delta, the bound of every element).  The bound
+    is the per-slice form of ``compare`` with, in the place of cond, the drift of the one-sided float64 gradient over the
+    distance the point was shifted: MARGIN floor + (C + ULP) scale + 2 max |g64(x -+ delta) - g64(x -+ 2 delta)|, the floor
+    from the float32 oracle at x -+ delta.  Nothing in it comes from a kernel."""
+    cs = knot_case(name)
+    lo, hi = interval(cs.spec)
+    delta = KNOT_SHIFT * (hi - lo)
+    out = {}
+    for side, sign in (("left", -1.0), ("right", 1.0)):
+        near, far = cs._replace(x=cs.x.double() + sign * delta), cs._replace(x=cs.x.double() + 2 * sign * delta)
+        g64 = element_slices(cs, *gradients(near, torch.float64))
+        g32 = element_slices(cs, *gradients(near, torch.float32))
+        g64_far = element_slices(cs, *gradients(far, torch.float64))
+        scale = g64.abs().amax(dim=1)
+        floor = (g32 - g64).abs().amax(dim=1)
+        drift = 2 * (g64 - g64_far).abs().amax(dim=1)
+        out[side] = (g64, MARGIN * floor + (C["spline"] + ULP) * scale + drift)
+    return out
+
+
+def check_knots(name, gx_t, gp):
+    """(ok, worst err / bound over the elements -- each on its better side --, a line on the worst element)."""
+    cs = knot_case(name)
+    got = element_slices(cs, gx_t, gp)
+    ratios = []
+    for side in ("left", "right"):
+        g64, bound = knot_reference(name)[side]
+        ratios.append((got - g64).abs().amax(dim=1) / bound.clamp_min(1e-300))
+    ratio = torch.minimum(*ratios).nan_to_num(nan=float("inf"))
+    finite = bool(torch.isfinite(got).all())
+    i = int(ratio.argmax())
+    detail = "element %d (row %d, dim %d): err / bound %.3g on the left, %.3g on the right; %d of %d elements fail" % (
+        i, i // cs.d_t, i % cs.d_t, ratios[0][i], ratios[1][i], int((ratio > 1).sum()), ratio.numel())
+    return finite and bool((ratio <= 1).all()), float(ratio.max()), detail
 
 
 def round_up_one_digit(v):

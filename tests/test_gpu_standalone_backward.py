@@ -162,6 +162,21 @@ def test_piecewise_spline_edges(cid, device):
     _outside_rows_are_the_identity(cs, gx, gp)
 
 
+@pytest.mark.parametrize("name", list(U.KNOT_CASES))
+def test_piecewise_spline_gradients_at_the_knots(name, device):
+    """x on the float32 rounding of every interior knot and on its four float32 neighbours on either side -- the elements
+    every case above leaves out.  Each element's (gx, gp) must be the float64 gradient of the bin on the left of the knot or
+    of the bin on the right (``U.check_knots``: taken at x -+ 2^-16 of the interval); no element is left out."""
+    cs = U.knot_case(name)
+    kw = U.spline_kwargs(cs.spec)
+    gx, gp = _backward_through(lambda a, b: ops.piecewise_spline_autograd(a, b, None, **kw), cs.x.to(device),
+                               cs.params.to(device), cs.gy.to(device), cs.gl.to(device))
+    torch.cuda.synchronize(device)
+    ok, worst, detail = U.check_knots(name, gx.cpu(), gp.reshape(cs.n, -1).cpu())
+    print("standalone-backward spline %s at the knots: err/bound %.3f (%s)" % (cs.id, worst, detail))
+    assert ok, (cs.id, detail)
+
+
 # ---- sum of sigmoids -----------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("cid", U.ids("sos"))

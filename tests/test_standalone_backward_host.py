@@ -115,6 +115,33 @@ def test_largest_bin_counts_are_those_of_the_operator():
         assert not ops.piecewise_spline_backward_supported(U.KIND_CODE[kind], k + 1, "linear" if tails else None)
 
 
+@pytest.mark.parametrize("name", list(U.KNOT_CASES))
+def test_knot_cases_sit_on_the_knots_with_room_on_either_side(name):
+    """63 rows per case: every interior float64 knot's float32 rounding and 4 float32 neighbours on either side, all distinct
+    and within 4 ulps of the knot; no bin narrower than 4 delta, so that x -+ 2 delta stays inside the neighbouring bin; the
+    one-sided references are finite and their bound is positive."""
+    cs = U.knot_case(name)
+    lo, hi = U.interval(cs.spec)
+    assert cs.x.shape == (63, 2) and cs.x.dtype == torch.float32 and cs.d_t == cs.d == 2
+    assert U.narrowest_bin(cs) >= 4 * U.KNOT_SHIFT
+    knots = U.inner_knots(cs)[0]                                      # [d_t, K - 1]
+    x = cs.x.t().reshape(2, U.KNOT_K - 1, 9).double()
+    assert bool((x[..., 1:] > x[..., :-1]).all())
+    assert torch.equal(x[..., 4].float(), knots.float())
+    ulp = torch.finfo(torch.float32).eps * (hi - lo)
+    assert float((x - knots.unsqueeze(-1)).abs().max()) <= 4.5 * ulp < U.KNOT_SHIFT * (hi - lo) / 16
+    assert not cs.cfg["tails"] or (lo, hi) == (-2.0, 2.0)
+    for side in ("left", "right"):
+        g64, bound = U.knot_reference(name)[side]
+        assert bool(torch.isfinite(g64).all()) and float(bound.min()) > 0
+    # the two sides are different answers, further apart than the two bounds together at every element: logabsdet's gradient
+    # with respect to the parameters jumps at a knot, so a gradient that passes on one side cannot pass on the other, and
+    # one that mixes the two bins passes on neither
+    (left, bound_left), (right, bound_right) = U.knot_reference(name)["left"], U.knot_reference(name)["right"]
+    gap = (left - right).abs().amax(dim=1)
+    assert bool((gap > 10 * (bound_left + bound_right)).all()), float((gap / (bound_left + bound_right)).min())
+
+
 FD_CASES = ["rq-K5-tails-d12-dt8-n512", "rq-K10-box-d12-dt8-n512", "sos-S6-n515-d5", "sos-S6-postact"] \
     + ["spline-%s-K%d-%s-d5-dt3-n400" % (kind, k, U._tn(tails)) for (kind, tails), k in U.SPLINE_MID.items()] \
     + [act + "-d10-dt6-n300" for act in ("affine-" + a for a in U.AFFINE_ACTS)]
