@@ -14,7 +14,11 @@ times:
   ``ops.cnf_dopri5_rows_pay``: the whole adaptive solve is one ``fc_cnf_dopri5`` launch in which every row controls
   its own step (a row is judged by its own error, and one that cannot finish within ``max_num_steps``, clipped to
   4096, attempts returns NaN where the host loop raises).
-Everything else is the torch composition on the tensors' device."""
+In training mode, or wherever a gradient is needed, with options ``cnf_solve_training`` (off by default), a solver in
+``euler`` / ``midpoint`` / ``rk4``, two integration times that are numbers, no regulariser and a net within
+``ops.cnf_solve_train_fits``: the whole solve is one autograd node, one ``fc_cnf_integrate_train`` launch forward and one
+``fc_cnf_integrate_backward`` launch backward (``_training_solve``; DESIGN.md, "CNF training: the whole solve").
+Everything else is the torch composition on the tensors' device (or the per-evaluation nodes of ``cnf_training``)."""
 import torch
 from torch import nn
 
@@ -22,6 +26,7 @@ from flowconductor_amd import ops, options
 from flowconductor_amd.transforms.base import Transform
 
 from .neural_odes.odefunc import ODEfunc
+from .neural_odes.util import divergence_approx, sample_gaussian_like, sample_rademacher_like
 from .neural_odes.wrappers.cnf_regularization import RegularizedODEfunc
 from .odeint import fixed_grid_steps, odeint
 
@@ -105,6 +110,51 @@ class CNF(nn.Module):
                                         first_step=first_step, max_attempts=max_attempts, **func._kernel_args(plan))
         return z_t, logp_t.view(logpz.shape)
 
+    def _training_solve(self, z, logpz, times):
+        """``(z_t, logp_t)`` from one ``_CnfSolveFunction`` node (options ``cnf_solve_training``): one
+        ``fc_cnf_integrate_train`` launch forward and one ``fc_cnf_integrate_backward`` launch backward; or None when
+        this call is not one for them, before anything has been drawn or counted."""
+        route = options.get("cnf_solve_training")
+        func = self.odefunc
+        if not route or self.nreg or type(func) is not ODEfunc or ops.has_hooks(self) \
+                or func.training != self.training:
+            return None
+        method = ops.CNF_METHODS.get(self.solver if self.training else self.test_solver)
+        if method is None or len(times) != 2 or any(isinstance(v, torch.Tensor) for v in times):
+            return None
+        if not (isinstance(z, torch.Tensor) and z.is_cuda and z.dtype == torch.float32 and z.dim() == 2
+                and z.shape[0] > 0 and z.is_contiguous()):
+            return None
+        if not (isinstance(logpz, torch.Tensor) and logpz.is_cuda and logpz.dtype == torch.float32
+                and logpz.device == z.device and logpz.shape == (z.shape[0], 1) and logpz.is_contiguous()):
+            return None
+        if not (self.training or func._needs_grad(z)):
+            return None
+        hutchinson = func.training and func.divergence_fn is divergence_approx      # eval mode is always exact
+        if route != "force" and not ops.cnf_solve_train_rows_pay(z.shape[0], z.shape[1], hutchinson):
+            return None     # the per-evaluation nodes' measured limit (DESIGN.md, "CNF training: the whole solve")
+        e = func._e
+        if hutchinson and e is not None and not (
+                isinstance(e, torch.Tensor) and e.dtype == torch.float32 and e.device == z.device
+                and e.shape == z.shape and e.is_contiguous() and not e.requires_grad):
+            return None
+        plan = func._plan_for(z)
+        steps = fixed_grid_steps(times[0], times[1], self.solver_options)
+        if plan is None or not ops.cnf_solve_train_fits(z.shape[0], plan.d, plan.hidden, steps, method, hutchinson):
+            return None
+        if func.training and func._e is None:       # where, and by the call with which, the composition draws it
+            func._e = sample_rademacher_like(z) if func.rademacher else sample_gaussian_like(z)
+        kw = func._kernel_args(plan)
+        kw.update(t0=times[0], t1=times[1], steps=steps, method=method)
+        e = func._e if hutchinson else None
+        if not (func._needs_grad(z) or (torch.is_grad_enabled() and logpz.requires_grad)):
+            z_t, logp_t = ops.cnf_integrate_train(z, logpz, e, **kw)        # nothing to carry: no tape
+            return z_t, logp_t.view(logpz.shape)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in ops.param_list(func)):
+            kw["image"] = func._training_image(plan)
+        image = kw.pop("image")
+        return ops._CnfSolveFunction.apply(z, logpz, image, e, kw)
+
     def forward(self, z, logpz=None, integration_times=None, reverse=False):
         _logpz = torch.zeros(z.shape[0], 1).to(z) if logpz is None else logpz
         if integration_times is None:
@@ -119,6 +169,8 @@ class CNF(nn.Module):
 
         self.odefunc.before_odeint()        # refresh the evaluation count and the noise
         solved = self._kernel_solve(z, _logpz, times)
+        if solved is None:
+            solved = self._training_solve(z, _logpz, times)
         if solved is not None:
             z_t, logpz_t = solved
             self.regularization_states = ()

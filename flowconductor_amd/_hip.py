@@ -175,6 +175,11 @@ SIGNATURES = {
     "fc_cnf_field_backward": [_P] * 8 + [_I64, _I32, _I32, _P, _I32, _I32, _I32, _F, _F, _I32, _F, _P, _P],
     "fc_cnf_field_backward_rows": [_I32, _I32, _P, _I32],
     "fc_cnf_field_backward_workspace": [_I64, _I32, _I32, _P, _I32],
+    "fc_cnf_integrate_train": [_P] * 8 + [_I64, _I32, _I32, _P, _I32, _I32, _I32, _F, _F, _I32, ctypes.c_double,
+                                          ctypes.c_double, _I32, _I32, _P],
+    "fc_cnf_integrate_backward": [_P] * 8 + [_I64, _I32, _I32, _P, _I32, _I32, _I32, _F, _F, _I32, ctypes.c_double,
+                                             ctypes.c_double, _I32, _I32, _P],
+    "fc_cnf_integrate_backward_workspace": [_I64, _I32, _I32, _P, _I32],
     "fc_umnn": [_P] * 7 + [_I64, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "fc_umnn_backward": [_P] * 11 + [_I64, _I32, _I32, _I32, _I32, _I32, _P],
     "fc_umnn_backward_workspace": [_I64, _I32, _I32],

@@ -93,6 +93,9 @@ from .cnf import (  # noqa: F401
 from .cnf import (  # noqa: F401
     CNF_BACKWARD_MAX_BLOCKS, CNF_DOUBLE_BACKWARD_MSG, CNF_TRAIN_MAX_HIDDEN_LAYERS, CNF_TRAIN_MAX_LANES, _CnfFieldFunction, cnf_backward_rows,
     cnf_field_backward, cnf_field_train, cnf_train_lanes, cnf_train_rows_pay, cnf_train_supported)
+from .cnf import (  # noqa: F401
+    CNF_SOLVE_DOUBLE_BACKWARD_MSG, CNF_SOLVE_TRAIN_MAX_TAPE_BYTES, _CnfSolveFunction, cnf_integrate_backward,
+    cnf_integrate_train, cnf_solve_train_fits, cnf_solve_train_rows_pay)
 from .umnn import (  # noqa: F401
     UMNN_DOUBLE_BACKWARD_MSG, UMNN_MAX_COND, UMNN_MAX_HIDDEN_LAYERS, UMNN_MAX_STEPS, UMNN_MAX_WIDTH, UMNN_POINTS,
     _UMNNFunction, pack_umnn, pack_umnn_backward, umnn, umnn_autograd, umnn_backward, umnn_backward_image, umnn_fits,

@@ -1,5 +1,5 @@
 """Continuous normalizing flows: one ODE-function evaluation, or a whole fixed-step solve, per launch (eval mode), and
-one evaluation as an autograd node of one forward and one backward launch (training)."""
+one evaluation, or a whole fixed-step solve, as an autograd node of one forward and one backward launch (training)."""
 import ctypes
 
 import torch
@@ -319,3 +319,115 @@ class _CnfFieldFunction(torch.autograd.Function):
         g_y, g_image = cnf_field_backward(ctx.t, y, e, image, g_dy.contiguous(), g_negdiv.contiguous(), **ctx.kw)
         need = ctx.needs_input_grad
         return g_y if need[0] else None, g_image if need[1] else None, None, None, None
+
+
+# ---- training: the whole fixed-step solve, fc_cnf_integrate_train / fc_cnf_integrate_backward ------------------------
+# The tape of a solve is ``steps * stages * N * D`` floats.  A call whose tape would be larger than this keeps the
+# per-evaluation route: a condition that keeps a long solve from allocating without bound, not a tuned number.
+CNF_SOLVE_TRAIN_MAX_TAPE_BYTES = 1 << 30
+CNF_SOLVE_DOUBLE_BACKWARD_MSG = (
+    "flowconductor_amd: the one-launch CNF solve (options 'cnf_solve_training') is once differentiable; for a gradient "
+    "of a gradient (create_graph=True, the regularisers) run the solve with "
+    "options.override(cnf_solve_training=False, cnf_training=False), the torch composition")
+
+
+def cnf_solve_train_fits(n, d, hidden, steps, method, hutchinson):
+    """Whether ``fc_cnf_integrate_train`` / ``fc_cnf_integrate_backward`` take ``n`` rows of a net ``d -> hidden... ->
+    d`` through ``steps`` steps of ``method``: ``cnf_train_supported`` (every such net fits the backward kernel's LDS in
+    either divergence mode) and a tape of at most ``CNF_SOLVE_TRAIN_MAX_TAPE_BYTES``.  Allocates nothing."""
+    del hutchinson      # the tape and the limits are those of both modes
+    if method not in CNF_STAGES or int(steps) < 1 or int(n) < 0 or not cnf_train_supported(d, hidden):
+        return False
+    return 4 * int(steps) * CNF_STAGES[method] * int(n) * int(d) <= CNF_SOLVE_TRAIN_MAX_TAPE_BYTES
+
+
+def cnf_solve_train_rows_pay(n, d, hutchinson):
+    """Whether ``cnf_solve_training=True`` sends a batch of ``n`` rows to the one-launch solve: the limit of the
+    per-evaluation nodes, whose arithmetic it shares, and the largest measured size at which it beat both other routes
+    in both divergence modes (tools/probe/bench_cnf_solve_training.py; DESIGN.md, "CNF training: the whole solve")."""
+    return cnf_train_lanes(n, d, hutchinson) <= CNF_TRAIN_MAX_LANES
+
+
+def _cnf_fixed_steps(name, steps, method):
+    if method not in CNF_STAGES or int(steps) < 1:
+        raise ValueError("flowconductor_amd: %s takes euler / midpoint / rk4 and at least one step" % name)
+    return int(steps), int(method)
+
+
+def cnf_integrate_train(inputs, logp, e, image, d, hidden, layer_kind, activation, t0, t1, steps, method,
+                        residual=False, scale_output=1.0, p0=1.0, evals=None, tape=False):
+    """``cnf_integrate`` for training, one launch: with ``e`` (float32 ``[N, d]``) every evaluation's divergence is
+    Hutchinson's estimate with that ``e``, with None the exact one.  ``tape=True`` returns ``(z(t1), logp(t1), tape)``,
+    ``tape [steps * stages, N, d]`` the float32 stage inputs ``cnf_integrate_backward`` reads; without it ``(z(t1),
+    logp(t1))``, bitwise ``cnf_integrate``'s when ``e`` is None.  No autograd (``_CnfSolveFunction`` has it)."""
+    _hip.require_no_grad(inputs, logp)
+    lib = _hip.load()
+    z, image, tail = _cnf_train_operands(inputs, e, image, d, hidden, layer_kind, activation, residual, scale_output,
+                                         p0, evals)
+    steps, method = _cnf_fixed_steps("fc_cnf_integrate_train", steps, method)
+    logp = _cnf_logp(logp, z)
+    z_out, logp_out = _cnf_outputs(z)
+    kept = None
+    if tape:
+        kept = torch.empty(steps * CNF_STAGES[method], z.shape[0], d, dtype=torch.float32, device=z.device)
+    _call("fc_cnf_integrate_train", lib.fc_cnf_integrate_train, z.device, _hip.ptr(z), _hip.ptr(logp), _hip.ptr(e),
+          _hip.ptr(image), _hip.ptr(z_out), _hip.ptr(logp_out), _hip.ptr(kept), _hip.ptr(evals), *tail, float(t0),
+          float(t1), steps, method, _hip.stream_ptr(z.device))
+    return (z_out, logp_out, kept) if tape else (z_out, logp_out)
+
+
+def cnf_integrate_backward(tape, e, image, g_z_out, g_logp_out, d, hidden, layer_kind, activation, t0, t1, steps,
+                           method, residual=False, scale_output=1.0, p0=1.0):
+    """The raw ``fc_cnf_integrate_backward``: ``(g_z [N, d], g_image [image floats])`` of ``sum(g_z_out * z(t1)) +
+    sum(g_logp_out * logp(t1))`` for the solve that wrote ``tape`` at the same arguments (the gradient with respect to
+    ``logp(t0)`` is ``g_logp_out`` itself); ``g_image`` as ``cnf_field_backward`` gives it, bitwise reproducible."""
+    lib = _hip.load()
+    steps, method = _cnf_fixed_steps("fc_cnf_integrate_backward", steps, method)
+    g_z_out = _hip.dev_f32(g_z_out, "g_z_out")
+    z, image, tail = _cnf_train_operands(g_z_out, e, image, d, hidden, layer_kind, activation, residual, scale_output,
+                                         p0, None)
+    n = z.shape[0]
+    g_logp_out = _hip.dev_f32(g_logp_out, "g_logp_out")
+    if not (isinstance(tape, torch.Tensor) and tape.dtype == torch.float32 and tape.device == z.device
+            and tape.shape == (steps * CNF_STAGES[method], n, d) and tape.is_contiguous()):
+        raise ValueError("flowconductor_amd: cnf_integrate_backward: the tape must be contiguous float32 "
+                         "[steps * stages, N, D] on the device of the rows")
+    if g_logp_out.numel() != n or g_logp_out.device != z.device:
+        raise ValueError("flowconductor_amd: cnf_integrate_backward: g_logp_out does not belong to the rows")
+    with torch.cuda.device(z.device):
+        floats = lib.fc_cnf_integrate_backward_workspace(*tail[:4], int(e is not None))
+    if floats < 0:
+        raise ValueError("flowconductor_amd: cnf_integrate_backward: outside the kernel's limits")
+    workspace = torch.empty(max(floats // 2, 1), dtype=torch.float64, device=z.device)
+    g_z = torch.empty_like(z)
+    g_image = torch.empty_like(image)
+    _call("fc_cnf_integrate_backward", lib.fc_cnf_integrate_backward, z.device, _hip.ptr(tape), _hip.ptr(e),
+          _hip.ptr(image), _hip.ptr(z), _hip.ptr(g_logp_out), _hip.ptr(g_z), _hip.ptr(g_image), _hip.ptr(workspace),
+          *tail, float(t0), float(t1), steps, method, _hip.stream_ptr(z.device))
+    return g_z, g_image
+
+
+class _CnfSolveFunction(torch.autograd.Function):
+    """``fc_cnf_integrate_train`` with ``fc_cnf_integrate_backward`` over ``(z, logp, image)``: saves the tape, the
+    image and ``e``; no activation is kept.  ``e`` gets no gradient.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, z, logp, image, e, kw):
+        z_t, logp_t, tape = cnf_integrate_train(z, logp, e, image=image, tape=True, **kw)
+        ctx.kw = {k: v for k, v in kw.items() if k != "evals"}
+        ctx.save_for_backward(tape, image, e)
+        return z_t, logp_t.view(logp.shape)
+
+    @staticmethod
+    def backward(ctx, g_z_out, g_logp_out):
+        if torch.is_grad_enabled():
+            raise RuntimeError(CNF_SOLVE_DOUBLE_BACKWARD_MSG)
+        return _CnfSolveFunction._backward_once(ctx, g_z_out, g_logp_out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _backward_once(ctx, g_z_out, g_logp_out):
+        tape, image, e = ctx.saved_tensors
+        g_z, g_image = cnf_integrate_backward(tape, e, image, g_z_out.contiguous(), g_logp_out.contiguous(), **ctx.kw)
+        need = ctx.needs_input_grad
+        return g_z if need[0] else None, g_logp_out if need[1] else None, g_image if need[2] else None, None, None

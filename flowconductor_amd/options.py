@@ -58,12 +58,20 @@ _DEFAULTS = {
     # cannot finish returns NaN where the host loop raises, so the results differ within the tolerance: off by default
     # ("dopri5 in one launch").
     "cnf_dopri5_kernel": False,
+    # a fixed-step solve (euler / midpoint / rk4) of a continuous normalizing flow in training mode, or wherever a
+    # gradient is needed, as ONE autograd node: fc_cnf_integrate_train forward, fc_cnf_integrate_backward (a reverse
+    # sweep over a tape of stage inputs) backward, instead of a node per evaluation (cnf_training) or the torch
+    # composition, for batches up to ops.CNF_TRAIN_MAX_LANES lanes; "force" takes it at any batch size (measurements,
+    # tests), False never.  Off by default; a training step measured 1.07x to 1.13x faster than on the per-evaluation
+    # route up to that size ("CNF training: the whole solve").
+    "cnf_solve_training": False,
 }
 
 # options that take a few named values only: anything else is a mistake at the call site
 _CHOICES = {
     "cnf_training": (False, True, "force"),
     "cnf_dopri5_kernel": (False, True, "force"),
+    "cnf_solve_training": (False, True, "force"),
 }
 
 _values = dict(_DEFAULTS)

@@ -677,6 +677,33 @@ int fc_cnf_field_backward(const float* y, const float* e, const float* image, co
 int fc_cnf_field_backward_rows(int32_t d, int32_t layers, const int32_t* hidden, int32_t with_e);
 int fc_cnf_field_backward_workspace(int64_t n, int32_t d, int32_t layers, const int32_t* hidden, int32_t with_e);
 
+/* Training: a whole fixed-step solve as an autograd node (the nets of fc_cnf_field_train, the step sequence of
+ * fc_cnf_integrate: stage i of step s at t0 + s h + a_i h, h = (t1 - t0) / steps; t1 < t0 integrates backwards).
+ * fc_cnf_integrate_train     fc_cnf_integrate with e as in fc_cnf_field_train (NULL: the exact divergence; float32
+ *           [n, d]: Hutchinson's estimate with that one e in every evaluation) and an optional tape, float32
+ *           [steps * stages, n, d]: tape[s * stages + i][row] is the float32 state stage i of step s handed to the net.
+ *           NULL stores nothing.  With e NULL and tape NULL the outputs are bitwise fc_cnf_integrate's.  Max-reduces
+ *           steps * stages into *evals.  z != z_out.
+ * fc_cnf_integrate_backward  from the tape, e as in the forward call, g_z_out [n, d] and g_logp_out [n]: g_z [n, d] and
+ *           g_image [image_floats] (laid out and summed as fc_cnf_field_backward does, over the rows and over the
+ *           evaluations of a row in reverse order), the exact gradient of the solve that wrote the tape.  The
+ *           gradient of logp is g_logp_out itself.  The adjoint of the state is carried in float64 and rounded to
+ *           float32 where it enters an evaluation's backward.  No atomics, bitwise reproducible; g_z of a row does not
+ *           depend on the other rows.  workspace: at least fc_cnf_integrate_backward_workspace(...) floats, 8-byte
+ *           aligned.  The rows a block carries are fc_cnf_field_backward_rows(...).
+ * fc_cnf_integrate_backward_workspace  floats of workspace for n rows (-1 outside the limits) */
+int fc_cnf_integrate_train(const float* z, const float* logp, const float* e, const float* image, float* z_out,
+                           float* logp_out, float* tape, float* evals, int64_t n, int32_t d, int32_t layers,
+                           const int32_t* hidden, int32_t layer_kind, int32_t activation, int32_t residual,
+                           float scale_output, float p0, int32_t image_floats, double t0, double t1, int32_t steps,
+                           int32_t method, void* stream);
+int fc_cnf_integrate_backward(const float* tape, const float* e, const float* image, const float* g_z_out,
+                              const float* g_logp_out, float* g_z, float* g_image, void* workspace, int64_t n,
+                              int32_t d, int32_t layers, const int32_t* hidden, int32_t layer_kind, int32_t activation,
+                              int32_t residual, float scale_output, float p0, int32_t image_floats, double t0,
+                              double t1, int32_t steps, int32_t method, void* stream);
+int fc_cnf_integrate_backward_workspace(int64_t n, int32_t d, int32_t layers, const int32_t* hidden, int32_t with_e);
+
 /* ---- batch-shared point-wise affine maps ---------------------------------------------------- */
 /* x, y viewed as [n, m] (m = elements of one batch item); scale/shift have 1 or m entries.
  * mode 0: y = x*scale + shift                    (standard.py:54-60, normalization.py:171-187)
