@@ -166,6 +166,8 @@ SIGNATURES = {
     "fc_conv1x1": [_P, _P, _P, _P, _P, _I64, _I32, _I64, _P],
     "fc_iresnet_forward": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "fc_iresnet_inverse": [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _P],
+    "fc_iresnet_backward": [_P] * 11 + [_I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
+    "fc_iresnet_backward_workspace": [_I64, _I32, _I32, _I32, _I32, _I32, _I32],
     "fc_cnf_field": [_P] * 5 + [_I64, _I32, _I32, _P, _I32, _I32, _I32, _F, _F, _I32, _F, _P, _P],
     "fc_cnf_integrate": [_P] * 6 + [_I64, _I32, _I32, _P, _I32, _I32, _I32, _F, _F, _I32, ctypes.c_double,
                                     ctypes.c_double, _I32, _I32, _P],

@@ -1,9 +1,11 @@
-// Invertible residual blocks over Lipschitz-constrained DenseNets in eval mode (reference
+// Invertible residual blocks over Lipschitz-constrained DenseNets (reference
 // flowcon/transforms/lipschitz/iresblock.py with flowcon/nn/nets/invertible_densenet.py, lipschitz_dense.py).
 //
 //   fc_iresnet_forward   y = x + s g(x),  logabsdet = log|det(I + s dg/dx)|      one launch
 //   fc_iresnet_inverse   x with x + s g(x) = y by the fixed-point iteration x <- y - s g(x), every row to its own
 //                        convergence                                             one launch
+//   fc_iresnet_backward  the reverse sweep of fc_iresnet_forward: gradients of the rows, the per-row operands and
+//                        every entry of the image, the streams recomputed in LDS      one launch + a reduction
 //
 // g is a DenseNet: `depth` layers  h <- cat(eta1 h, eta2 act(W h + b))  (act may itself concatenate act(t), act(-t))
 // followed by one linear layer back to d outputs.  The host hands over an IMAGE of the net with the spectral
@@ -30,6 +32,12 @@
 // holds for all its elements (no square: stricter than the reference's batch-wide squared test) or after
 // max_iterations; lanes that are done idle until their wave's slowest row is.  The largest iteration count of the
 // launch is max-reduced into a device word for tools and tests; nothing is read back on the normal path.
+//
+// Backward: the forward's lane groups and LDS layout plus an adjoint state of the same shape.  A tile recomputes the
+// streams through ires_net, inverts I + s J inside the lane group (the cotangent of column j of J is gl s (A^-T)[:, j]),
+// and sweeps the layers from the last; every block adds its parameter-gradient sums onto one image-shaped float64
+// partial, each entry by one thread in a fixed order, and a second kernel adds the partials in block order (no
+// atomics).  See DESIGN.md, "iResBlock training".
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/flowcon_hip.h"
@@ -56,48 +64,92 @@ __host__ __device__ inline int ires_image_floats(const IresShape& sh) {
 
 // value f(t) and derivative f'(t) of the element-wise part of the activation (for the concatenating ones the caller
 // evaluates at t and at -t).  Evaluated in float64 on the float64 pre-activation: the value a stream stores is rounded
-// to float32 once, after the concatenation weight.
-__device__ __forceinline__ void ires_act(int act, double t, double p0, double p1, double& f, double& df) {
+// to float32 once, after the concatenation weight.  SECOND adds what the reverse sweep of fc_iresnet_backward needs:
+// f''(t) and the derivatives of f and f' with respect to the activation scalars p0 / p1.
+struct IresActJet {
+  double f, df, d2f, f_p0, df_p0, f_p1, df_p1;
+};
+
+template <bool SECOND>
+__device__ __forceinline__ void ires_act_jet(int act, double t, double p0, double p1, IresActJet& r) {
+  r.d2f = r.f_p0 = r.df_p0 = r.f_p1 = r.df_p1 = 0.0;
   switch (act) {
     case FC_IRES_ACT_RELU:
-      f = t > 0.0 ? t : 0.0;
-      df = t > 0.0 ? 1.0 : 0.0;
+      r.f = t > 0.0 ? t : 0.0;
+      r.df = t > 0.0 ? 1.0 : 0.0;
       break;
     case FC_IRES_ACT_TANH: {
       const double th = tanh(t);
-      f = th;
-      df = 1.0 - th * th;
+      r.f = th;
+      r.df = 1.0 - th * th;
+      if (SECOND) r.d2f = -2.0 * th * r.df;
       break;
     }
     case FC_IRES_ACT_ELU: {
-      f = t > 0.0 ? t : p0 * expm1(t);
-      df = t > 0.0 ? 1.0 : p0 * exp(t);
+      r.f = t > 0.0 ? t : p0 * expm1(t);
+      r.df = t > 0.0 ? 1.0 : p0 * exp(t);
+      if (SECOND) {
+        r.d2f = t > 0.0 ? 0.0 : r.df;
+        r.f_p0 = t > 0.0 ? 0.0 : expm1(t);
+        r.df_p0 = t > 0.0 ? 0.0 : exp(t);
+      }
       break;
     }
     case FC_IRES_ACT_SIN:
     case FC_IRES_ACT_CSIN: {
       const double a = p0 * t;
       const double div = act == FC_IRES_ACT_CSIN ? 1.41421356237309504880 : 1.0;
-      f = sin(a) / (p0 * div);
-      df = cos(a) / div;
+      r.f = sin(a) / (p0 * div);
+      r.df = cos(a) / div;
+      if (SECOND) {
+        r.d2f = -(p0 * sin(a)) / div;
+        r.f_p0 = (a * cos(a) - sin(a)) / (p0 * p0 * div);
+        r.df_p0 = -(t * sin(a)) / div;
+      }
       break;
     }
     default: {  // the Swish family: t sigmoid(b t) / 1.1 (/ 1.004 for LipSwish, CLipSwish), LeakyLSwish mixes with t
       const double sg = 1.0 / (1.0 + exp(-p0 * t));
       double v = t * sg / 1.1;
       double dv = (sg + p0 * t * sg * (1.0 - sg)) / 1.1;
+      // q = sg (1 - sg): d sg / dt = p0 q, d sg / dp0 = t q, dq / d(p0 t) = q (1 - 2 sg)
+      const double q = sg * (1.0 - sg);
+      const double bend = q * (2.0 + p0 * t * (1.0 - 2.0 * sg)) / 1.1;
+      double d2v = p0 * bend, v_p0 = t * t * q / 1.1, dv_p0 = t * bend;
       if (act == FC_IRES_ACT_LIPSWISH || act == FC_IRES_ACT_CLIPSWISH) {
         v = v / 1.004;
         dv = dv / 1.004;
+        d2v = d2v / 1.004;
+        v_p0 = v_p0 / 1.004;
+        dv_p0 = dv_p0 / 1.004;
       } else if (act == FC_IRES_ACT_LEAKY_LSWISH) {
+        if (SECOND) {
+          r.f_p1 = t - v;
+          r.df_p1 = 1.0 - dv;
+        }
         v = p1 * t + (1.0 - p1) * v;
         dv = p1 + (1.0 - p1) * dv;
+        d2v = (1.0 - p1) * d2v;
+        v_p0 = (1.0 - p1) * v_p0;
+        dv_p0 = (1.0 - p1) * dv_p0;
       }
-      f = v;
-      df = dv;
+      r.f = v;
+      r.df = dv;
+      if (SECOND) {
+        r.d2f = d2v;
+        r.f_p0 = v_p0;
+        r.df_p0 = dv_p0;
+      }
       break;
     }
   }
+}
+
+__device__ __forceinline__ void ires_act(int act, double t, double p0, double p1, double& f, double& df) {
+  IresActJet r;
+  ires_act_jet<false>(act, t, p0, p1, r);
+  f = r.f;
+  df = r.df;
 }
 
 // ---- the net on one stream ---------------------------------------------------------------------------------------
@@ -340,6 +392,316 @@ __global__ __launch_bounds__(256) void iresnet_inverse_kernel(const float* __res
   }
 }
 
+// ---- backward: recompute the streams, invert I + s J, sweep the layers from the last ----------------------------------
+
+// Sum over the lanes of a row group / of a wave, in the fixed order of the butterfly.
+template <int W>
+__device__ __forceinline__ double ires_lane_sum(double v) {
+#pragma unroll
+  for (int off = W / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, W);
+  return v;
+}
+
+// part[at + k * ld + o] += sum over the block's streams of lhs[o][t] * st[k][t] for k < rows, and the bias entries
+// part[bias_at + o] += sum over the VALUE streams of lhs[o][t] (a tangent has no bias), o < cols.  One (k, o) per
+// thread and pass; the sum over t is a float64 fma chain that starts at the thread's own lane (conflict-free LDS
+// reads), so its order is a function of the entry alone and a rerun gives the same bits.
+template <int G>
+__device__ __forceinline__ void ires_outer_sums(double* part, int at, int bias_at, int ld, int cols, int rows,
+                                                const float* lhs, const float* st, int T, int tid) {
+  for (int idx = tid; idx < (rows + 1) * ld; idx += T) {
+    const int k = idx / ld, o = idx - k * ld;
+    if (o >= cols) continue;
+    const float* l = lhs + o * T;
+    double sum = 0.0;
+    if (k < rows) {
+      const float* r = st + k * T;
+      for (int i = 0; i < T; ++i) {
+        const int t = (tid + i) & (T - 1);
+        sum = fma((double)l[t], (double)r[t], sum);
+      }
+      part[at + k * ld + o] += sum;
+    } else {
+      for (int i = 0; i < T; i += G) sum += (double)l[((tid & ~(G - 1)) + i) & (T - 1)];
+      part[bias_at + o] += sum;
+    }
+  }
+}
+
+// LDS: the image, the state st[wtot][T] and its adjoint adj[wtot][T] (one column per stream, as the forward keeps its
+// state), cb[dp][T] for the rows of (I + s J)^-1 on their way to the lanes that need them and then for the cotangent of
+// the final layer, and two float64 words per wave for the concatenation weights' sums.  A block owns one image-shaped
+// float64 partial of ws and adds every tile's sums onto it: each entry by one thread, always the same one.
+template <int G>
+__global__ __launch_bounds__(256) void iresnet_backward_kernel(
+    const float* __restrict__ x, const float* __restrict__ extra, const float* __restrict__ scale,
+    const float* __restrict__ image, const float* __restrict__ gy, const float* __restrict__ gl,
+    float* __restrict__ dx, float* __restrict__ dextra, float* __restrict__ dscale, double* __restrict__ ws, int64_t n,
+    IresShape sh, int image_floats) {
+  constexpr int DMAX = G == 32 ? 16 : G - 1;
+  constexpr int DP = (DMAX + 3) & ~3;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int T = blockDim.x, tid = threadIdx.x;
+  const int d = sh.d, e = sh.e, op = ires_pad4(sh.out_ch), dp = ires_pad4(d), wtot = sh.wtot;
+  float* img = lds;
+  float* st = lds + image_floats;
+  float* adj = st + wtot * T;
+  float* cb = adj + wtot * T;
+  double* red = reinterpret_cast<double*>(cb + dp * T);
+  double* part = ws + (size_t)blockIdx.x * image_floats;
+  for (int i = tid; i < image_floats; i += T) {
+    img[i] = image[i];
+    part[i] = 0.0;
+  }
+  __syncthreads();
+  const double p0 = (double)img[0], p1 = (double)img[1];
+  const int s = tid % G;
+  const bool value = s == 0;
+  const int rows_per_block = T / G;
+  const int64_t tiles = (n + rows_per_block - 1) / rows_per_block;
+  float* mine = st + tid;
+  float* adjm = adj + tid;
+  const int final_at = image_floats - dp - wtot * dp;
+  double dp0 = 0.0, dp1 = 0.0;
+
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    int64_t row = tile * rows_per_block + tid / G;
+    const bool live = row < n;
+    if (!live) row = n - 1;  // every lane runs; a row beyond the batch carries zero cotangents
+    const float* xr = x + row * d;
+    for (int k = 0; k < d; ++k) mine[k * T] = value ? xr[k] : (k == s - 1 ? 1.f : 0.f);
+    for (int k = 0; k < e; ++k) mine[(d + k) * T] = value ? extra[row * e + k] : 0.f;
+
+    // the forward again: g in the value lane, column s - 1 of J in lane s
+    double c[DP];
+    {
+      double jc[DP], a[DP], b[DP];
+      ires_net<G, DP>(img, mine, T, sh, s, p0, p1, jc);
+      const double sc = scale ? (double)scale[row] : 1.0;
+      const double glv = live ? (double)gl[row] : 0.0;
+      const bool column = s >= 1 && s <= d;
+      // Gauss-Jordan on [I + s J | I], one column of either half per lane: the row operations of the pivot column's
+      // lane, handed round by shuffles, leave column s - 1 of the inverse in lane s
+#pragma unroll
+      for (int i = 0; i < DP; ++i) {
+        a[i] = column && i < d ? sc * jc[i] : 0.0;
+        b[i] = 0.0;
+        if (column && i == s - 1) {
+          a[i] += 1.0;
+          b[i] = 1.0;
+        }
+      }
+#pragma unroll
+      for (int pv = 0; pv < DMAX; ++pv) {
+        if (pv < d) {
+          int r = pv;
+          double best = fabs(a[pv]);
+#pragma unroll
+          for (int i = pv + 1; i < DMAX; ++i) {
+            const double m = fabs(a[i]);
+            if (i < d && m > best) {
+              best = m;
+              r = i;
+            }
+          }
+          r = __shfl(r, pv + 1, G);
+#pragma unroll
+          for (int i = pv + 1; i < DMAX; ++i) {
+            if (i == r) {
+              double t = a[pv];
+              a[pv] = a[i];
+              a[i] = t;
+              t = b[pv];
+              b[pv] = b[i];
+              b[i] = t;
+            }
+          }
+          const double piv = __shfl(a[pv], pv + 1, G);
+          const double inv = piv != 0.0 ? 1.0 / piv : 0.0;
+#pragma unroll
+          for (int i = 0; i < DMAX; ++i) {
+            if (i != pv) {
+              const double mult = __shfl(a[i] * inv, pv + 1, G);
+              a[i] = fma(-mult, a[pv], a[i]);
+              b[i] = fma(-mult, b[pv], b[i]);
+            }
+          }
+          a[pv] *= inv;
+          b[pv] *= inv;
+        }
+      }
+      // lane s needs ROW s - 1 of the inverse (the cotangent of column s - 1 of J is gl s (A^-T)[:, s - 1])
+#pragma unroll
+      for (int i = 0; i < DP; ++i)
+        if (i < d) cb[i * T + tid] = (float)b[i];
+      __syncthreads();
+      double ds = 0.0;
+#pragma unroll
+      for (int i = 0; i < DP; ++i) {
+        c[i] = 0.0;
+        if (i < d && value) {
+          const double g = live ? (double)gy[row * d + i] : 0.0;
+          c[i] = sc * g;
+          ds = fma(g, jc[i], ds);
+        } else if (i < d && column) {
+          const double inv_row = (double)cb[(s - 1) * T + tid - s + 1 + i];
+          c[i] = glv * sc * inv_row;
+          ds = fma(glv * inv_row, jc[i], ds);
+        }
+      }
+      ds = ires_lane_sum<G>(ds);  // <gy, g> + gl tr(A^-1 J)
+      if (value && live && dscale) dscale[row] = (float)ds;
+      __syncthreads();
+    }
+
+    // the final layer: its input is the state as the forward left it
+    {
+      const float* wt = img + final_at + dp;
+#pragma unroll
+      for (int i = 0; i < DP; ++i)
+        if (i < dp) cb[i * T + tid] = (float)c[i];
+      for (int k = 0; k < wtot; ++k) {
+        double acc = 0.0;
+#pragma unroll
+        for (int q = 0; q < DP / 4; ++q) {
+          if (4 * q < dp) {
+            const float4 w4 = *reinterpret_cast<const float4*>(wt + k * dp + 4 * q);
+            acc = fma((double)w4.x, c[4 * q + 0], acc);
+            acc = fma((double)w4.y, c[4 * q + 1], acc);
+            acc = fma((double)w4.z, c[4 * q + 2], acc);
+            acc = fma((double)w4.w, c[4 * q + 3], acc);
+          }
+        }
+        adjm[k * T] = (float)acc;
+      }
+      __syncthreads();
+      ires_outer_sums<G>(part, final_at + dp, final_at, dp, d, wtot, cb, st, T, tid);
+      __syncthreads();
+    }
+
+    // the dense layers, last first.  Entering layer l the state holds the layer's OUTPUT; dividing its first w_in
+    // entries by eta1 gives the layer's input back (the forward scaled them in place).
+    int at = final_at;
+    for (int l = sh.depth - 1; l >= 0; --l) {
+      const int w_in = d + e + l * sh.growth;
+      at -= 4 + op + w_in * op;
+      const float* lp = img + at;
+      const double eta1 = (double)lp[0], eta2 = (double)lp[1];
+      const float* bias = lp + 4;
+      const float* wt = bias + op;
+      double de1 = 0.0, de2 = 0.0;
+      for (int k = 0; k < w_in; ++k) {
+        const float h = (float)((double)mine[k * T] / eta1);
+        mine[k * T] = h;
+        de1 = fma((double)adjm[k * T], (double)h, de1);
+      }
+      for (int o = 0; o < op; o += 4) {
+        double sum[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) sum[q] = value ? (double)bias[o + q] : 0.0;
+        for (int k = 0; k < w_in; ++k) {
+          const double v = (double)mine[k * T];
+          const float4 w4 = *reinterpret_cast<const float4*>(wt + k * op + o);
+          sum[0] = fma((double)w4.x, v, sum[0]);
+          sum[1] = fma((double)w4.y, v, sum[1]);
+          sum[2] = fma((double)w4.z, v, sum[2]);
+          sum[3] = fma((double)w4.w, v, sum[3]);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const double pre = __shfl(sum[q], 0, G);
+          if (o + q < sh.out_ch) {  // uniform over the block
+            IresActJet f1, f2;
+            ires_act_jet<true>(sh.act, pre, p0, p1, f1);
+            const double a1 = (double)adjm[(w_in + o + q) * T];
+            double a2 = 0.0;
+            f2.f = f2.df = f2.d2f = f2.f_p0 = f2.df_p0 = f2.f_p1 = f2.df_p1 = 0.0;
+            if (sh.concat) {
+              ires_act_jet<true>(sh.act, -pre, p0, p1, f2);
+              a2 = (double)adjm[(w_in + sh.out_ch + o + q) * T];
+            }
+            // value stream: h = eta2 [f(pre), f(-pre)];  tangent: t = eta2 [f'(pre) u, -f'(-pre) u], u = W t_in
+            const double u = value ? 1.0 : sum[q];
+            double apre, bend = 0.0;
+            if (value) {
+              apre = eta2 * (f1.df * a1 - f2.df * a2);
+              de2 += f1.f * a1 + f2.f * a2;
+              dp0 += eta2 * (f1.f_p0 * a1 + f2.f_p0 * a2);
+              dp1 += eta2 * (f1.f_p1 * a1 + f2.f_p1 * a2);
+            } else {
+              apre = eta2 * (f1.df * a1 - f2.df * a2);
+              bend = eta2 * u * (f1.d2f * a1 + f2.d2f * a2);
+              de2 += u * (f1.df * a1 - f2.df * a2);
+              dp0 += eta2 * u * (f1.df_p0 * a1 - f2.df_p0 * a2);
+              dp1 += eta2 * u * (f1.df_p1 * a1 - f2.df_p1 * a2);
+            }
+            // the value stream's pre-activation also moves every tangent through f''
+            bend = ires_lane_sum<G>(bend);
+            if (value) apre += bend;
+            adjm[(w_in + o + q) * T] = (float)apre;
+          }
+        }
+      }
+      de1 = ires_lane_sum<64>(de1);
+      de2 = ires_lane_sum<64>(de2);
+      if ((tid & 63) == 0) {
+        red[2 * (tid >> 6)] = de1;
+        red[2 * (tid >> 6) + 1] = de2;
+      }
+      __syncthreads();
+      ires_outer_sums<G>(part, at + 4 + op, at + 4, op, sh.out_ch, w_in, adj + w_in * T, st, T, tid);
+      if (tid == 0) {
+        for (int w = 0; w < T / 64; ++w) {
+          part[at] += red[2 * w];
+          part[at + 1] += red[2 * w + 1];
+        }
+      }
+      // adjoint of the layer's input: eta1 times that of the copied entries plus W^T adj_pre
+      for (int k = 0; k < w_in; ++k) {
+        double acc = eta1 * (double)adjm[k * T];
+        for (int o = 0; o < op; o += 4) {
+          const float4 w4 = *reinterpret_cast<const float4*>(wt + k * op + o);
+          const float w[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (o + q < sh.out_ch) acc = fma((double)w[q], (double)adjm[(w_in + o + q) * T], acc);
+        }
+        adjm[k * T] = (float)acc;
+      }
+      __syncthreads();
+    }
+
+    if (value && live) {
+      for (int k = 0; k < d; ++k) dx[row * d + k] = (float)((double)gy[row * d + k] + (double)adjm[k * T]);
+      for (int k = 0; k < e; ++k) dextra[row * e + k] = adjm[(d + k) * T];
+    }
+  }
+
+  dp0 = ires_lane_sum<64>(dp0);
+  dp1 = ires_lane_sum<64>(dp1);
+  if ((tid & 63) == 0) {
+    red[2 * (tid >> 6)] = dp0;
+    red[2 * (tid >> 6) + 1] = dp1;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 0; w < T / 64; ++w) {
+      part[0] += red[2 * w];
+      part[1] += red[2 * w + 1];
+    }
+  }
+}
+
+// dimage[i] = the blocks' partials added in block order
+__global__ __launch_bounds__(256) void iresnet_backward_reduce_kernel(const double* __restrict__ ws, int blocks,
+                                                                      int image_floats, float* __restrict__ dimage) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= image_floats) return;
+  double sum = 0.0;
+  for (int b = 0; b < blocks; ++b) sum += ws[(size_t)b * image_floats + i];
+  dimage[i] = (float)sum;
+}
+
 // ---- launch ---------------------------------------------------------------------------------------------------------
 
 constexpr int kIresLdsLimit = 128 * 1024;
@@ -409,7 +771,101 @@ static int launch_ires_inverse(const float* y, const float* extra, const float* 
   return hipGetLastError();
 }
 
+constexpr int kIresBackwardBlocks = 256;
+
+// the backward's LDS: image, state, adjoint state, dp cotangent rows and two float64 words per wave.  The block is
+// chosen like the forward's: the largest of 256 / 128 / 64 threads (at least one row group) that stays within 64 KiB,
+// else 64 threads.  Worst case (d 16, width 128, 8692-float image): 4 (8692 + 272 * 64) + 16 = 104 416 bytes.
+static int ires_backward_threads(const IresShape& sh, int image_floats, int min_threads, size_t* lds) {
+  int threads = 256;
+  for (;; threads >>= 1) {
+    *lds = sizeof(float) * ((size_t)image_floats + (size_t)(2 * sh.wtot + ires_pad4(sh.d)) * threads) +
+           sizeof(double) * 2 * (threads / 64);
+    if (*lds <= 64 * 1024 || threads <= 64 || threads <= min_threads) break;
+  }
+  return threads;
+}
+
+static int ires_group(int d) { return d < 2 ? 2 : d < 4 ? 4 : d < 8 ? 8 : d < 16 ? 16 : 32; }
+
+static int64_t ires_backward_grid(int64_t n, const IresShape& sh, int image_floats, int max_blocks) {
+  size_t lds;
+  const int g = ires_group(sh.d);
+  const int rows = ires_backward_threads(sh, image_floats, g, &lds) / g;
+  const int64_t tiles = (n + rows - 1) / rows;
+  const int64_t cap = max_blocks > 0 && max_blocks < kIresBackwardBlocks ? max_blocks : kIresBackwardBlocks;
+  return tiles < cap ? tiles : cap;
+}
+
+template <int G>
+static int launch_ires_backward(const float* x, const float* extra, const float* scale, const float* image,
+                                const float* gy, const float* gl, float* dx, float* dextra, float* dscale,
+                                float* dimage, double* ws, int64_t n, const IresShape& sh, int image_floats,
+                                int max_blocks, hipStream_t s) {
+  size_t lds;
+  const int threads = ires_backward_threads(sh, image_floats, G, &lds);
+  if (lds > (size_t)kIresLdsLimit) return hipErrorInvalidConfiguration;
+  static PerDeviceOnce once;
+  const hipError_t e = ensure_max_dynamic_lds(once, reinterpret_cast<const void*>(&iresnet_backward_kernel<G>),
+                                              kIresLdsLimit);
+  if (e != hipSuccess) return e;
+  const int64_t grid = ires_backward_grid(n, sh, image_floats, max_blocks);
+  hipLaunchKernelGGL((iresnet_backward_kernel<G>), dim3((unsigned)grid), dim3(threads), lds, s, x, extra, scale, image,
+                     gy, gl, dx, dextra, dscale, ws, n, sh, image_floats);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(iresnet_backward_reduce_kernel, dim3((unsigned)((image_floats + 255) / 256)), dim3(256), 0, s, ws,
+                     (int)grid, image_floats, dimage);
+  return hipGetLastError();
+}
+
 }  // namespace fc
+
+extern "C" int fc_iresnet_backward_workspace(int64_t n, int32_t d, int32_t e, int32_t depth, int32_t growth,
+                                             int32_t activation, int32_t max_blocks) {
+  fc::IresShape sh;
+  sh.d = d;
+  sh.e = e;
+  sh.depth = depth;
+  sh.growth = growth;
+  const bool concat = activation == FC_IRES_ACT_CLIPSWISH || activation == FC_IRES_ACT_CSIN;
+  sh.out_ch = concat ? growth / 2 : growth;
+  if (n < 0 || d < 1 || d > FC_IRES_MAX_DIM || e < 0 || e > FC_IRES_MAX_WIDTH || depth < 1 ||
+      depth > FC_IRES_MAX_DEPTH || growth < 1 || growth > FC_IRES_MAX_WIDTH)
+    return -1;
+  if (!fc::ires_shape(d, e, depth, growth, activation, fc::ires_image_floats(sh), &sh)) return -1;
+  if (n == 0) return 0;
+  const int image_floats = fc::ires_image_floats(sh);
+  return (int)(fc::ires_backward_grid(n, sh, image_floats, max_blocks) * image_floats);
+}
+
+extern "C" int fc_iresnet_backward(const float* x, const float* extra, const float* scale, const float* image,
+                                   const float* gy, const float* gl, float* dx, float* dextra, float* dscale,
+                                   float* dimage, double* ws, int64_t n, int32_t d, int32_t e, int32_t depth,
+                                   int32_t growth, int32_t activation, int32_t image_floats, int32_t max_blocks,
+                                   void* stream) {
+  fc::IresShape sh;
+  if (n < 0 || !fc::ires_shape(d, e, depth, growth, activation, image_floats, &sh)) return hipErrorInvalidValue;
+  if (!dimage) return hipErrorInvalidValue;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n == 0) return hipMemsetAsync(dimage, 0, sizeof(float) * image_floats, s);
+  if (!x || !image || !gy || !gl || !dx || !ws || (e > 0 && (!extra || !dextra)) || (scale && !dscale))
+    return hipErrorInvalidValue;
+  if (d < 2)
+    return fc::launch_ires_backward<2>(x, extra, scale, image, gy, gl, dx, dextra, dscale, dimage, ws, n, sh,
+                                       image_floats, max_blocks, s);
+  if (d < 4)
+    return fc::launch_ires_backward<4>(x, extra, scale, image, gy, gl, dx, dextra, dscale, dimage, ws, n, sh,
+                                       image_floats, max_blocks, s);
+  if (d < 8)
+    return fc::launch_ires_backward<8>(x, extra, scale, image, gy, gl, dx, dextra, dscale, dimage, ws, n, sh,
+                                       image_floats, max_blocks, s);
+  if (d < 16)
+    return fc::launch_ires_backward<16>(x, extra, scale, image, gy, gl, dx, dextra, dscale, dimage, ws, n, sh,
+                                        image_floats, max_blocks, s);
+  return fc::launch_ires_backward<32>(x, extra, scale, image, gy, gl, dx, dextra, dscale, dimage, ws, n, sh,
+                                      image_floats, max_blocks, s);
+}
 
 extern "C" int fc_iresnet_forward(const float* x, const float* extra, const float* scale, const float* image, float* y,
                                   float* logabsdet, int64_t n, int32_t d, int32_t e, int32_t depth, int32_t growth,

@@ -81,7 +81,8 @@ from .image import (  # noqa: F401
 from .iresnet import (  # noqa: F401
     IRES_ACT_CLIPSWISH, IRES_ACT_CSIN, IRES_ACT_ELU, IRES_ACT_LEAKY_LSWISH, IRES_ACT_LIPSWISH, IRES_ACT_RELU,
     IRES_ACT_SIN, IRES_ACT_SWISH, IRES_ACT_TANH, IRES_CONCAT_ACTS, IRES_MAX_DEPTH, IRES_MAX_DIM, IRES_MAX_WIDTH,
-    _ires_operands, _pad4, iresnet_forward, iresnet_image_floats, iresnet_inverse, iresnet_supported)
+    IRES_DOUBLE_BACKWARD_MSG, _IResNetFunction, _ires_operands, _pad4, iresnet_autograd, iresnet_backward, iresnet_forward,
+    iresnet_image_floats, iresnet_inverse, iresnet_supported)
 from .cnf import (  # noqa: F401
     CNF_ACT_ELU, CNF_ACT_IDENTITY, CNF_ACT_RELU, CNF_ACT_SOFTPLUS, CNF_ACT_SQUARE, CNF_ACT_SWISH, CNF_ACT_TANH,
     CNF_EULER, CNF_KERNEL_MAX_LANES, CNF_LAYER_CONCAT, CNF_LAYER_CONCATSQUASH, CNF_LAYER_CONCAT_V2, CNF_LAYER_IGNORE, CNF_LAYER_SQUASH,

@@ -1,4 +1,4 @@
-"""Invertible residual blocks over Lipschitz DenseNets (eval mode)."""
+"""Invertible residual blocks over Lipschitz DenseNets: the eval-mode kernels and the training node around them."""
 import torch
 
 from flowconductor_amd import _hip
@@ -96,3 +96,80 @@ def iresnet_inverse(inputs, image, d, e, depth, growth, activation, extra=None, 
           _hip.ptr(image), _hip.ptr(x), _hip.ptr(iterations_out), y.shape[0], d, e, depth, growth, activation,
           image.numel(), int(max_iterations), float(atol), float(rtol), _hip.stream_ptr(y.device))
     return x
+
+
+# ---- training: fc_iresnet_backward ---------------------------------------------------------------------------------------
+IRES_DOUBLE_BACKWARD_MSG = (
+    "flowconductor_amd: the iResBlock kernel route (options 'iresblock_training') is once differentiable; for a gradient "
+    "of a gradient (create_graph=True) run the block with options.override(iresblock_training=False), the torch "
+    "composition")
+
+
+def iresnet_backward(inputs, image, d, e, depth, growth, activation, grad_outputs, grad_logabsdet, extra=None, scale=None,
+                     _max_blocks=0):
+    """The raw ``fc_iresnet_backward``: ``(grad_inputs [N, D], grad_image [image floats], grad_extra [N, E] or None,
+    grad_scale [N] or None)`` of ``iresnet_forward`` at ``inputs`` for the cotangents of its two outputs.  The streams
+    are recomputed in the kernel; the parameter gradient is summed without atomics (the same bits on every run).
+    ``_max_blocks`` caps the grid below the kernel's own 256 blocks (tests: several partials at a small N)."""
+    lib = _hip.load()
+    x, image, extra, scale = _ires_operands(inputs, image, d, e, depth, growth, activation, extra, scale)
+    n = x.shape[0]
+    gy = _hip.dev_f32(grad_outputs, "grad_outputs")
+    gl = _hip.dev_f32(grad_logabsdet, "grad_logabsdet")
+    if tuple(gy.shape) != tuple(x.shape) or gl.numel() != n:
+        raise ValueError("flowconductor_amd: iresnet_backward: cotangents of shapes %s / %s for %d rows of %d"
+                         % (tuple(gy.shape), tuple(gl.shape), n, d))
+    if gy.device != x.device or gl.device != x.device:
+        raise RuntimeError("flowconductor_amd: cotangents on %s / %s, rows on %s" % (gy.device, gl.device, x.device))
+    floats = lib.fc_iresnet_backward_workspace(n, d, e, depth, growth, activation, int(_max_blocks))
+    if floats < 0:
+        raise ValueError("flowconductor_amd: iresnet_backward: outside the kernel's limits")
+    dx = torch.empty_like(x)
+    dimage = torch.empty_like(image)
+    dextra = None if extra is None else torch.empty_like(extra)
+    dscale = None if scale is None else torch.empty(n, dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(floats, 1), dtype=torch.float64, device=x.device)
+    _call("fc_iresnet_backward", lib.fc_iresnet_backward, x.device, _hip.ptr(x), _hip.ptr(extra), _hip.ptr(scale),
+          _hip.ptr(image), _hip.ptr(gy), _hip.ptr(gl), _hip.ptr(dx), _hip.ptr(dextra), _hip.ptr(dscale),
+          _hip.ptr(dimage), _hip.ptr(ws), n, d, e, depth, growth, activation, image.numel(), int(_max_blocks),
+          _hip.stream_ptr(x.device))
+    return dx, dimage, dextra, dscale
+
+
+class _IResNetFunction(torch.autograd.Function):
+    """``fc_iresnet_forward`` with ``fc_iresnet_backward``: saves the rows, the image and the per-row extras -- no
+    activation and no Jacobian outlives the forward launch."""
+
+    @staticmethod
+    def forward(ctx, inputs, image, extra, scale, shape, max_blocks):
+        y, logabsdet = iresnet_forward(inputs.detach(), image.detach(), *shape,
+                                       extra=None if extra is None else extra.detach(),
+                                       scale=None if scale is None else scale.detach())
+        ctx.shape, ctx.max_blocks = shape, max_blocks
+        ctx.scale_shape = None if scale is None else tuple(scale.shape)
+        ctx.save_for_backward(inputs, image, extra, scale)
+        return y, logabsdet
+
+    @staticmethod
+    def backward(ctx, grad_y, grad_logabsdet):
+        if torch.is_grad_enabled():
+            raise RuntimeError(IRES_DOUBLE_BACKWARD_MSG)
+        return _IResNetFunction._backward_once(ctx, grad_y, grad_logabsdet)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _backward_once(ctx, grad_y, grad_logabsdet):
+        x, image, extra, scale = ctx.saved_tensors
+        dx, dimage, dextra, dscale = iresnet_backward(x, image, *ctx.shape, grad_y.contiguous(),
+                                                      grad_logabsdet.contiguous(), extra=extra, scale=scale,
+                                                      _max_blocks=ctx.max_blocks)
+        need = ctx.needs_input_grad
+        return (dx.view(x.shape) if need[0] else None, dimage if need[1] else None,
+                dextra if need[2] and dextra is not None else None,
+                dscale.view(ctx.scale_shape) if need[3] and dscale is not None else None, None, None)
+
+
+def iresnet_autograd(inputs, image, d, e, depth, growth, activation, extra=None, scale=None, _max_blocks=0):
+    """``iresnet_forward`` as one autograd node: gradients reach ``inputs``, ``image`` (every entry of the packed net),
+    ``extra`` and ``scale`` through one ``fc_iresnet_backward`` launch.  Once differentiable."""
+    return _IResNetFunction.apply(inputs, image, extra, scale, (d, e, depth, growth, activation), _max_blocks)

@@ -65,6 +65,12 @@ _DEFAULTS = {
     # tests), False never.  Off by default; a training step measured 1.07x to 1.13x faster than on the per-evaluation
     # route up to that size ("CNF training: the whole solve").
     "cnf_solve_training": False,
+    # iResBlock: a forward call that needs a gradient and would compute the EXACT determinant (train() mode with
+    # brute_force=True, eval mode with autograd on) runs as one autograd node, fc_iresnet_forward + fc_iresnet_backward
+    # (streams recomputed in the kernel), instead of the torch composition and its double backward.  The power-series
+    # estimators, inverse(), float64 modules and nets outside ops.iresnet_supported stay on the composition.  Off until
+    # a default can be moved on measured times ("iResBlock training").
+    "iresblock_training": False,
 }
 
 # options that take a few named values only: anything else is a mistake at the call site
@@ -72,6 +78,7 @@ _CHOICES = {
     "cnf_training": (False, True, "force"),
     "cnf_dopri5_kernel": (False, True, "force"),
     "cnf_solve_training": (False, True, "force"),
+    "iresblock_training": (False, True),
 }
 
 _values = dict(_DEFAULTS)

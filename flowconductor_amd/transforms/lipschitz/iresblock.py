@@ -14,15 +14,24 @@ Two routes:
   convergence in one launch without a host sync.  The per-row stopping test is ``|x - x_prev| <= atol + rtol |y|``
   (DESIGN.md, "Invertible residual blocks").
 
-``train()`` mode never takes the kernels, whatever ``brute_force`` says."""
+By default ``train()`` mode never takes the kernels, whatever ``brute_force`` says, and neither does a call that needs a
+gradient.  With ``options.override(iresblock_training=True)`` a ``forward`` call that needs a gradient and would compute
+the EXACT determinant -- ``train()`` mode with ``brute_force=True``, eval mode with autograd on -- is one autograd node:
+``fc_iresnet_forward`` on an image that torch builds differentiably from the live modules (so the gradient of the image
+flows on into the spectral normalisation, the concatenation weights and the activation scalars, and a training-mode
+call advances the power iteration exactly as one composition call does), and ``fc_iresnet_backward``, which recomputes
+the streams and sweeps them in reverse.  The node is once differentiable (``ops.IRES_DOUBLE_BACKWARD_MSG``).  The
+power-series estimators (their law is stochastic), ``inverse`` with gradients, float64 modules, hooks, a ``bn`` in
+training mode and every net outside the kernels' limits stay on the composition ("iResBlock training")."""
 import abc
+import contextlib
 import copy
 import logging
 from typing import Tuple
 
 import torch
 
-from flowconductor_amd import ops
+from flowconductor_amd import ops, options as fc_options
 from flowconductor_amd.nn.nets import activations
 from flowconductor_amd.nn.nets.invertible_densenet import (
     DenseNet,
@@ -76,7 +85,9 @@ class iResBlock(Transform):
     truncated power series, ``options['trace_estimator']`` between ``'neumann'`` and ``'basic'``.  Eval mode is always
     exact."""
 
-    _HIP_AUTOGRAD = True    # every route that runs with autograd on is the differentiable torch composition
+    _HIP_AUTOGRAD = True    # with autograd on: the differentiable torch composition, or the node of ops.iresnet_autograd
+
+    _backward_blocks = 0    # tests: a cap on fc_iresnet_backward's grid below the kernel's own (0: the kernel's)
 
     def __init__(self, contractive_network: _DenseNet, brute_force=False, unbiased_estimator=True, **options):
         super().__init__()
@@ -151,17 +162,24 @@ class iResBlock(Transform):
     def _use_kernels(self, inputs, context):
         if self.training or self.nnet.training or not isinstance(inputs, torch.Tensor):
             return None
+        if torch.is_grad_enabled() and self._needs_gradient(inputs, context):
+            return None
+        # a sub-module in training mode (net.bn.train()) means the composition
+        if any(m.training for m in ops.module_list(self.nnet)):
+            return None
+        return self._plan_for(inputs, context)
+
+    def _needs_gradient(self, inputs, context):
+        return (inputs.requires_grad or (context is not None and context.requires_grad)
+                or any(p.requires_grad for p in ops.param_list(self)))
+
+    def _plan_for(self, inputs, context):
+        """The kernel plan if rows, context, parameters and net are what the kernels take (whatever the mode), or None."""
         if not (inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() == 2
                 and inputs.shape[1] == self.nnet.dimension and inputs.shape[0] > 0):
             return None
         params = ops.param_list(self)
-        if torch.is_grad_enabled() and (inputs.requires_grad or (context is not None and context.requires_grad)
-                                        or any(p.requires_grad for p in params)):
-            return None
         if any(p.dtype != torch.float32 or p.device != inputs.device for p in params) or ops.has_hooks(self.nnet):
-            return None
-        # a sub-module in training mode (net.bn.train()) means the composition
-        if any(m.training for m in ops.module_list(self.nnet)):
             return None
         plan = ops.static_memo(self, "static_ok", (id(self.nnet), id(self.nnet.activation)), self._kernel_plan)
         if plan is None:
@@ -172,6 +190,20 @@ class iResBlock(Transform):
                                         and context.shape[0] == inputs.shape[0]):
             return None
         return plan
+
+    def _use_training_kernels(self, inputs, context):
+        """The plan for the one-node training route (options ``iresblock_training``): a call that needs a gradient and
+        whose estimator is the exact one."""
+        if not fc_options.get("iresblock_training") or not isinstance(inputs, torch.Tensor):
+            return None
+        if type(self.logabsdet_estimator) is not BruteForceDeterminantEstimator:
+            return None     # a power-series estimate is a random variable whose law must stay what it is
+        if not torch.is_grad_enabled() or not self._needs_gradient(inputs, context):
+            return None
+        bn = getattr(self.nnet, "bn", None)
+        if bn is not None and bn.training:
+            return None     # batch statistics of the context: the composition's business
+        return self._plan_for(inputs, context)
 
     def _image_constants(self):
         """The plain Python numbers that end up in the image (they have no version counter to watch)."""
@@ -227,12 +259,57 @@ class iResBlock(Transform):
         assert image.numel() == expected, (image.numel(), expected)
         return image
 
-    def _extras(self, plan, context):
-        """Per-row extra input channels and output factor of the conditional nets (torch, eval mode)."""
+    def _training_image(self, plan):
+        """The image of ``_pack_image``, built differentiably in the modules' own dtype (float32 on the kernel route) from
+        the live modules: every parametrised
+        ``weight`` is evaluated exactly once (in training mode with its power iteration, as one composition call does),
+        and the result is never cached -- it is a node of the caller's graph."""
+        net = self.nnet
+        layers = list(net.dense_net)
+        device, dtype = layers[-1].bias.device, layers[-1].bias.dtype
+        _, p0, p1 = _kernel_activation(net.activation)
+
+        def scalar(fn):
+            if fn is None:
+                return torch.zeros(1, dtype=dtype, device=device)
+            value = fn()
+            if isinstance(value, torch.Tensor):
+                return value.reshape(1)
+            return torch.full((1,), value, dtype=dtype, device=device)
+
+        def normalised(linear):
+            # What ``linear.weight`` evaluates, once: the power iteration in training mode, then W / max(1, sigma /
+            # coeff) with the factor held in float32 -- but sigma = <u, W v> summed in float64.  A float32 sum leaves
+            # sigma, and with it every entry of a clamped weight, up to 3 ulp from the image of ``_pack_image``.
+            norm, original = linear.parametrizations.weight[0], linear.parametrizations.weight.original
+            if norm.training:
+                norm._power_method(original, norm.n_power_iterations)
+            sigma = torch.dot(norm._u.clone().double(), original.double() @ norm._v.clone().double())
+            return original / torch.clamp(sigma / norm.coeff, min=1.0).to(torch.float32)
+
+        def padded(linear):
+            weight, bias = normalised(linear), linear.bias
+            pad = ops._pad4(weight.shape[0]) - weight.shape[0]
+            return [torch.nn.functional.pad(bias, (0, pad)), torch.nn.functional.pad(weight.t(), (0, pad)).reshape(-1)]
+
+        zeros2 = torch.zeros(2, dtype=dtype, device=device)
+        pieces = [scalar(p0), scalar(p1), zeros2]
+        for layer in layers[:-1]:
+            eta1, eta2 = layer.get_eta1_eta2()
+            pieces += [eta1.reshape(1), eta2.reshape(1), zeros2] + padded(layer.network[0])
+        pieces += padded(layers[-1])
+        image = torch.cat(pieces)
+        expected = ops.iresnet_image_floats(net.dimension, plan[3], net.densenet_depth, net.densenet_growth, plan[0])
+        assert image.numel() == expected and image.dtype == dtype, (image.numel(), expected, image.dtype)
+        return image
+
+    def _extras(self, plan, context, differentiable=False):
+        """Per-row extra input channels and output factor of the conditional nets (torch, eval-mode ``bn``);
+        ``differentiable``: under the caller's autograd mode, so the context nets train through them."""
         net, extra, scale = self.nnet, None, None
         if context is None:
             return extra, scale
-        with torch.no_grad():
+        with contextlib.nullcontext() if differentiable else torch.no_grad():
             context = net.bn(context)
             if plan[4]:
                 scale = torch.tanh(net.factor_net(context)).reshape(-1).contiguous()
@@ -259,6 +336,11 @@ class iResBlock(Transform):
         if plan is not None:
             extra, scale = self._extras(plan, context)
             return ops.iresnet_forward(inputs, self._image(plan), *self._shape_args(plan), extra=extra, scale=scale)
+        plan = self._use_training_kernels(inputs, context)
+        if plan is not None:
+            extra, scale = self._extras(plan, context, differentiable=True)
+            return ops.iresnet_autograd(inputs, self._training_image(plan), *self._shape_args(plan), extra=extra,
+                                        scale=scale, _max_blocks=self._backward_blocks)
         g, logdetgrad = self._g_and_logabsdet(inputs, context=context)
         return inputs + g, logdetgrad.view(-1)
 

@@ -581,6 +581,24 @@ int fc_iresnet_inverse(const float* y, const float* extra, const float* scale, c
                        uint32_t* max_iters, int64_t n, int32_t d, int32_t e, int32_t depth, int32_t growth,
                        int32_t activation, int32_t image_floats, int32_t max_iterations, float atol, float rtol,
                        void* stream);
+/* fc_iresnet_backward  the reverse sweep of fc_iresnet_forward for the cotangents gy [n, d] of y and gl [n] of logabsdet.
+ *           Nothing but x, extra, scale and the image is read from the forward call: a block recomputes the value and
+ *           tangent streams in LDS (the forward's lane groups and rounding points), inverts I + scale J inside the lane
+ *           group (Gauss-Jordan with partial pivoting, float64) and sweeps the layers from the last.
+ *   dx      [n, d], dextra [n, e] (NULL when e == 0), dscale [n] (NULL when scale is NULL): written once per row
+ *   dimage  [image_floats]: the gradient of every image entry (weights in the image's transposed padded layout, biases,
+ *           eta1 / eta2, p0 / p1; padding entries zero).  Every block sums its rows into one image-shaped float64
+ *           partial of ws in a fixed order and a second kernel adds the partials in block order: no atomics, the same
+ *           bits on every run.
+ *   ws      float64 [fc_iresnet_backward_workspace(...)]; max_blocks caps the grid (<= 0: the default of 256 blocks;
+ *           the blocks stride over the row tiles).
+ * fc_iresnet_backward_workspace  the number of float64 entries of ws, or -1 for a shape outside the limits. */
+int fc_iresnet_backward(const float* x, const float* extra, const float* scale, const float* image, const float* gy,
+                        const float* gl, float* dx, float* dextra, float* dscale, float* dimage, double* ws, int64_t n,
+                        int32_t d, int32_t e, int32_t depth, int32_t growth, int32_t activation, int32_t image_floats,
+                        int32_t max_blocks, void* stream);
+int fc_iresnet_backward_workspace(int64_t n, int32_t d, int32_t e, int32_t depth, int32_t growth, int32_t activation,
+                                  int32_t max_blocks);
 
 /* ---- continuous normalizing flows (eval mode) ------------------------------------------------- */
 /* ODEfunc over an ODEnet of time-conditioned linear layers (CNF/neural_odes/odefunc.py:98-182,
