@@ -38,10 +38,10 @@ __device__ __forceinline__ void householder(Row<E>& x, const float* __restrict__
   }
 }
 
-// y_i = sum_j W[i][j] x_j with Wt = W^T stored [d_in][d_out] (lane i reads a contiguous column)
+// y_i = sum_j W[i][j] x_j with Wt = W^T stored [d_in][d_out] (lane i reads a contiguous column).  EVERY entry of W is read:
+// a triangular W (the U of mode 1, the shared R1 / R2 of the Sylvester flow) must hold its zeros.
 template <int E>
-__device__ __forceinline__ void matvec(Row<E>& y, const Row<E>& x, const float* __restrict__ wt, int d,
-                                       int lane, int j_lo_is_i /*1: upper-triangular W (skip j<i)*/) {
+__device__ __forceinline__ void matvec(Row<E>& y, const Row<E>& x, const float* __restrict__ wt, int d, int lane) {
 #pragma unroll
   for (int e = 0; e < E; ++e) y.v[e] = 0.f;
   for (int j = 0; j < d; ++j) {
@@ -305,16 +305,16 @@ __global__ __launch_bounds__(256) void linear_kernel(const float* __restrict__ x
     Row<E> r, t;
     load_row<E>(r, x + row * d, d, lane);
     if (mode == 0) {
-      matvec<E>(t, r, at, d, lane, 0);
+      matvec<E>(t, r, at, d, lane);
 #pragma unroll
       for (int e = 0; e < E; ++e) r.v[e] = t.v[e] + bv.v[e];
     } else if (mode == 3) {
 #pragma unroll
       for (int e = 0; e < E; ++e) t.v[e] = r.v[e] - bv.v[e];
-      matvec<E>(r, t, at, d, lane, 0);
+      matvec<E>(r, t, at, d, lane);
     } else if (mode == 1) {
-      matvec<E>(t, r, at, d, lane, 1);   // U x
-      matvec<E>(r, t, bt, d, lane, 0);   // L (U x)
+      matvec<E>(t, r, at, d, lane);   // U x
+      matvec<E>(r, t, bt, d, lane);   // L (U x)
 #pragma unroll
       for (int e = 0; e < E; ++e) r.v[e] = r.v[e] + bv.v[e];
     } else {
@@ -377,7 +377,7 @@ __global__ __launch_bounds__(256) void sylvester_kernel(const float* __restrict_
     if constexpr (kPS) householder_rows<E>(t, qr, m, d, lane, true);      // Q^T z
     else householder<E, true>(t, qr, m, d, lane, true);
     if constexpr (kPS) matvec_rows_upper<E>(a, t, r1, d, lane);   // R1 Q^T z (row-major per-sample R, upper part only)
-    else matvec<E>(a, t, r1, d, lane, 1);
+    else matvec<E>(a, t, r1, d, lane);
     float ld = 0.f;
 #pragma unroll
     for (int e = 0; e < E; ++e) {
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(256) void sylvester_kernel(const float* __restrict_
     }
     ld = per_sample ? wave_sum(ld) : wave_sum_lds(ld);
     if constexpr (kPS) matvec_rows_upper<E>(t, a, r2, d, lane);   // R2 act
-    else matvec<E>(t, a, r2, d, lane, 1);
+    else matvec<E>(t, a, r2, d, lane);
     if constexpr (kPS) householder_rows<E>(t, qr, m, d, lane, false);     // Q R2 act
     else householder<E, true>(t, qr, m, d, lane, false);
 #pragma unroll

@@ -577,7 +577,12 @@ def sylvester(inputs, q_vectors, r1, r2, bias):
     """Sylvester flow forward + logabsdet (reference no_analytic_inv/planar.py:144-166).
 
     Shared parameters: ``q [M, D]``, ``r1``/``r2`` ``[D, D]`` upper triangular, ``bias [D]``;
-    per-sample: ``q [N, M, D]``, ``r1``/``r2`` ``[N, D, D]``, ``bias [N, D]``."""
+    per-sample: ``q [N, M, D]``, ``r1``/``r2`` ``[N, D, D]``, ``bias [N, D]``.
+
+    The two forms read the matrices differently.  The shared form multiplies by EVERY entry of ``r1`` / ``r2`` (as
+    ``pack_sylvester`` and ``sylvester_mm`` do), so the caller must pass matrices whose strict lower triangle is zero; an
+    entry there enters the outputs, while the log-determinant is still that of the diagonal.  The per-sample form reads
+    the upper triangle of every matrix only: whatever a hyper-network leaves below the diagonal is never fetched."""
     lib = _hip.load()
     x = _rows(inputs)
     _hip.require_no_grad(inputs)
