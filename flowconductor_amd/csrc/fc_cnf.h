@@ -1,13 +1,13 @@
-// What the continuous-normalizing-flow kernels share (fc_cnf.hip, fc_cnf_dopri5.hip): the description of a net, the
-// activations, the source of the terms that depend on t alone, the block set-up (CnfBlock), cnf_hidden_layers / cnf_net /
-// cnf_field_row -- the one copy of the layer arithmetic, which the backward kernel's recompute runs too -- and the host
-// side's launch plan.  The image layout and the lane layout are described at the top of fc_cnf.hip.
+// What the continuous-normalizing-flow kernels share (fc_cnf.hip, fc_cnf_dopri5.hip) on top of the lane-group scaffold
+// of fc_lane_group.h (the block set-up, the weight sums, the launch plan): the description of a net, the activations,
+// the source of the terms that depend on t alone, and cnf_hidden_layers / cnf_net / cnf_field_row -- the one copy of the
+// layer arithmetic, which the backward kernel's recompute runs too.  The image layout and the lane layout are described
+// at the top of fc_cnf.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <type_traits>
 #include "../../include/flowcon_hip.h"
-#include "fc_device.h"
+#include "fc_lane_group.h"
 
 namespace fc {
 
@@ -17,17 +17,15 @@ struct CnfShape {
   double scale, p0;
 };
 
-__host__ __device__ inline int cnf_pad4(int v) { return (v + 3) & ~3; }
-
 __host__ __device__ inline int cnf_image_floats(const CnfShape& sh) {
   int total = 0;
-  for (int l = 0; l < sh.layers; ++l) total += (5 + sh.w[l]) * cnf_pad4(sh.w[l + 1]);
+  for (int l = 0; l < sh.layers; ++l) total += (5 + sh.w[l]) * pad4(sh.w[l + 1]);
   return total;
 }
 
 __host__ __device__ inline int cnf_table_doubles(const CnfShape& sh) {
   int total = 0;
-  for (int l = 0; l < sh.layers; ++l) total += 3 * cnf_pad4(sh.w[l + 1]);
+  for (int l = 0; l < sh.layers; ++l) total += 3 * pad4(sh.w[l + 1]);
   return total;
 }
 
@@ -106,7 +104,7 @@ __device__ __forceinline__ void cnf_time_table(const float* img, double* tab, co
   const float* p = img;
   double* q = tab;
   for (int l = 0; l < sh.layers; ++l) {
-    const int op = cnf_pad4(sh.w[l + 1]);
+    const int op = pad4(sh.w[l + 1]);
     for (int o = tid; o < op; o += T) {
       q[o] = (double)p[o] + (double)p[op + o] * t;
       q[op + o] = sh.gated ? 1.0 / (1.0 + exp(-((double)p[2 * op + o] * t + (double)p[3 * op + o]))) : 1.0;
@@ -117,45 +115,20 @@ __device__ __forceinline__ void cnf_time_table(const float* img, double* tab, co
   }
 }
 
-// ---- the block ------------------------------------------------------------------------------------------------------
-
-// Dynamic LDS of every kernel: the image | `mid`, the doubles between (the block's time table, or a gate strip per row)
-// | the state columns st[k][thread].  A row is carried by the G lanes of a group: lane s of row r of the block.
-struct CnfBlock {
-  float* img;
-  double* mid;
-  float* st;
-  float* mine;  // st + tid: this lane's entry of a column, the columns T apart
-  int T, tid, s, r, rows, half;  // half: the second ping-pong buffer, that many floats after the first
-  int64_t tiles;
+// The scaffold's block with the forward kernels' two ping-pong columns: `mid` holds the block's time table or a gate
+// strip per row.  Like group_block it ends without a barrier.
+struct CnfBlock : GroupBlock {
+  int half;  // the second ping-pong buffer, that many floats after the first
 };
 
-// Carves the LDS and starts the image copy; it ends WITHOUT a barrier, which the caller owes before the image is read.
 template <int G>
 __device__ __forceinline__ CnfBlock cnf_block(float* lds, const float* __restrict__ image, int image_floats,
                                               int block_doubles, int row_doubles, int64_t n, const CnfShape& sh) {
   CnfBlock b;
-  b.T = blockDim.x;
-  b.tid = threadIdx.x;
-  b.s = b.tid % G;
-  b.r = b.tid / G;
-  b.rows = b.T / G;
+  static_cast<GroupBlock&>(b) = group_lanes<G>();
   b.half = cnf_max_width(sh) * b.T;
-  b.img = lds;
-  b.mid = reinterpret_cast<double*>(lds + image_floats);
-  b.st = lds + image_floats + 2 * (block_doubles + b.rows * row_doubles);
-  b.mine = b.st + b.tid;
-  b.tiles = (n + b.rows - 1) / b.rows;
-  for (int i = b.tid; i < image_floats; i += b.T) b.img[i] = image[i];
+  group_carve(b, lds, image, image_floats, block_doubles, row_doubles, n);
   return b;
-}
-
-// The row of this lane's group in `tile`.  A group past the end runs along on the last row (the shuffles, and the
-// barriers where a kernel has them, need every lane); only live rows are stored.
-__device__ __forceinline__ int64_t cnf_tile_row(const CnfBlock& b, int64_t tile, int64_t n, bool& live) {
-  const int64_t row = tile * b.rows + b.r;
-  live = row < n;
-  return live ? row : n - 1;
 }
 
 // ---- where cnf_net takes the time terms of a layer from ---------------------------------------------------------------
@@ -231,20 +204,11 @@ struct CnfStacked {
 
 // ---- the net on one stream -------------------------------------------------------------------------------------------
 
-// sum[c] = (value ? b + w_t t : 0) + sum_k W[o + c][k] x[k]: a tangent has no bias and no time terms
+// weight_sum4 with the layer's time-dependent bias b + w_t t
 template <class Time>
 __device__ __forceinline__ void cnf_sum4(const float* wt, const Time& tm, const float* p, const float* x, int T, int in,
                                          int op, int o, bool value, double (&sum)[4]) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c) sum[c] = value ? tm.bias(p, op, o + c) : 0.0;
-  for (int k = 0; k < in; ++k) {
-    const double v = (double)x[k * T];
-    const float4 w4 = *reinterpret_cast<const float4*>(wt + k * op + o);
-    sum[0] = fma((double)w4.x, v, sum[0]);
-    sum[1] = fma((double)w4.y, v, sum[1]);
-    sum[2] = fma((double)w4.z, v, sum[2]);
-    sum[3] = fma((double)w4.w, v, sum[3]);
-  }
+  weight_sum4(wt, x, T, in, op, o, value, [&](int oc) { return tm.bias(p, op, oc); }, sum);
 }
 
 // From cnf_sum4's sum of output o: lin, this stream's gated product, and pre, the value stream's, which is the
@@ -265,7 +229,7 @@ __device__ __forceinline__ const float* cnf_hidden_layers(const float* img, Time
                                                           const CnfShape& sh, bool value) {
   const float* p = img;
   for (int l = 0; l + 1 < sh.layers; ++l) {
-    const int in = sh.w[l], width = sh.w[l + 1], op = cnf_pad4(width);
+    const int in = sh.w[l], width = sh.w[l + 1], op = pad4(width);
     const float* wt = p + 5 * op;
     const float* cur = at.in(T);
     float* nxt = at.out(in, T);
@@ -301,7 +265,7 @@ __device__ __forceinline__ void cnf_net(const float* img, Time tm, float* mine, 
   CnfPingPong at{mine, mine + half};
   const float* p = cnf_hidden_layers<G>(img, tm, at, T, sh, value);
   const float* cur = at.in(T);
-  const int in = sh.w[sh.layers - 1], dp = cnf_pad4(sh.d);
+  const int in = sh.w[sh.layers - 1], dp = pad4(sh.d);
   const float* wt = p + 5 * dp;
   tm.begin_layer(p, dp);
 #pragma unroll
@@ -342,9 +306,7 @@ struct CnfExactDiv {
 #pragma unroll
     for (int i = 0; i < DP; ++i)
       if (i == s - 1 && i < d) diag = k[i];
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) diag += __shfl_xor(diag, off, G);
-    return diag;
+    return lane_sum<G>(diag);
   }
 };
 
@@ -390,12 +352,6 @@ __device__ __forceinline__ void cnf_field_row(const float* img, Time tm, Div dv,
   negdiv = -div;
 }
 
-template <int G>
-struct CnfGroup {
-  static constexpr int DMAX = G == 32 ? 16 : G - 1;
-  static constexpr int DP = (DMAX + 3) & ~3;
-};
-
 // ---- entry: the net a call describes -----------------------------------------------------------------------------------
 
 inline bool cnf_shape(int d, int layers, const int32_t* hidden, int kind, int act, int residual, float scale, float p0,
@@ -434,72 +390,12 @@ inline bool cnf_operands(const void* in, const void* image, const void* out, con
 
 // ---- launch ---------------------------------------------------------------------------------------------------------
 
-constexpr int kCnfLdsLimit = 128 * 1024;
-constexpr int kCnfMaxBlocks = 2048;
-
-// The smallest power of two >= d + 1 lanes carry a row; under Hutchinson's estimator 2 lanes do.
-inline int cnf_group(const CnfShape& sh, bool hutchinson = false) {
-  if (hutchinson || sh.d < 2) return 2;
-  return sh.d < 4 ? 4 : sh.d < 8 ? 8 : sh.d < 16 ? 16 : 32;
-}
-
-// f(std::integral_constant<int, N>) for the N of the list that v equals
-template <int... Ns, class F>
-inline int cnf_with_constant(int v, F&& f) {
-  int result = hipErrorInvalidConfiguration;
-  (void)((v == Ns && ((result = f(std::integral_constant<int, Ns>{})), true)) || ...);
-  return result;
-}
-
-// What a kernel keeps in dynamic LDS besides the image.
-struct CnfLds {
-  size_t block_bytes;  // once per block
-  int thread_floats;   // per thread: the state columns
-  int row_doubles;     // per row
-};
+// The lane group of a net's rows; under Hutchinson's estimator 2 lanes carry a row.
+inline int cnf_group(const CnfShape& sh, bool hutchinson = false) { return hutchinson ? 2 : lane_group(sh.d); }
 
 // the forward kernels' time table and two ping-pong columns
-inline CnfLds cnf_forward_lds(const CnfShape& sh) {
-  return {sizeof(double) * (size_t)cnf_table_doubles(sh), 2 * cnf_max_width(sh), 0};
-}
-
-enum CnfFit {
-  kCnfPrefer64K,     // the largest block within 64 KiB, else the smallest block if it fits the limit
-  kCnfLargestBlock,  // the largest block that fits the limit
-};
-
-struct CnfLaunch {
-  int threads;  // 0: not even the smallest block fits kCnfLdsLimit
-  size_t lds;
-  int64_t grid;
-};
-
-// Blocks of 256, 128 or 64 threads, a block per tile of threads / group rows up to max_blocks.
-inline CnfLaunch cnf_launch_plan(int image_floats, int group, const CnfLds& need, CnfFit fit, int64_t n,
-                                 int max_blocks) {
-  const size_t aim = fit == kCnfPrefer64K ? 64 * 1024 : (size_t)kCnfLdsLimit;
-  CnfLaunch plan{256, 0, 0};
-  for (;; plan.threads >>= 1) {
-    plan.lds = sizeof(float) * ((size_t)image_floats + (size_t)need.thread_floats * plan.threads) + need.block_bytes +
-               sizeof(double) * (size_t)need.row_doubles * (size_t)(plan.threads / group);
-    if (plan.lds <= aim || plan.threads <= 64) break;
-  }
-  if (plan.lds > (size_t)kCnfLdsLimit) plan.threads = 0;
-  const int rows = plan.threads ? plan.threads / group : 1;
-  const int64_t tiles = (n + rows - 1) / rows;
-  plan.grid = tiles < max_blocks ? tiles : max_blocks;
-  return plan;
-}
-
-// Raises the kernel's dynamic-LDS limit once per device and launches it.
-template <auto Kernel, class... Args>
-inline int cnf_launch(const CnfLaunch& plan, hipStream_t s, Args... args) {
-  if (!plan.threads) return hipErrorInvalidConfiguration;
-  static PerDeviceOnce once;
-  const hipError_t e = ensure_max_dynamic_lds(once, reinterpret_cast<const void*>(Kernel), kCnfLdsLimit);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(Kernel, dim3((unsigned)plan.grid), dim3(plan.threads), plan.lds, s, args...);
-  return hipGetLastError();
+inline GroupLds cnf_forward_lds(const CnfShape& sh) {
+  return {sizeof(double) * (size_t)cnf_table_doubles(sh), 2 * cnf_max_width(sh), 0, 0};
 }
 
 }  // namespace fc

@@ -8,9 +8,10 @@
 //                      Hutchinson's estimate, and the gradients of both outputs (further down)
 //   fc_cnf_integrate_train / fc_cnf_integrate_backward   the whole fixed-step solve as an autograd node: the solve with
 //                      a tape of its stage inputs, and the reverse sweep over that tape            one launch each
-// (fc_cnf_dopri5, the adaptive solve with per-row step control, is in fc_cnf_dopri5.hip; what the kernels share --
-// CnfShape, the activations, cnf_time_table, CnfBlock, cnf_hidden_layers, cnf_net, cnf_field_row and the launch plan --
-// is in fc_cnf.h.)
+// (fc_cnf_dopri5, the adaptive solve with per-row step control, is in fc_cnf_dopri5.hip; what the CNF kernels share --
+// CnfShape, the activations, cnf_time_table, cnf_hidden_layers, cnf_net and cnf_field_row -- is in fc_cnf.h.  The block
+// set-up (GroupBlock), the weight sums and the launch plan are the lane-group scaffold's, fc_lane_group.h, which the
+// iResBlock kernels use too; the sum over the blocks' partials is fc_partial_sum.h.)
 //
 // f is an MLP whose layers all reduce to
 //     pre = W x + b + w_t t,   out = pre * gate + w_b t,   gate = sigmoid(w_g t + b_g)  or  1
@@ -34,6 +35,7 @@
 // is the one place that decides this); the integrator keeps (z, logp) and the stage slopes in float64 registers and
 // rounds a stage's state to float32 where it enters the net.
 #include "fc_cnf.h"
+#include "fc_partial_sum.h"
 
 namespace fc {
 
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(256) void cnf_field_kernel(const float* __restrict_
 
   for (int64_t tile = blockIdx.x; tile < b.tiles; tile += gridDim.x) {
     bool live;
-    const int64_t row = cnf_tile_row(b, tile, n, live);
+    const int64_t row = tile_row(b, tile, n, live);
     float xin[DP];
 #pragma unroll
     for (int i = 0; i < DP; ++i) xin[i] = i < d ? y[row * d + i] : 0.f;
@@ -97,7 +99,7 @@ __device__ __forceinline__ double cnf_weight(int method, int stage) {
 
 // Div as in cnf_field_kernel, with one row of e for the whole solve.  Tape: the float32 state every stage hands to the
 // net is kept as tape[step * stages + stage][row][:], which is all fc_cnf_integrate_backward needs of the forward.
-// fc_cnf_integrate is the instance <G, CnfGroup<G>::DP, CnfExactDiv, false>.
+// fc_cnf_integrate is the instance <G, LaneGroup<G>::DP, CnfExactDiv, false>.
 template <int G, int DP, class Div, bool Tape>
 __global__ __launch_bounds__(256) void cnf_integrate_kernel(const float* __restrict__ z, const float* __restrict__ logp,
                                                             const float* __restrict__ e,
@@ -119,7 +121,7 @@ __global__ __launch_bounds__(256) void cnf_integrate_kernel(const float* __restr
   // the tile loop's trip count depends on the block alone, so the barriers below are met by every thread
   for (int64_t tile = blockIdx.x; tile < b.tiles; tile += gridDim.x) {
     bool live;
-    const int64_t row = cnf_tile_row(b, tile, n, live);
+    const int64_t row = tile_row(b, tile, n, live);
     double yv[DP], acc[DP], k[DP];
 #pragma unroll
     for (int i = 0; i < DP; ++i) {
@@ -195,8 +197,8 @@ __global__ __launch_bounds__(256) void cnf_integrate_kernel(const float* __restr
 //
 // The sums over rows: inside a block every entry of the gradient image is owned by one thread that adds the lanes in
 // a fixed (rotated, bank-conflict-free) order in float64 and accumulates its tiles in the block's float64 partial
-// image in global memory; cnf_backward_sum_kernel adds the blocks' partials in block order and rounds once.  No
-// atomics: bitwise reproducible.  scale_output multiplies the results, not the seeds.
+// image in global memory; partial_sum_kernel (fc_partial_sum.h) adds the blocks' partials in block order and rounds
+// once.  No atomics: bitwise reproducible.  scale_output multiplies the results, not the seeds.
 
 // floats of LDS a lane of the backward kernel owns: the inputs of every layer, the seeds, the gate products
 __host__ __device__ inline int cnf_backward_lane_floats(const CnfShape& sh) {
@@ -234,7 +236,7 @@ __device__ __forceinline__ void cnf_backward_walk(const CnfBlock& b, const CnfSh
 
   for (int l = sh.layers - 1; l >= 0; --l) {
     const bool last = l == sh.layers - 1;
-    const int in = sh.w[l], width = sh.w[l + 1], op = cnf_pad4(width);
+    const int in = sh.w[l], width = sh.w[l + 1], op = pad4(width);
     const float* wt = p + 5 * op;
     const CnfBlockTime here{q};          // the layer's time terms
     float* x = mine + off * T;           // this lane's input of the layer
@@ -366,8 +368,8 @@ __device__ __forceinline__ void cnf_backward_walk(const CnfBlock& b, const CnfSh
     }
     if (l > 0) {
       const int below = sh.w[l - 1];
-      p -= (5 + below) * cnf_pad4(in);
-      q -= 3 * cnf_pad4(in);
+      p -= (5 + below) * pad4(in);
+      q -= 3 * pad4(in);
       off -= below;
     }
   }
@@ -393,7 +395,7 @@ __global__ __launch_bounds__(256) void cnf_backward_kernel(
   // the trip count depends on the block alone, so every thread meets the barriers of the walk
   for (int64_t tile = blockIdx.x; tile < b.tiles; tile += gridDim.x) {
     bool live;  // a row past the end runs along with zero seeds
-    const int64_t row = cnf_tile_row(b, tile, n, live);
+    const int64_t row = tile_row(b, tile, n, live);
     for (int i = 0; i < d; ++i)
       b.mine[i * b.T] = value ? y[row * d + i] : (e ? e[row * d + i] : (i == s - 1 ? 1.f : 0.f));
     const float gn = live ? g_negdiv[row] : 0.f;
@@ -443,7 +445,7 @@ __global__ __launch_bounds__(256) void cnf_solve_backward_kernel(
   // the trip counts depend on the block alone, so every thread meets the barriers below and those of the walk
   for (int64_t tile = blockIdx.x; tile < b.tiles; tile += gridDim.x) {
     bool live;  // a row past the end runs along with zero seeds and touches no plane
-    const int64_t row = cnf_tile_row(b, tile, n, live);
+    const int64_t row = tile_row(b, tile, n, live);
     const size_t at = (size_t)row * (size_t)d;
     double* ybar = planes + at;
     double* total = ybar + plane;
@@ -503,20 +505,8 @@ __global__ __launch_bounds__(256) void cnf_solve_backward_kernel(
   }
 }
 
-// g_image[i] = scale * (the blocks' partials in block order)
-__global__ __launch_bounds__(256) void cnf_backward_sum_kernel(const double* __restrict__ partial,
-                                                               float* __restrict__ g_image, int blocks,
-                                                               int image_floats, double scale) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= image_floats) return;
-  double sum = 0.0;
-  for (int b = 0; b < blocks; ++b) sum += partial[(size_t)b * (size_t)image_floats + i];
-  g_image[i] = (float)(sum * scale);
-}
-
 // ---- launch ---------------------------------------------------------------------------------------------------------
 
-constexpr int kCnfBackwardMaxBlocks = 256;
 constexpr int kCnfTrainMaxLayers = FC_CNF_TRAIN_MAX_HIDDEN_LAYERS + 1;
 
 // the exact divergence by the group of d, Hutchinson's estimate (e) in 2 lanes by the padded d
@@ -524,24 +514,24 @@ static int launch_cnf_field(const float* y, const float* e, const float* image, 
                             int64_t n, const CnfShape& sh, int image_floats, float t_host, const float* t_dev,
                             hipStream_t s) {
   const int group = cnf_group(sh, e != nullptr), table = cnf_table_doubles(sh);
-  const CnfLaunch plan = cnf_launch_plan(image_floats, group, cnf_forward_lds(sh), kCnfPrefer64K, n, kCnfMaxBlocks);
+  const GroupLaunch plan = group_launch_plan(image_floats, group, cnf_forward_lds(sh), kPrefer64K, n, kGroupMaxBlocks);
   if (e)
-    return cnf_with_constant<4, 8, 16>(sh.d <= 4 ? 4 : sh.d <= 8 ? 8 : 16, [&](auto dp) {
+    return with_constant<4, 8, 16>(sh.d <= 4 ? 4 : sh.d <= 8 ? 8 : 16, [&](auto dp) {
       constexpr int DP = decltype(dp)::value;
-      return cnf_launch<&cnf_field_kernel<2, DP, CnfHutchinsonDiv<DP>>>(plan, s, y, e, image, dy, negdiv, evals, n, sh,
+      return group_launch<&cnf_field_kernel<2, DP, CnfHutchinsonDiv<DP>>>(plan, s, y, e, image, dy, negdiv, evals, n, sh,
                                                                         image_floats, table, t_host, t_dev);
     });
-  return cnf_with_constant<2, 4, 8, 16, 32>(group, [&](auto g) {
+  return with_constant<2, 4, 8, 16, 32>(group, [&](auto g) {
     constexpr int G = decltype(g)::value;
-    return cnf_launch<&cnf_field_kernel<G, CnfGroup<G>::DP, CnfExactDiv>>(plan, s, y, e, image, dy, negdiv, evals, n,
+    return group_launch<&cnf_field_kernel<G, LaneGroup<G>::DP, CnfExactDiv>>(plan, s, y, e, image, dy, negdiv, evals, n,
                                                                           sh, image_floats, table, t_host, t_dev);
   });
 }
 
 template <int G, int DP, class Div, class... Args>
-static int launch_cnf_integrate_as(bool tape, const CnfLaunch& plan, hipStream_t s, Args... args) {
-  return tape ? cnf_launch<&cnf_integrate_kernel<G, DP, Div, true>>(plan, s, args...)
-              : cnf_launch<&cnf_integrate_kernel<G, DP, Div, false>>(plan, s, args...);
+static int launch_cnf_integrate_as(bool tape, const GroupLaunch& plan, hipStream_t s, Args... args) {
+  return tape ? group_launch<&cnf_integrate_kernel<G, DP, Div, true>>(plan, s, args...)
+              : group_launch<&cnf_integrate_kernel<G, DP, Div, false>>(plan, s, args...);
 }
 
 // the fixed-step solve: instances as launch_cnf_field picks them, with the tape or without
@@ -549,17 +539,17 @@ static int launch_cnf_integrate(const float* z, const float* logp, const float* 
                                 float* logp_out, float* tape, float* evals, int64_t n, const CnfShape& sh,
                                 int image_floats, double t0, double t1, int steps, int method, hipStream_t s) {
   const int group = cnf_group(sh, e != nullptr), table = cnf_table_doubles(sh);
-  const CnfLaunch plan = cnf_launch_plan(image_floats, group, cnf_forward_lds(sh), kCnfPrefer64K, n, kCnfMaxBlocks);
+  const GroupLaunch plan = group_launch_plan(image_floats, group, cnf_forward_lds(sh), kPrefer64K, n, kGroupMaxBlocks);
   if (e)
-    return cnf_with_constant<4, 8, 16>(sh.d <= 4 ? 4 : sh.d <= 8 ? 8 : 16, [&](auto dp) {
+    return with_constant<4, 8, 16>(sh.d <= 4 ? 4 : sh.d <= 8 ? 8 : 16, [&](auto dp) {
       constexpr int DP = decltype(dp)::value;
       return launch_cnf_integrate_as<2, DP, CnfHutchinsonDiv<DP>>(tape != nullptr, plan, s, z, logp, e, image, z_out,
                                                                   logp_out, tape, evals, n, sh, image_floats, table,
                                                                   t0, t1, steps, method);
     });
-  return cnf_with_constant<2, 4, 8, 16, 32>(group, [&](auto g) {
+  return with_constant<2, 4, 8, 16, 32>(group, [&](auto g) {
     constexpr int G = decltype(g)::value;
-    return launch_cnf_integrate_as<G, CnfGroup<G>::DP, CnfExactDiv>(tape != nullptr, plan, s, z, logp, e, image, z_out,
+    return launch_cnf_integrate_as<G, LaneGroup<G>::DP, CnfExactDiv>(tape != nullptr, plan, s, z, logp, e, image, z_out,
                                                                     logp_out, tape, evals, n, sh, image_floats, table,
                                                                     t0, t1, steps, method);
   });
@@ -571,14 +561,14 @@ inline bool cnf_fixed_steps(double t0, double t1, int steps, int method) {
 }
 
 // the backward kernel's table and a lane's slots: the largest block that fits, a block per tile up to the cap
-static CnfLaunch cnf_backward_plan(const CnfShape& sh, int image_floats, bool with_e, int64_t n) {
-  const CnfLds need{sizeof(double) * (size_t)cnf_table_doubles(sh), cnf_backward_lane_floats(sh), 0};
-  return cnf_launch_plan(image_floats, cnf_group(sh, with_e), need, kCnfLargestBlock, n, kCnfBackwardMaxBlocks);
+static GroupLaunch cnf_backward_plan(const CnfShape& sh, int image_floats, bool with_e, int64_t n) {
+  const GroupLds need{sizeof(double) * (size_t)cnf_table_doubles(sh), cnf_backward_lane_floats(sh), 0, 0};
+  return group_launch_plan(image_floats, cnf_group(sh, with_e), need, kLargestBlock, n, kGroupBackwardMaxBlocks);
 }
 
 // The plan of the backward launch for n rows of a net known by its widths alone; false outside the kernel's limits.
 static bool cnf_backward_query(int64_t n, int d, int layers, const int32_t* hidden, bool with_e, CnfShape* sh,
-                               CnfLaunch* plan) {
+                               GroupLaunch* plan) {
   if (n < 0 || layers > kCnfTrainMaxLayers || !cnf_shape(d, layers, hidden, 0, 0, 0, 1.f, 1.f, sh)) return false;
   *plan = cnf_backward_plan(*sh, cnf_image_floats(*sh), with_e, n);
   return plan->threads != 0;
@@ -602,7 +592,7 @@ extern "C" int fc_cnf_field_train(const float* y, const float* e, const float* i
 
 extern "C" int fc_cnf_field_backward_rows(int32_t d, int32_t layers, const int32_t* hidden, int32_t with_e) {
   fc::CnfShape sh;
-  fc::CnfLaunch plan;
+  fc::GroupLaunch plan;
   if (!fc::cnf_backward_query(0, d, layers, hidden, with_e != 0, &sh, &plan)) return -1;
   return plan.threads / fc::cnf_group(sh, with_e != 0);
 }
@@ -610,7 +600,7 @@ extern "C" int fc_cnf_field_backward_rows(int32_t d, int32_t layers, const int32
 extern "C" int fc_cnf_field_backward_workspace(int64_t n, int32_t d, int32_t layers, const int32_t* hidden,
                                                int32_t with_e) {
   fc::CnfShape sh;
-  fc::CnfLaunch plan;
+  fc::GroupLaunch plan;
   if (!fc::cnf_backward_query(n, d, layers, hidden, with_e != 0, &sh, &plan)) return -1;
   return (int)(2 * plan.grid * fc::cnf_image_floats(sh));
 }
@@ -630,16 +620,14 @@ extern "C" int fc_cnf_field_backward(const float* y, const float* e, const float
   if (!y || !image || !g_dy || !g_negdiv || !g_y || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 7))
     return hipErrorInvalidValue;
   double* partial = static_cast<double*>(workspace);
-  const fc::CnfLaunch plan = fc::cnf_backward_plan(sh, image_floats, e != nullptr, n);
-  const int launched = fc::cnf_with_constant<2, 4, 8, 16, 32>(fc::cnf_group(sh, e != nullptr), [&](auto g) {
-    return fc::cnf_launch<&fc::cnf_backward_kernel<decltype(g)::value>>(
+  const fc::GroupLaunch plan = fc::cnf_backward_plan(sh, image_floats, e != nullptr, n);
+  const int launched = fc::with_constant<2, 4, 8, 16, 32>(fc::cnf_group(sh, e != nullptr), [&](auto g) {
+    return fc::group_launch<&fc::cnf_backward_kernel<decltype(g)::value>>(
         plan, s, y, e, image, g_dy, g_negdiv, g_y, partial, n, sh, image_floats, fc::cnf_table_doubles(sh),
         fc::cnf_backward_lane_floats(sh), t, t_dev);
   });
   if (launched != hipSuccess) return launched;
-  hipLaunchKernelGGL(fc::cnf_backward_sum_kernel, dim3((unsigned)((image_floats + 255) / 256)), dim3(256), 0, s,
-                     partial, g_image, (int)plan.grid, image_floats, sh.scale);
-  return hipGetLastError();
+  return fc::launch_partial_sum(partial, g_image, (int)plan.grid, image_floats, sh.scale, s);  // scale_output
 }
 
 extern "C" int fc_cnf_field(const float* y, const float* image, float* dy, float* negdiv, float* evals, int64_t n,
@@ -692,7 +680,7 @@ extern "C" int fc_cnf_integrate_train(const float* z, const float* logp, const f
 extern "C" int fc_cnf_integrate_backward_workspace(int64_t n, int32_t d, int32_t layers, const int32_t* hidden,
                                                    int32_t with_e) {
   fc::CnfShape sh;
-  fc::CnfLaunch plan;
+  fc::GroupLaunch plan;
   if (!fc::cnf_backward_query(n, d, layers, hidden, with_e != 0, &sh, &plan)) return -1;
   if (n > (INT32_MAX / 8) / d) return -1;
   const int64_t floats = 2 * (plan.grid * (int64_t)fc::cnf_image_floats(sh) + 3 * n * (int64_t)d);
@@ -715,16 +703,14 @@ extern "C" int fc_cnf_integrate_backward(const float* tape, const float* e, cons
   if (n == 0) return hipMemsetAsync(g_image, 0, sizeof(float) * (size_t)image_floats, s);
   if (!tape || !image || !g_z_out || !g_logp_out || !g_z || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 7))
     return hipErrorInvalidValue;
-  const fc::CnfLaunch plan = fc::cnf_backward_plan(sh, image_floats, e != nullptr, n);
+  const fc::GroupLaunch plan = fc::cnf_backward_plan(sh, image_floats, e != nullptr, n);
   double* partial = static_cast<double*>(workspace);
   double* planes = partial + (size_t)plan.grid * (size_t)image_floats;
-  const int launched = fc::cnf_with_constant<2, 4, 8, 16, 32>(fc::cnf_group(sh, e != nullptr), [&](auto g) {
-    return fc::cnf_launch<&fc::cnf_solve_backward_kernel<decltype(g)::value>>(
+  const int launched = fc::with_constant<2, 4, 8, 16, 32>(fc::cnf_group(sh, e != nullptr), [&](auto g) {
+    return fc::group_launch<&fc::cnf_solve_backward_kernel<decltype(g)::value>>(
         plan, s, tape, e, image, g_z_out, g_logp_out, g_z, partial, planes, n, sh, image_floats,
         fc::cnf_table_doubles(sh), fc::cnf_backward_lane_floats(sh), t0, t1, steps, method);
   });
   if (launched != hipSuccess) return launched;
-  hipLaunchKernelGGL(fc::cnf_backward_sum_kernel, dim3((unsigned)((image_floats + 255) / 256)), dim3(256), 0, s,
-                     partial, g_image, (int)plan.grid, image_floats, sh.scale);
-  return hipGetLastError();
+  return fc::launch_partial_sum(partial, g_image, (int)plan.grid, image_floats, sh.scale, s);  // scale_output
 }

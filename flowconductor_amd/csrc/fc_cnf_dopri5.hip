@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void cnf_dopri5_kernel(const float* __restrict
                                                          int image_floats, int strip_doubles, double t0, double t1,
                                                          double atol, double rtol, double first_step,
                                                          int max_attempts) {
-  constexpr int DP = CnfGroup<G>::DP;
+  constexpr int DP = LaneGroup<G>::DP;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const CnfBlock b = cnf_block<G>(lds, image, image_floats, 0, strip_doubles, n, sh);
   __syncthreads();  // the only barrier (cnf_block has none): the tile loop below has none
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void cnf_dopri5_kernel(const float* __restrict
 
   for (int64_t tile = blockIdx.x; tile < b.tiles; tile += gridDim.x) {
     bool live;
-    const int64_t row = cnf_tile_row(b, tile, n, live);
+    const int64_t row = tile_row(b, tile, n, live);
     double y = 0.0;
     if (s < d) y = (double)z[row * d + s];
     if (s == d && logp) y = (double)logp[row];
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void cnf_dopri5_kernel(const float* __restrict
 }
 
 // a strip of the widest layer's gates per row in place of the block's time table, and the two ping-pong columns
-static CnfLds cnf_dopri5_lds(const CnfShape& sh) { return {0, 2 * cnf_max_width(sh), cnf_pad4(cnf_max_width(sh))}; }
+static GroupLds cnf_dopri5_lds(const CnfShape& sh) { return {0, 2 * cnf_max_width(sh), pad4(cnf_max_width(sh)), 0}; }
 
 }  // namespace fc
 
@@ -232,11 +232,11 @@ extern "C" int fc_cnf_dopri5(const float* z, const float* logp, const float* ima
     return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!fc::cnf_operands(z, image, z_out, logp_out) || !attempts) return hipErrorInvalidValue;
-  const fc::CnfLds need = fc::cnf_dopri5_lds(sh);
-  const fc::CnfLaunch plan =
-      fc::cnf_launch_plan(image_floats, fc::cnf_group(sh), need, fc::kCnfPrefer64K, n, fc::kCnfMaxBlocks);
-  return fc::cnf_with_constant<2, 4, 8, 16, 32>(fc::cnf_group(sh), [&](auto g) {
-    return fc::cnf_launch<&fc::cnf_dopri5_kernel<decltype(g)::value>>(
+  const fc::GroupLds need = fc::cnf_dopri5_lds(sh);
+  const fc::GroupLaunch plan =
+      fc::group_launch_plan(image_floats, fc::cnf_group(sh), need, fc::kPrefer64K, n, fc::kGroupMaxBlocks);
+  return fc::with_constant<2, 4, 8, 16, 32>(fc::cnf_group(sh), [&](auto g) {
+    return fc::group_launch<&fc::cnf_dopri5_kernel<decltype(g)::value>>(
         plan, static_cast<hipStream_t>(stream), z, logp, image, z_out, logp_out, attempts, evals, n, sh, image_floats,
         need.row_doubles, t0, t1, atol, rtol, first_step, max_attempts);
   });

@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include "fc_device.h"
 #include "fc_math.h"
+#include "fc_partial_sum.h"
 #include "../../include/flowcon_hip.h"
 
 namespace fc {
@@ -166,8 +167,8 @@ __device__ __forceinline__ float wave_sum(float v) {
 // One batch-shared row [D, 3S]: its gradient is the sum over the batch.  The row sits in LDS; a wave takes 64 consecutive
 // samples and walks the D dims, so that its 64 lanes hold the same (dim, sigmoid) of 64 samples: a butterfly sum, then one
 // lane adds the three totals onto the wave's own accumulator row in LDS.  The four accumulator rows are added in wave order
-// into row blockIdx.x of `partial`; ds_backward_finish_kernel adds the rows in order.  No atomics: the order of every
-// floating-point sum is fixed by (N, D) alone.
+// into row blockIdx.x of `partial`; partial_sum_kernel (fc_partial_sum.h) adds the rows in order.  No atomics: the order
+// of every floating-point sum is fixed by (N, D) alone.
 __global__ __launch_bounds__(256) void ds_backward_shared_kernel(DsBwdArgs a, float* __restrict__ partial) {
   extern __shared__ float ds_smem[];
   const int S = a.S, P = 3 * S, D = a.D, rowlen = D * P;
@@ -206,15 +207,6 @@ __global__ __launch_bounds__(256) void ds_backward_shared_kernel(DsBwdArgs a, fl
     partial[(size_t)blockIdx.x * rowlen + i] = ((a0[i] + a0[rowlen + i]) + a0[2 * rowlen + i]) + a0[3 * rowlen + i];
 }
 
-__global__ __launch_bounds__(256) void ds_backward_finish_kernel(const float* __restrict__ partial, float* __restrict__ out,
-                                                                 int rows, int rowlen) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rowlen) return;
-  float tot = 0.f;
-  for (int r = 0; r < rows; ++r) tot += partial[(size_t)r * rowlen + i];
-  out[i] = tot;
-}
-
 inline int ds_shared_rows(int64_t n, int d, int n_sigmoids) {
   const int64_t rowlen = (int64_t)d * 3 * n_sigmoids;
   if (n <= 0 || d <= 0 || n_sigmoids <= 0 || (size_t)(5 * rowlen) * sizeof(float) > kDsSharedMaxLds) return 0;
@@ -249,9 +241,7 @@ extern "C" int fc_deep_sigmoid_backward(const float* x, const float* raw, const 
                        a, partial);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fc::ds_backward_finish_kernel, dim3((unsigned)((rowlen + 255) / 256)), dim3(256), 0, s, partial,
-                       grad_raw, rows, rowlen);
-    return hipGetLastError();
+    return fc::launch_partial_sum<float>(partial, grad_raw, rows, rowlen, 1.f, s);
   }
   int ts = P | 1;                      // odd stride (conflict-free per-lane rows)
   const size_t wave_bytes = (size_t)64 * ts * sizeof(float);

@@ -36,12 +36,17 @@
 // Backward: the forward's lane groups and LDS layout plus an adjoint state of the same shape.  A tile recomputes the
 // streams through ires_net, inverts I + s J inside the lane group (the cotangent of column j of J is gl s (A^-T)[:, j]),
 // and sweeps the layers from the last; every block adds its parameter-gradient sums onto one image-shaped float64
-// partial, each entry by one thread in a fixed order, and a second kernel adds the partials in block order (no
-// atomics).  See DESIGN.md, "iResBlock training".
+// partial, each entry by one thread in a fixed order, and partial_sum_kernel (fc_partial_sum.h) adds the partials in
+// block order (no atomics).  See DESIGN.md, "iResBlock training".
+//
+// The lane groups, the block set-up (GroupBlock), the float64 weight sums and the launch plan are the lane-group
+// scaffold's (fc_lane_group.h), which the CNF kernels share; this file keeps the image layout, the activations, the
+// concatenating dense layers, the LU, the fixed-point loop and the reverse sweep.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/flowcon_hip.h"
-#include "fc_device.h"
+#include "fc_lane_group.h"
+#include "fc_partial_sum.h"
 
 namespace fc {
 
@@ -49,16 +54,14 @@ struct IresShape {
   int d, e, depth, growth, out_ch, concat, act, wtot;
 };
 
-__host__ __device__ inline int ires_pad4(int v) { return (v + 3) & ~3; }
-
 __host__ __device__ inline int ires_image_floats(const IresShape& sh) {
   int total = 4, w_in = sh.d + sh.e;
-  const int op = ires_pad4(sh.out_ch);
+  const int op = pad4(sh.out_ch);
   for (int l = 0; l < sh.depth; ++l) {
     total += 4 + op + w_in * op;
     w_in += sh.growth;
   }
-  const int dp = ires_pad4(sh.d);
+  const int dp = pad4(sh.d);
   return total + dp + w_in * dp;
 }
 
@@ -163,7 +166,7 @@ __device__ __forceinline__ void ires_act(int act, double t, double p0, double p1
 template <int G, int DP>
 __device__ __forceinline__ void ires_net(const float* img, float* mine, int T, const IresShape& sh, int s, double p0,
                                          double p1, double (&out)[DP]) {
-  const int op = ires_pad4(sh.out_ch), dp = ires_pad4(sh.d);
+  const int op = pad4(sh.out_ch), dp = pad4(sh.d);
   const bool value = G == 1 || s == 0;
   int w_in = sh.d + sh.e;
   const float* p = img + 4;
@@ -174,16 +177,7 @@ __device__ __forceinline__ void ires_net(const float* img, float* mine, int T, c
     const float* wt = bias + op;
     for (int o = 0; o < op; o += 4) {
       double sum[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) sum[c] = value ? (double)bias[o + c] : 0.0;  // a tangent has no bias
-      for (int k = 0; k < w_in; ++k) {
-        const double v = (double)mine[k * T];
-        const float4 w4 = *reinterpret_cast<const float4*>(wt + k * op + o);
-        sum[0] = fma((double)w4.x, v, sum[0]);
-        sum[1] = fma((double)w4.y, v, sum[1]);
-        sum[2] = fma((double)w4.z, v, sum[2]);
-        sum[3] = fma((double)w4.w, v, sum[3]);
-      }
+      weight_sum4(wt, mine, T, w_in, op, o, value, [&](int oc) { return (double)bias[oc]; }, sum);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const double pre = G == 1 ? sum[c] : __shfl(sum[c], 0, G);  // the value stream's pre-activation
@@ -229,25 +223,18 @@ __global__ __launch_bounds__(256) void iresnet_forward_kernel(const float* __res
                                                               const float* __restrict__ image, float* __restrict__ y,
                                                               float* __restrict__ logabsdet, int64_t n, IresShape sh,
                                                               int image_floats) {
-  constexpr int DMAX = G == 32 ? 16 : G - 1;
-  constexpr int DP = (DMAX + 3) & ~3;
+  constexpr int DMAX = LaneGroup<G>::DMAX, DP = LaneGroup<G>::DP;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* img = lds;
-  float* st = lds + image_floats;
-  const int T = blockDim.x, tid = threadIdx.x;
-  for (int i = tid; i < image_floats; i += T) img[i] = image[i];
+  const GroupBlock b = group_block<G>(lds, image, image_floats, 0, 0, n);
   __syncthreads();
+  const float* img = b.img;
+  float* mine = b.mine;
   const double p0 = (double)img[0], p1 = (double)img[1];
-  const int d = sh.d, e = sh.e;
-  const int s = tid % G;
-  const int rows_per_block = T / G;
-  const int64_t tiles = (n + rows_per_block - 1) / rows_per_block;
-  float* mine = st + tid;
+  const int T = b.T, d = sh.d, e = sh.e, s = b.s;
 
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    int64_t row = tile * rows_per_block + tid / G;
-    const bool live = row < n;
-    if (!live) row = n - 1;  // every lane runs (the shuffles need them); only live rows are stored
+  for (int64_t tile = blockIdx.x; tile < b.tiles; tile += gridDim.x) {
+    bool live;
+    const int64_t row = tile_row(b, tile, n, live);
     const float* xr = x + row * d;
     for (int k = 0; k < d; ++k) mine[k * T] = s == 0 ? xr[k] : (k == s - 1 ? 1.f : 0.f);
     for (int k = 0; k < e; ++k) mine[(d + k) * T] = s == 0 ? extra[row * e + k] : 0.f;
@@ -329,21 +316,17 @@ __global__ __launch_bounds__(256) void iresnet_inverse_kernel(const float* __res
                                                               int image_floats, int max_iterations, float atol,
                                                               float rtol) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* img = lds;
-  float* st = lds + image_floats;
-  const int T = blockDim.x, tid = threadIdx.x;
-  for (int i = tid; i < image_floats; i += T) img[i] = image[i];
+  const GroupBlock b = group_block<1>(lds, image, image_floats, 0, 0, n);  // a group of one lane: a row per thread
   __syncthreads();
+  const float* img = b.img;
+  float* mine = b.mine;
   const double p0 = (double)img[0], p1 = (double)img[1];
-  const int d = sh.d;
-  const int64_t tiles = (n + T - 1) / T;
-  float* mine = st + tid;
+  const int T = b.T, tid = b.tid, d = sh.d;
   uint32_t most = 0;
 
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    int64_t row = tile * T + tid;
-    const bool live = row < n;
-    if (!live) row = n - 1;
+  for (int64_t tile = blockIdx.x; tile < b.tiles; tile += gridDim.x) {
+    bool live;
+    const int64_t row = tile_row(b, tile, n, live);
     const float* er = extra + row * sh.e;  // read only when e > 0
     const double sc = scale ? (double)scale[row] : 1.0;
     float yv[DP], tol[DP], xc[DP];
@@ -394,14 +377,6 @@ __global__ __launch_bounds__(256) void iresnet_inverse_kernel(const float* __res
 
 // ---- backward: recompute the streams, invert I + s J, sweep the layers from the last ----------------------------------
 
-// Sum over the lanes of a row group / of a wave, in the fixed order of the butterfly.
-template <int W>
-__device__ __forceinline__ double ires_lane_sum(double v) {
-#pragma unroll
-  for (int off = W / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, W);
-  return v;
-}
-
 // part[at + k * ld + o] += sum over the block's streams of lhs[o][t] * st[k][t] for k < rows, and the bias entries
 // part[bias_at + o] += sum over the VALUE streams of lhs[o][t] (a tangent has no bias), o < cols.  One (k, o) per
 // thread and pass; the sum over t is a float64 fma chain that starts at the thread's own lane (conflict-free LDS
@@ -438,36 +413,29 @@ __global__ __launch_bounds__(256) void iresnet_backward_kernel(
     const float* __restrict__ image, const float* __restrict__ gy, const float* __restrict__ gl,
     float* __restrict__ dx, float* __restrict__ dextra, float* __restrict__ dscale, double* __restrict__ ws, int64_t n,
     IresShape sh, int image_floats) {
-  constexpr int DMAX = G == 32 ? 16 : G - 1;
-  constexpr int DP = (DMAX + 3) & ~3;
+  constexpr int DMAX = LaneGroup<G>::DMAX, DP = LaneGroup<G>::DP;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int T = blockDim.x, tid = threadIdx.x;
-  const int d = sh.d, e = sh.e, op = ires_pad4(sh.out_ch), dp = ires_pad4(d), wtot = sh.wtot;
-  float* img = lds;
-  float* st = lds + image_floats;
+  const GroupBlock b = group_block<G>(lds, image, image_floats, 0, 0, n);
+  const int T = b.T, tid = b.tid, s = b.s;
+  const int d = sh.d, e = sh.e, op = pad4(sh.out_ch), dp = pad4(d), wtot = sh.wtot;
+  const float* img = b.img;
+  float* st = b.st;
   float* adj = st + wtot * T;
   float* cb = adj + wtot * T;
   double* red = reinterpret_cast<double*>(cb + dp * T);
   double* part = ws + (size_t)blockIdx.x * image_floats;
-  for (int i = tid; i < image_floats; i += T) {
-    img[i] = image[i];
-    part[i] = 0.0;
-  }
+  for (int i = tid; i < image_floats; i += T) part[i] = 0.0;
   __syncthreads();
   const double p0 = (double)img[0], p1 = (double)img[1];
-  const int s = tid % G;
   const bool value = s == 0;
-  const int rows_per_block = T / G;
-  const int64_t tiles = (n + rows_per_block - 1) / rows_per_block;
-  float* mine = st + tid;
+  float* mine = b.mine;
   float* adjm = adj + tid;
   const int final_at = image_floats - dp - wtot * dp;
   double dp0 = 0.0, dp1 = 0.0;
 
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    int64_t row = tile * rows_per_block + tid / G;
-    const bool live = row < n;
-    if (!live) row = n - 1;  // every lane runs; a row beyond the batch carries zero cotangents
+  for (int64_t tile = blockIdx.x; tile < b.tiles; tile += gridDim.x) {
+    bool live;  // a row beyond the batch carries zero cotangents
+    const int64_t row = tile_row(b, tile, n, live);
     const float* xr = x + row * d;
     for (int k = 0; k < d; ++k) mine[k * T] = value ? xr[k] : (k == s - 1 ? 1.f : 0.f);
     for (int k = 0; k < e; ++k) mine[(d + k) * T] = value ? extra[row * e + k] : 0.f;
@@ -549,7 +517,7 @@ __global__ __launch_bounds__(256) void iresnet_backward_kernel(
           ds = fma(glv * inv_row, jc[i], ds);
         }
       }
-      ds = ires_lane_sum<G>(ds);  // <gy, g> + gl tr(A^-1 J)
+      ds = lane_sum<G>(ds);  // <gy, g> + gl tr(A^-1 J)
       if (value && live && dscale) dscale[row] = (float)ds;
       __syncthreads();
     }
@@ -597,16 +565,7 @@ __global__ __launch_bounds__(256) void iresnet_backward_kernel(
       }
       for (int o = 0; o < op; o += 4) {
         double sum[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) sum[q] = value ? (double)bias[o + q] : 0.0;
-        for (int k = 0; k < w_in; ++k) {
-          const double v = (double)mine[k * T];
-          const float4 w4 = *reinterpret_cast<const float4*>(wt + k * op + o);
-          sum[0] = fma((double)w4.x, v, sum[0]);
-          sum[1] = fma((double)w4.y, v, sum[1]);
-          sum[2] = fma((double)w4.z, v, sum[2]);
-          sum[3] = fma((double)w4.w, v, sum[3]);
-        }
+        weight_sum4(wt, mine, T, w_in, op, o, value, [&](int oc) { return (double)bias[oc]; }, sum);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const double pre = __shfl(sum[q], 0, G);
@@ -636,14 +595,14 @@ __global__ __launch_bounds__(256) void iresnet_backward_kernel(
               dp1 += eta2 * u * (f1.df_p1 * a1 - f2.df_p1 * a2);
             }
             // the value stream's pre-activation also moves every tangent through f''
-            bend = ires_lane_sum<G>(bend);
+            bend = lane_sum<G>(bend);
             if (value) apre += bend;
             adjm[(w_in + o + q) * T] = (float)apre;
           }
         }
       }
-      de1 = ires_lane_sum<64>(de1);
-      de2 = ires_lane_sum<64>(de2);
+      de1 = lane_sum<64>(de1);
+      de2 = lane_sum<64>(de2);
       if ((tid & 63) == 0) {
         red[2 * (tid >> 6)] = de1;
         red[2 * (tid >> 6) + 1] = de2;
@@ -677,8 +636,8 @@ __global__ __launch_bounds__(256) void iresnet_backward_kernel(
     }
   }
 
-  dp0 = ires_lane_sum<64>(dp0);
-  dp1 = ires_lane_sum<64>(dp1);
+  dp0 = lane_sum<64>(dp0);
+  dp1 = lane_sum<64>(dp1);
   if ((tid & 63) == 0) {
     red[2 * (tid >> 6)] = dp0;
     red[2 * (tid >> 6) + 1] = dp1;
@@ -692,22 +651,9 @@ __global__ __launch_bounds__(256) void iresnet_backward_kernel(
   }
 }
 
-// dimage[i] = the blocks' partials added in block order
-__global__ __launch_bounds__(256) void iresnet_backward_reduce_kernel(const double* __restrict__ ws, int blocks,
-                                                                      int image_floats, float* __restrict__ dimage) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= image_floats) return;
-  double sum = 0.0;
-  for (int b = 0; b < blocks; ++b) sum += ws[(size_t)b * image_floats + i];
-  dimage[i] = (float)sum;
-}
+// ---- entry and launch -------------------------------------------------------------------------------------------------
 
-// ---- launch ---------------------------------------------------------------------------------------------------------
-
-constexpr int kIresLdsLimit = 128 * 1024;
-constexpr int kIresMaxBlocks = 2048;
-
-static bool ires_shape(int d, int e, int depth, int growth, int act, int image_floats, IresShape* sh) {
+static bool ires_shape(int d, int e, int depth, int growth, int act, IresShape* sh) {
   if (d < 1 || d > FC_IRES_MAX_DIM || e < 0 || depth < 1 || depth > FC_IRES_MAX_DEPTH || growth < 1) return false;
   if (act < 0 || act > FC_IRES_ACT_LEAKY_LSWISH) return false;
   const bool concat = act == FC_IRES_ACT_CLIPSWISH || act == FC_IRES_ACT_CSIN;
@@ -722,101 +668,27 @@ static bool ires_shape(int d, int e, int depth, int growth, int act, int image_f
   sh->out_ch = concat ? growth / 2 : growth;
   sh->act = act;
   sh->wtot = (int)wtot;
-  return ires_image_floats(*sh) == image_floats;
+  return true;
 }
 
-// the largest block (256, 128, 64 threads) whose image + state fits 64 KiB, else 64 threads (<= 128 KiB by the limits)
-static int ires_threads(const IresShape& sh, int image_floats, int min_threads, size_t* lds) {
-  int threads = 256;
-  for (;; threads >>= 1) {
-    *lds = sizeof(float) * ((size_t)image_floats + (size_t)sh.wtot * threads);
-    if (*lds <= 64 * 1024 || threads <= 64 || threads <= min_threads) break;
-  }
-  return threads;
+// what every launching entry point starts with: a row count, a net within the limits, the image it says
+static bool ires_entry(int64_t n, int d, int e, int depth, int growth, int act, int image_floats, IresShape* sh) {
+  return n >= 0 && ires_shape(d, e, depth, growth, act, sh) && ires_image_floats(*sh) == image_floats;
 }
 
-template <int G>
-static int launch_ires_forward(const float* x, const float* extra, const float* scale, const float* image, float* y,
-                               float* logabsdet, int64_t n, const IresShape& sh, int image_floats, hipStream_t s) {
-  size_t lds;
-  const int threads = ires_threads(sh, image_floats, G, &lds);
-  if (lds > (size_t)kIresLdsLimit) return hipErrorInvalidConfiguration;
-  static PerDeviceOnce once;
-  const hipError_t e = ensure_max_dynamic_lds(once, reinterpret_cast<const void*>(&iresnet_forward_kernel<G>),
-                                              kIresLdsLimit);
-  if (e != hipSuccess) return e;
-  const int rows = threads / G;
-  int64_t grid = (n + rows - 1) / rows;
-  if (grid > kIresMaxBlocks) grid = kIresMaxBlocks;
-  hipLaunchKernelGGL((iresnet_forward_kernel<G>), dim3((unsigned)grid), dim3(threads), lds, s, x, extra, scale, image,
-                     y, logabsdet, n, sh, image_floats);
-  return hipGetLastError();
+// The state columns of the forward (group lanes a row) and of the inverse (group 1: a row per thread).  The widest net
+// the limits admit needs 67.5 KiB at 64 threads; a plan that did not fit comes back with 0 threads, which group_launch
+// answers with an error.
+static GroupLaunch ires_plan(const IresShape& sh, int image_floats, int group, int64_t n) {
+  return group_launch_plan(image_floats, group, GroupLds{0, sh.wtot, 0, 0}, kPrefer64K, n, kGroupMaxBlocks);
 }
 
-template <int DP>
-static int launch_ires_inverse(const float* y, const float* extra, const float* scale, const float* image, float* x,
-                               uint32_t* max_iters, int64_t n, const IresShape& sh, int image_floats,
-                               int max_iterations, float atol, float rtol, hipStream_t s) {
-  size_t lds;
-  const int threads = ires_threads(sh, image_floats, 64, &lds);
-  if (lds > (size_t)kIresLdsLimit) return hipErrorInvalidConfiguration;
-  static PerDeviceOnce once;
-  const hipError_t e = ensure_max_dynamic_lds(once, reinterpret_cast<const void*>(&iresnet_inverse_kernel<DP>),
-                                              kIresLdsLimit);
-  if (e != hipSuccess) return e;
-  int64_t grid = (n + threads - 1) / threads;
-  if (grid > kIresMaxBlocks) grid = kIresMaxBlocks;
-  hipLaunchKernelGGL((iresnet_inverse_kernel<DP>), dim3((unsigned)grid), dim3(threads), lds, s, y, extra, scale, image,
-                     x, max_iters, n, sh, image_floats, max_iterations, atol, rtol);
-  return hipGetLastError();
-}
-
-constexpr int kIresBackwardBlocks = 256;
-
-// the backward's LDS: image, state, adjoint state, dp cotangent rows and two float64 words per wave.  The block is
-// chosen like the forward's: the largest of 256 / 128 / 64 threads (at least one row group) that stays within 64 KiB,
-// else 64 threads.  Worst case (d 16, width 128, 8692-float image): 4 (8692 + 272 * 64) + 16 = 104 416 bytes.
-static int ires_backward_threads(const IresShape& sh, int image_floats, int min_threads, size_t* lds) {
-  int threads = 256;
-  for (;; threads >>= 1) {
-    *lds = sizeof(float) * ((size_t)image_floats + (size_t)(2 * sh.wtot + ires_pad4(sh.d)) * threads) +
-           sizeof(double) * 2 * (threads / 64);
-    if (*lds <= 64 * 1024 || threads <= 64 || threads <= min_threads) break;
-  }
-  return threads;
-}
-
-static int ires_group(int d) { return d < 2 ? 2 : d < 4 ? 4 : d < 8 ? 8 : d < 16 ? 16 : 32; }
-
-static int64_t ires_backward_grid(int64_t n, const IresShape& sh, int image_floats, int max_blocks) {
-  size_t lds;
-  const int g = ires_group(sh.d);
-  const int rows = ires_backward_threads(sh, image_floats, g, &lds) / g;
-  const int64_t tiles = (n + rows - 1) / rows;
-  const int64_t cap = max_blocks > 0 && max_blocks < kIresBackwardBlocks ? max_blocks : kIresBackwardBlocks;
-  return tiles < cap ? tiles : cap;
-}
-
-template <int G>
-static int launch_ires_backward(const float* x, const float* extra, const float* scale, const float* image,
-                                const float* gy, const float* gl, float* dx, float* dextra, float* dscale,
-                                float* dimage, double* ws, int64_t n, const IresShape& sh, int image_floats,
-                                int max_blocks, hipStream_t s) {
-  size_t lds;
-  const int threads = ires_backward_threads(sh, image_floats, G, &lds);
-  if (lds > (size_t)kIresLdsLimit) return hipErrorInvalidConfiguration;
-  static PerDeviceOnce once;
-  const hipError_t e = ensure_max_dynamic_lds(once, reinterpret_cast<const void*>(&iresnet_backward_kernel<G>),
-                                              kIresLdsLimit);
-  if (e != hipSuccess) return e;
-  const int64_t grid = ires_backward_grid(n, sh, image_floats, max_blocks);
-  hipLaunchKernelGGL((iresnet_backward_kernel<G>), dim3((unsigned)grid), dim3(threads), lds, s, x, extra, scale, image,
-                     gy, gl, dx, dextra, dscale, ws, n, sh, image_floats);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(iresnet_backward_reduce_kernel, dim3((unsigned)((image_floats + 255) / 256)), dim3(256), 0, s, ws,
-                     (int)grid, image_floats, dimage);
-  return hipGetLastError();
+// The backward's LDS: state, adjoint state, dp cotangent rows and two float64 words per wave.  Worst case (d 16, width
+// 128, 8692-float image): 4 (8692 + 272 * 64) + 16 = 104 416 bytes.  The workspace is a partial per block of this grid.
+static GroupLaunch ires_backward_plan(const IresShape& sh, int image_floats, int64_t n, int max_blocks) {
+  const int cap = max_blocks > 0 && max_blocks < kGroupBackwardMaxBlocks ? max_blocks : kGroupBackwardMaxBlocks;
+  return group_launch_plan(image_floats, lane_group(sh.d), GroupLds{0, 2 * sh.wtot + pad4(sh.d), 0, 2}, kPrefer64K, n,
+                           cap);
 }
 
 }  // namespace fc
@@ -824,19 +696,13 @@ static int launch_ires_backward(const float* x, const float* extra, const float*
 extern "C" int fc_iresnet_backward_workspace(int64_t n, int32_t d, int32_t e, int32_t depth, int32_t growth,
                                              int32_t activation, int32_t max_blocks) {
   fc::IresShape sh;
-  sh.d = d;
-  sh.e = e;
-  sh.depth = depth;
-  sh.growth = growth;
-  const bool concat = activation == FC_IRES_ACT_CLIPSWISH || activation == FC_IRES_ACT_CSIN;
-  sh.out_ch = concat ? growth / 2 : growth;
-  if (n < 0 || d < 1 || d > FC_IRES_MAX_DIM || e < 0 || e > FC_IRES_MAX_WIDTH || depth < 1 ||
-      depth > FC_IRES_MAX_DEPTH || growth < 1 || growth > FC_IRES_MAX_WIDTH)
-    return -1;
-  if (!fc::ires_shape(d, e, depth, growth, activation, fc::ires_image_floats(sh), &sh)) return -1;
+  // (ires_shape alone rejects an e or a growth past the width limit, before anything is computed from them; the two
+  // bounds are the entry's documented ones, stated here as well)
+  if (n < 0 || e > FC_IRES_MAX_WIDTH || growth > FC_IRES_MAX_WIDTH) return -1;
+  if (!fc::ires_shape(d, e, depth, growth, activation, &sh)) return -1;
   if (n == 0) return 0;
   const int image_floats = fc::ires_image_floats(sh);
-  return (int)(fc::ires_backward_grid(n, sh, image_floats, max_blocks) * image_floats);
+  return (int)(fc::ires_backward_plan(sh, image_floats, n, max_blocks).grid * image_floats);
 }
 
 extern "C" int fc_iresnet_backward(const float* x, const float* extra, const float* scale, const float* image,
@@ -845,41 +711,34 @@ extern "C" int fc_iresnet_backward(const float* x, const float* extra, const flo
                                    int32_t growth, int32_t activation, int32_t image_floats, int32_t max_blocks,
                                    void* stream) {
   fc::IresShape sh;
-  if (n < 0 || !fc::ires_shape(d, e, depth, growth, activation, image_floats, &sh)) return hipErrorInvalidValue;
+  if (!fc::ires_entry(n, d, e, depth, growth, activation, image_floats, &sh)) return hipErrorInvalidValue;
   if (!dimage) return hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (n == 0) return hipMemsetAsync(dimage, 0, sizeof(float) * image_floats, s);
   if (!x || !image || !gy || !gl || !dx || !ws || (e > 0 && (!extra || !dextra)) || (scale && !dscale))
     return hipErrorInvalidValue;
-  if (d < 2)
-    return fc::launch_ires_backward<2>(x, extra, scale, image, gy, gl, dx, dextra, dscale, dimage, ws, n, sh,
-                                       image_floats, max_blocks, s);
-  if (d < 4)
-    return fc::launch_ires_backward<4>(x, extra, scale, image, gy, gl, dx, dextra, dscale, dimage, ws, n, sh,
-                                       image_floats, max_blocks, s);
-  if (d < 8)
-    return fc::launch_ires_backward<8>(x, extra, scale, image, gy, gl, dx, dextra, dscale, dimage, ws, n, sh,
-                                       image_floats, max_blocks, s);
-  if (d < 16)
-    return fc::launch_ires_backward<16>(x, extra, scale, image, gy, gl, dx, dextra, dscale, dimage, ws, n, sh,
-                                        image_floats, max_blocks, s);
-  return fc::launch_ires_backward<32>(x, extra, scale, image, gy, gl, dx, dextra, dscale, dimage, ws, n, sh,
-                                      image_floats, max_blocks, s);
+  const fc::GroupLaunch plan = fc::ires_backward_plan(sh, image_floats, n, max_blocks);
+  const int launched = fc::with_constant<2, 4, 8, 16, 32>(fc::lane_group(d), [&](auto g) {
+    return fc::group_launch<&fc::iresnet_backward_kernel<decltype(g)::value>>(
+        plan, s, x, extra, scale, image, gy, gl, dx, dextra, dscale, ws, n, sh, image_floats);
+  });
+  if (launched != hipSuccess) return launched;
+  return fc::launch_partial_sum(ws, dimage, (int)plan.grid, image_floats, 1.0, s);
 }
 
 extern "C" int fc_iresnet_forward(const float* x, const float* extra, const float* scale, const float* image, float* y,
                                   float* logabsdet, int64_t n, int32_t d, int32_t e, int32_t depth, int32_t growth,
                                   int32_t activation, int32_t image_floats, void* stream) {
   fc::IresShape sh;
-  if (n < 0 || !fc::ires_shape(d, e, depth, growth, activation, image_floats, &sh)) return hipErrorInvalidValue;
+  if (!fc::ires_entry(n, d, e, depth, growth, activation, image_floats, &sh)) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!x || !image || !y || !logabsdet || x == y || (e > 0 && !extra)) return hipErrorInvalidValue;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (d < 2) return fc::launch_ires_forward<2>(x, extra, scale, image, y, logabsdet, n, sh, image_floats, s);
-  if (d < 4) return fc::launch_ires_forward<4>(x, extra, scale, image, y, logabsdet, n, sh, image_floats, s);
-  if (d < 8) return fc::launch_ires_forward<8>(x, extra, scale, image, y, logabsdet, n, sh, image_floats, s);
-  if (d < 16) return fc::launch_ires_forward<16>(x, extra, scale, image, y, logabsdet, n, sh, image_floats, s);
-  return fc::launch_ires_forward<32>(x, extra, scale, image, y, logabsdet, n, sh, image_floats, s);
+  const int group = fc::lane_group(d);
+  const fc::GroupLaunch plan = fc::ires_plan(sh, image_floats, group, n);
+  return fc::with_constant<2, 4, 8, 16, 32>(group, [&](auto g) {
+    return fc::group_launch<&fc::iresnet_forward_kernel<decltype(g)::value>>(
+        plan, static_cast<hipStream_t>(stream), x, extra, scale, image, y, logabsdet, n, sh, image_floats);
+  });
 }
 
 extern "C" int fc_iresnet_inverse(const float* y, const float* extra, const float* scale, const float* image, float* x,
@@ -887,17 +746,14 @@ extern "C" int fc_iresnet_inverse(const float* y, const float* extra, const floa
                                   int32_t activation, int32_t image_floats, int32_t max_iterations, float atol,
                                   float rtol, void* stream) {
   fc::IresShape sh;
-  if (n < 0 || max_iterations < 0 || !(atol >= 0.f) || !(rtol >= 0.f)) return hipErrorInvalidValue;
-  if (!fc::ires_shape(d, e, depth, growth, activation, image_floats, &sh)) return hipErrorInvalidValue;
+  if (max_iterations < 0 || !(atol >= 0.f) || !(rtol >= 0.f)) return hipErrorInvalidValue;
+  if (!fc::ires_entry(n, d, e, depth, growth, activation, image_floats, &sh)) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!y || !image || !x || x == y || (e > 0 && !extra)) return hipErrorInvalidValue;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (d <= 4)
-    return fc::launch_ires_inverse<4>(y, extra, scale, image, x, max_iters, n, sh, image_floats, max_iterations, atol,
-                                      rtol, s);
-  if (d <= 8)
-    return fc::launch_ires_inverse<8>(y, extra, scale, image, x, max_iters, n, sh, image_floats, max_iterations, atol,
-                                      rtol, s);
-  return fc::launch_ires_inverse<16>(y, extra, scale, image, x, max_iters, n, sh, image_floats, max_iterations, atol,
-                                     rtol, s);
+  const fc::GroupLaunch plan = fc::ires_plan(sh, image_floats, 1, n);
+  return fc::with_constant<4, 8, 16>(d <= 4 ? 4 : d <= 8 ? 8 : 16, [&](auto dp) {  // the padded d
+    return fc::group_launch<&fc::iresnet_inverse_kernel<decltype(dp)::value>>(
+        plan, static_cast<hipStream_t>(stream), y, extra, scale, image, x, max_iters, n, sh, image_floats,
+        max_iterations, atol, rtol);
+  });
 }

@@ -45,6 +45,7 @@
 #include "fc_lane.h"
 #include "fc_math.h"
 #include "fc_device.h"
+#include "fc_partial_sum.h"
 #include "../../include/flowcon_hip.h"
 
 namespace fc {
@@ -452,15 +453,6 @@ __global__ __launch_bounds__(kUbThreads, 1) void umnn_backward_kernel(UmnnBwdArg
   for (int i = tid; i < G::kParams; i += kUbThreads) dst[i] = red[i];
 }
 
-// out[i] = sum over the workspace rows in index order
-__global__ __launch_bounds__(256) void umnn_backward_reduce_kernel(const float* ws, float* out, int rows, int params) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= params) return;
-  float s = 0.f;
-  for (int r = 0; r < rows; ++r) s += ws[(size_t)r * params + i];
-  out[i] = s;
-}
-
 static int64_t umnn_backward_grid(int64_t total) {
   const int64_t blocks = (total + 15) / 16;
   const int64_t need = (blocks + kUbWaves - 1) / kUbWaves;
@@ -483,9 +475,8 @@ hipError_t launch_umnn_backward(const UmnnBwdArgs& a, float* g_params, hipStream
   hipLaunchKernelGGL((umnn_backward_kernel<NL>), dim3((unsigned)grid), dim3(kUbThreads), I::kBytes, s, a);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(umnn_backward_reduce_kernel, dim3((G::kParams + 255) / 256), dim3(256), 0, s, a.ws, g_params, (int)grid,
-                     (int)G::kParams);
-  return hipGetLastError();
+  // the workspace rows added in index order
+  return (hipError_t)launch_partial_sum<float>(a.ws, g_params, (int)grid, (int)G::kParams, 1.f, s);
 }
 
 }  // namespace fc

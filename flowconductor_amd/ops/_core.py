@@ -6,6 +6,7 @@ right away, a CompositeTransform / Flow defers the read to once per cascade.  ``
 of that word) and ``KernelTimer._active`` exist here and nowhere else.
 """
 import contextlib
+import functools
 import threading
 
 import torch
@@ -208,6 +209,22 @@ def _call(name, fn, device, *args):
         for t in timers:
             t.pairs.append((start, end))
     _hip.check(code, name)
+
+
+def once_differentiable(message):
+    """Decorator for the ``backward`` of an autograd node whose gradient is a kernel autograd cannot see into: a backward
+    that is itself being recorded (``create_graph=True``) raises ``RuntimeError(message)`` before anything runs, every
+    other one runs under ``torch.autograd.function.once_differentiable``."""
+    def wrap(backward_once):
+        once = torch.autograd.function.once_differentiable(backward_once)
+
+        @functools.wraps(backward_once)
+        def backward(ctx, *grads):
+            if torch.is_grad_enabled():
+                raise RuntimeError(message)
+            return once(ctx, *grads)
+        return backward
+    return wrap
 
 
 def rq_param_count(num_bins, tails):

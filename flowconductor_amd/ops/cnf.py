@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from flowconductor_amd import _hip
-from ._core import _call, _prep_2d
+from ._core import _call, _prep_2d, once_differentiable
 
 
 CNF_MAX_DIM = 16
@@ -307,14 +307,8 @@ class _CnfFieldFunction(torch.autograd.Function):
         return dy, negdiv
 
     @staticmethod
+    @once_differentiable(CNF_DOUBLE_BACKWARD_MSG)
     def backward(ctx, g_dy, g_negdiv):
-        if torch.is_grad_enabled():
-            raise RuntimeError(CNF_DOUBLE_BACKWARD_MSG)
-        return _CnfFieldFunction._backward_once(ctx, g_dy, g_negdiv)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def _backward_once(ctx, g_dy, g_negdiv):
         y, image, e = ctx.saved_tensors
         g_y, g_image = cnf_field_backward(ctx.t, y, e, image, g_dy.contiguous(), g_negdiv.contiguous(), **ctx.kw)
         need = ctx.needs_input_grad
@@ -419,14 +413,8 @@ class _CnfSolveFunction(torch.autograd.Function):
         return z_t, logp_t.view(logp.shape)
 
     @staticmethod
+    @once_differentiable(CNF_SOLVE_DOUBLE_BACKWARD_MSG)
     def backward(ctx, g_z_out, g_logp_out):
-        if torch.is_grad_enabled():
-            raise RuntimeError(CNF_SOLVE_DOUBLE_BACKWARD_MSG)
-        return _CnfSolveFunction._backward_once(ctx, g_z_out, g_logp_out)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def _backward_once(ctx, g_z_out, g_logp_out):
         tape, image, e = ctx.saved_tensors
         g_z, g_image = cnf_integrate_backward(tape, e, image, g_z_out.contiguous(), g_logp_out.contiguous(), **ctx.kw)
         need = ctx.needs_input_grad

@@ -2,7 +2,7 @@
 import torch
 
 from flowconductor_amd import _hip
-from ._core import _call, _prep_2d
+from ._core import _call, _prep_2d, once_differentiable
 
 
 IRES_MAX_DIM = 16
@@ -151,14 +151,8 @@ class _IResNetFunction(torch.autograd.Function):
         return y, logabsdet
 
     @staticmethod
+    @once_differentiable(IRES_DOUBLE_BACKWARD_MSG)
     def backward(ctx, grad_y, grad_logabsdet):
-        if torch.is_grad_enabled():
-            raise RuntimeError(IRES_DOUBLE_BACKWARD_MSG)
-        return _IResNetFunction._backward_once(ctx, grad_y, grad_logabsdet)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def _backward_once(ctx, grad_y, grad_logabsdet):
         x, image, extra, scale = ctx.saved_tensors
         dx, dimage, dextra, dscale = iresnet_backward(x, image, *ctx.shape, grad_y.contiguous(),
                                                       grad_logabsdet.contiguous(), extra=extra, scale=scale,

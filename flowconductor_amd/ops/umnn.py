@@ -3,7 +3,7 @@ import numpy as np
 import torch
 
 from flowconductor_amd import _hip
-from ._core import LAD_STORE, _call, _logabsdet_target, _pad_to, _prep_2d, cache_key, memo
+from ._core import LAD_STORE, _call, _logabsdet_target, _pad_to, _prep_2d, cache_key, memo, once_differentiable
 from .packing import _bias_accumulator_order, _hb_perm, _hidden_layer_fragments, _pow2_scale
 
 UMNN_MAX_HIDDEN_LAYERS = 3
@@ -212,14 +212,8 @@ class _UMNNFunction(torch.autograd.Function):
         return out, lad, jac
 
     @staticmethod
+    @once_differentiable(UMNN_DOUBLE_BACKWARD_MSG)
     def backward(ctx, grad_out, grad_lad, grad_jac):
-        if torch.is_grad_enabled():
-            raise RuntimeError(UMNN_DOUBLE_BACKWARD_MSG)
-        return _UMNNFunction._backward_once(ctx, grad_out, grad_lad, grad_jac)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def _backward_once(ctx, grad_out, grad_lad, grad_jac):
         x, h, jac = ctx.saved_tensors
         cond_size, nb_steps, inverse, h_shape = ctx.meta
         fold = grad_lad.unsqueeze(1) / jac                       # logabsdet = +-sum log jac
